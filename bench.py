@@ -2,9 +2,19 @@
 """
 bench.py -- BASELINE.json's metric on BASELINE.json's configuration, on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+ms_per_step = wall time of the K steps / K, ...).  `--full` adds every figure that takes runs of its own:
+the per-phase and per-kernel timings, the rooflines built on them, the repeated regions, the stress and
+fresh-grid steps, the CPU baseline (cfg2 / cfg5), the crop-window timings and the roofline (cfg4), the
+cast route (16-bit storage).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds can be compared file by file.  The
+forward outputs repeat bit for bit from run to run; a float32 gradient does not: tiles add their partial sums
+into the result with float atomics (deform_hot.hip, deform_tile.hip), whose order varies, so it differs by a few
+ulps between runs (measured on cfg2: at most 4.8e-6 on values up to 4.9) and is compared with a tolerance.
 
 Workload (config.workload = "cfg2"): one 256^3 float32 volume per GPU, 5x5x5 displacement grid
 (sigma 5), order 3, mode 'mirror', the reference's default prefilter=True,
@@ -34,7 +44,7 @@ rank 0, the grids are broadcast, the volumes go out and the results come back po
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) and relays
 rank 0's JSON line.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a `--full` run (a plain run carries step_roofline alone):
   roofline      the DOMINANT kernel of the timed step = the kernel with the largest per-step GPU
                 time.  The level-1 launches of K1 (forward gather) and K2 (gradient scatter) are
                 both timed live with HIP events recorded by the library on the launch stream
@@ -94,7 +104,36 @@ def parse():
                     help="cfg2, N = 1: the K-step region timed this many more times behind the headline region "
                          "(median / min / max reported as `repeat_ms_per_step`; 0 = off)")
     ap.add_argument("--no-stress", action="store_true", help=argparse.SUPPRESS)      # profile collection: headline kernels only
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (phases, kernels, rooflines, repeats, stress, "
+                         "fresh grids, CPU baseline, crop window, cast route)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "a fixed seeded sample of each when all of them would exceed 64 MB)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: every file together, headers included, stays under 64 MB
+
+
+def dump_outputs(dirname, named):
+    """--dump-outputs: [(name, tensor)] -> DIR/<name>.npy.  float64 is written as float64, every other dtype as
+    float32.  Each array gets an equal share of DUMP_BYTES; one larger than its share is written flat, as the
+    elements at the sorted indices that a generator seeded with the array's position draws (no repeats): the same
+    indices on every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    named = [(k, t) for k, t in named if t is not None]
+    share = DUMP_BYTES // max(len(named), 1)
+    for i, (name, t) in enumerate(named):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        keep = share // (8 if dt == torch.float64 else 4)
+        t = t.detach()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(i).choice(t.numel(), keep, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(dt).cpu().numpy())
 
 
 def cpu_baseline(side=128):
@@ -233,10 +272,26 @@ def cfg4_main(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        fwd()
-        bwd()
+        last = None         # (the previous step's results go before the next step allocates, as when discarded)
+        last = fwd(), bwd()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("deform_grid_%d" % i, y) for i, y in enumerate(last[0])] +
+                     [("deform_grid_gradient_%d" % i, g) for i, g in enumerate(last[1])])
+    vox = float(sum(int(np.prod(o.shape)) for o in outs))
+    ms = elapsed / args.steps * 1e3
+    res = {"metric": "Mvoxels/s fwd+grad, cfg4 multi-input crop 64^3", "value": round(vox * args.steps / elapsed / 1e6, 2),
+           "unit": "Mvoxels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "cfg4: [3x%d^3 float32 image order 3 mirror, %d^3 int32 labels order 0 nearest], "
+                                  "axis [(1,2,3),(0,1,2)], crop %d^3, affine rotate 10 deg + zoom 1.1, 5x5x5 grid sigma 5, "
+                                  "prefilter on, deform_grid + deform_grid_gradient per step" % (n, n, n // 4),
+                      "parallelism": "1 GPU"},
+           "output_voxels_per_step": int(vox)}
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        return
     window = {"auto": {"deform_grid_ms": round(timed(fwd), 4), "deform_grid_gradient_ms": round(timed(bwd), 4)}}
     saved = (dgm.CROP_WINDOW_MIN_SAVING, dgm.CROP_WINDOW_MAX_FRACTION)
     try:
@@ -246,8 +301,6 @@ def cfg4_main(args):
         window["forced_off"] = {"deform_grid_ms": round(timed(fwd), 4), "deform_grid_gradient_ms": round(timed(bwd), 4)}
     finally:
         dgm.CROP_WINDOW_MIN_SAVING, dgm.CROP_WINDOW_MAX_FRACTION = saved
-    vox = float(sum(int(np.prod(o.shape)) for o in outs))
-    ms = elapsed / args.steps * 1e3
     # Algorithmic bytes of the step, SURVEY.md 8(d): "with crop use bytes(output) + bytes(source bounding box actually
     # needed)".  The box is the filter window the library computed ON THE DEVICE for this very call
     # (edhip_source_window: the source box + the filter's decay margin); it is read back here, outside every timed
@@ -280,13 +333,7 @@ def cfg4_main(args):
     grad_bytes = 4.0 * out_img + 4.0 * win_g + 24.0 * win_g + 8.0 * out_lab     # dY, dX box, K4 passes, labels
     step_bytes = fwd_bytes + grad_bytes
     whole_bytes = 2.0 * (24.0 + 4.0) * float(img.size) + 8.0 * out_img + 16.0 * out_lab
-    res = {"metric": "Mvoxels/s fwd+grad, cfg4 multi-input crop 64^3", "value": round(vox * args.steps / elapsed / 1e6, 2),
-           "unit": "Mvoxels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": "cfg4: [3x%d^3 float32 image order 3 mirror, %d^3 int32 labels order 0 nearest], "
-                                  "axis [(1,2,3),(0,1,2)], crop %d^3, affine rotate 10 deg + zoom 1.1, 5x5x5 grid sigma 5, "
-                                  "prefilter on, deform_grid + deform_grid_gradient per step" % (n, n, n // 4),
-                      "parallelism": "1 GPU"},
+    res.update({
            "roofline": {"bound": "hbm", "achieved": round(step_bytes / (ms * 1e-3) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                         "frac": round(step_bytes / (ms * 1e-3) / 1e9 / 8000.0, 4), "traffic": None,
                         "kernel": "whole step against the bytes of the source window actually filtered and read "
@@ -298,8 +345,7 @@ def cfg4_main(args):
                         "if_filtered_whole": {"algorithmic_bytes_per_step": int(whole_bytes),
                                               "note": "the reference's pipeline (deform_grid.py:155-164, 277-286) moves "
                                                       "these bytes; NOT what this step is priced on"}},
-           "crop_window": window,
-           "output_voxels_per_step": int(vox)}
+           "crop_window": window})
     print(json.dumps(res), flush=True)
 
 
@@ -324,8 +370,7 @@ def storage16_main(args):
     ed.set_reduced_precision(True)
 
     def step():
-        ed.deform_grid(X, disp, **kw)
-        ed.deform_grid_gradient(dY, disp, **kw)
+        return ed.deform_grid(X, disp, **kw), ed.deform_grid_gradient(dY, disp, **kw)
 
     def run():
         for _ in range(args.warmup):
@@ -333,17 +378,23 @@ def storage16_main(args):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = None     # (the previous step's results go before the next step allocates, as when discarded)
+            last = step()
         torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / args.steps * 1e3
+        return (time.perf_counter() - t0) / args.steps * 1e3, last
 
-    ms = run()
-    real = dgm._direct16
-    try:
-        dgm._direct16 = lambda *a, **k: False
-        ms_cast = run()
-    finally:
-        dgm._direct16 = real
+    ms, last = run()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("deform_grid", last[0]), ("deform_grid_gradient", last[1])])
+    del last
+    ms_cast = None
+    if args.full:
+        real = dgm._direct16
+        try:
+            dgm._direct16 = lambda *a, **k: False
+            ms_cast, _ = run()
+        finally:
+            dgm._direct16 = real
     vox = float(n) ** 3
     # bytes the step moves by design, per voxel: K3 (2 + 4) + 8 + 8, K1 4 + 2, K2 2 + 4, K4 8 + 8 + (4 + 2)
     direct_b, cast_b = 56.0, 64.0 + 4 * 6.0
@@ -359,9 +410,10 @@ def storage16_main(args):
                         "kernel": "whole step against the bytes it moves by design: 56 B/voxel (float32 intermediates "
                                   "between the filter passes; the cast route moves 88)",
                         "algorithmic_bytes_per_step": direct_b * vox},
-           "cast_route": {"ms_per_step": round(ms_cast, 4), "bytes_per_voxel": cast_b,
-                          "note": "the same step with torch casts around the float32 pipeline"},
            "cpu_baseline": None}
+    if ms_cast is not None:
+        res["cast_route"] = {"ms_per_step": round(ms_cast, 4), "bytes_per_voxel": cast_b,
+                             "note": "the same step with torch casts around the float32 pipeline"}
     print(json.dumps(res))
 
 
@@ -385,8 +437,8 @@ def collective_main(args, rank, world, dev, distributed):
     kw = dict(order=3, mode="mirror")
 
     def step():
-        edd.deform_batch_sharded(X, disp, scatter_from=0, gather_to=0, device=dev, **kw)
-        edd.deform_batch_sharded(dY, disp, gradient=True, scatter_from=0, gather_to=0, device=dev, **kw)
+        return (edd.deform_batch_sharded(X, disp, scatter_from=0, gather_to=0, device=dev, **kw),
+                edd.deform_batch_sharded(dY, disp, gradient=True, scatter_from=0, gather_to=0, device=dev, **kw))
 
     def fence():
         torch.cuda.synchronize()
@@ -399,13 +451,16 @@ def collective_main(args, rank, world, dev, distributed):
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = None         # (the previous step's results go before the next step allocates, as when discarded)
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:      # (the whole batch, gathered on rank 0)
+        dump_outputs(args.dump_outputs, [("deform_grid_batch", last[0]), ("deform_grid_gradient_batch", last[1])])
     if rank == 0:
         vox = float(B) * float(n) ** 3
         moved = 4.0 * vox * 4.0 * (world - 1) / max(world, 1)       # X out, Y back, dY out, dX back: float32, off-rank shards only
@@ -499,15 +554,78 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = None         # (the previous step's results go before the next step allocates, as when discarded)
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        names = ("deform_grid_batch", "deform_grid_gradient_batch") if cfg5 else ("deform_grid", "deform_grid_gradient")
+        dump_outputs(args.dump_outputs, list(zip(names, last)))
+    del last
 
-    # ---- per-phase and per-kernel timing with HIP events on the launch stream ---------------------
+    vox = float(B) * float(n) ** 3
+    ms_per_step = elapsed / args.steps * 1e3
+    step_bytes = 64.0 * vox
+    step_obj = {"bound": "hbm", "algorithmic_bytes_per_step": int(step_bytes),
+                "achieved": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1), "peak": 8000.0,
+                "unit": "GB/s", "frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / 8000.0, 4),
+                "note": "64 B/voxel = prefilter 24 + forward 8 + gradient 8 + transposed prefilter 24"}
+
+    def commit_id():
+        try:
+            import subprocess
+            return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"],
+                                           stderr=subprocess.DEVNULL).decode().strip()
+        except Exception:
+            return None
+
+    def commit_built():
+        try:
+            from elasticdeform_amd import _build_info
+            return _build_info.COMMIT
+        except Exception:
+            return None
+
+    res = None
+    if rank == 0:
+        if cfg5:
+            workload = ("cfg5 shard: %d volumes of %d^3 float32 per GPU, one 5x5x5 grid (sigma %.3g) each, "
+                        "order 3, mode mirror, prefilter on, deform_grid_batch + "
+                        "deform_grid_gradient_batch per step" % (B, n, sigma))
+        else:
+            workload = ("cfg2: 3D %dx%dx%d float32, 5x5x5 grid sigma 5, order 3, mode mirror, prefilter "
+                        "on, deform_grid + deform_grid_gradient per step, one volume per GPU" % (n, n, n))
+        res = {
+            "metric": "Mvoxels/s fwd+grad, 256^3 fp32 order=3" if not cfg5 else
+                      "Mvoxels/s fwd+grad, batch of 128^3 fp32 order=3",
+            "value": round(world * vox * args.steps / elapsed / 1e6, 2),
+            "unit": "Mvoxels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": workload,
+                       "parallelism": "%s per GPU, no collective" % ("%d volumes" % B if cfg5 else "1 volume")},
+            "step_roofline": step_obj,
+            "commit": commit_id() or commit_built(),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: per-phase and per-kernel timing with HIP events on the launch stream ---------------------
     def timed(fn, iters):
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(iters)]
@@ -590,16 +708,7 @@ def main():
     _, k3_ms = timed(lambda: dgm._filter_axes(X, vol_axes, 3, False, dev), iters)
     _, k4_ms = timed(lambda: dgm._filter_axes(dxs, vol_axes, 3, True, dev), iters)
 
-    vox = float(B) * float(n) ** 3
     algo_bytes = ALGO_BYTES_PER_VOXEL * vox
-
-    def commit_id():
-        try:
-            import subprocess
-            return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"],
-                                           stderr=subprocess.DEVNULL).decode().strip()
-        except Exception:
-            return None
 
     # HBM bytes per launch from the PMC passes (profiles/hbm_traffic.json): reported only while the kernels'
     # sources are the ones the passes were made on (hash of the files, written by tools/hbm_traffic.py)
@@ -634,13 +743,6 @@ def main():
                 "avg_launch_us": round(us, 2), "median_launch_us": round(med, 2),
                 "whole_call_avg_us": round(call_ms * 1e3, 2)}
 
-    def commit_built():
-        try:
-            from elasticdeform_amd import _build_info
-            return _build_info.COMMIT
-        except Exception:
-            return None
-
     k1_obj = kernel_obj("K1", "K1 forward deform: k1z_tile_kernel<3,false> (deform_k1z.hip, the z-walk kernel of "
                         "round 6; the tile launch of one edhip_deform gradient=0 call on the prefiltered input; "
                         "whole_call adds the geometry kernel in front of it and the fix-up kernel behind it)",
@@ -655,7 +757,6 @@ def main():
                         "(K3/K4: %.1f / %.1f us per axis pass); HBM is the bounding roofline by definition "
                         "(gather / scatter, no MFMA); both tile kernels are LDS- and issue-bound today, "
                         "see DESIGN.md 5" % (k3_ms * 1e3 / 3, k4_ms * 1e3 / 3))
-    ms_per_step = elapsed / args.steps * 1e3
     # box-to-box and run-to-run noise is a few per cent: the same K-step region REPEATS more times (outside the headline
     # number, which stays "exactly K steps after W warm-up steps"); median, minimum and maximum are reported beside it
     repeats = []
@@ -668,11 +769,6 @@ def main():
             fence()
             repeats.append((time.perf_counter() - tr) / args.steps * 1e3)
         repeats.sort()
-    step_bytes = 64.0 * vox
-    step_obj = {"bound": "hbm", "algorithmic_bytes_per_step": int(step_bytes),
-                "achieved": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1), "peak": 8000.0,
-                "unit": "GB/s", "frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / 8000.0, 4),
-                "note": "64 B/voxel = prefilter 24 + forward 8 + gradient 8 + transposed prefilter 24"}
 
     stress = None
     if rank == 0 and world == 1 and not cfg5 and not args.no_stress:
@@ -723,40 +819,16 @@ def main():
         fresh["vs_headline_ms"] = round(fresh["sigma_5"]["ms_per_step"] / ms_per_step, 3)
 
     if rank == 0:
-        if cfg5:
-            workload = ("cfg5 shard: %d volumes of %d^3 float32 per GPU, one 5x5x5 grid (sigma %.3g) each, "
-                        "order 3, mode mirror, prefilter on, deform_grid_batch + "
-                        "deform_grid_gradient_batch per step" % (B, n, sigma))
-        else:
-            workload = ("cfg2: 3D %dx%dx%d float32, 5x5x5 grid sigma 5, order 3, mode mirror, prefilter "
-                        "on, deform_grid + deform_grid_gradient per step, one volume per GPU" % (n, n, n))
-        res = {
-            "metric": "Mvoxels/s fwd+grad, 256^3 fp32 order=3" if not cfg5 else
-                      "Mvoxels/s fwd+grad, batch of 128^3 fp32 order=3",
-            "value": round(world * vox * args.steps / elapsed / 1e6, 2),
-            "unit": "Mvoxels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": workload,
-                       "parallelism": "%s per GPU, no collective" % ("%d volumes" % B if cfg5 else "1 volume")},
+        res.update({
             "roofline": dominant,
             "north_star_kernel": k1_obj,
-            "step_roofline": step_obj,
-            "commit": commit_id() or commit_built(),
             "phases_ms": {"deform_grid": round(fwd_ms, 4), "deform_grid_gradient": round(grad_ms, 4),
                           "K1_forward": round(k1_ms, 4), "K2_gradient": round(k2_ms, 4),
                           "K3_prefilter_3axes": round(k3_ms, 4),
                           "K4_prefilter_transpose_3axes": round(k4_ms, 4)},
             "fwd_only_mvox_s": round(vox / (fwd_ms * 1e-3) / 1e6, 1),
             "k1_only_mvox_s": round(vox / (k1_ms * 1e-3) / 1e6, 1),
-        }
+        })
         if repeats:
             res["repeat_ms_per_step"] = {"repeats": len(repeats), "steps_each": args.steps,
                                          "median": round(repeats[len(repeats) // 2], 4),

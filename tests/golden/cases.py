@@ -318,3 +318,35 @@ def seeded_dY(case, outputs):
 
 def x_shapes(X):
     return [x.shape for x in X] if isinstance(X, list) else X.shape
+
+
+# ---- fixed-seed sweeps whose reference results live in live_reference.npz (gen_golden.live_plan / live_deform) -------
+
+def live_plan_cases():
+    """Output offset and inverse affine of the host plan: 2D 20x30, crop, with and without affine / rotate / zoom.
+    Yields (X, crop, affine, rotate, zoom)."""
+    rng = np.random.default_rng(1)
+    X = rng.random((20, 30))
+    for rotate, zoom in ((None, None), (17.0, None), (None, 0.7), (-33, 1.3)):
+        for affine in (None, np.eye(2, 3) + rng.standard_normal((2, 3)) * 0.1):
+            yield X, (slice(2, 18), slice(5, 25)), affine, rotate, zoom
+
+
+def live_deform_cases():
+    """240 forward cases (2D and 3D, orders 0-5, every mode, four dtypes, crop + affine; cval 0.5), with a gradient seed
+    for the floating-point ones.  Yields (X, displacement, kwargs, dY or None)."""
+    rng = np.random.default_rng(123)
+    for shape, points in (((23, 31), (3, 3)), ((9, 11, 10), (2, 4, 3))):
+        for order in range(6):
+            for mode in MODES:
+                for dt in (np.float64, np.float32, np.int16, np.uint8):
+                    X = (rng.random(shape) * 100).astype(dt)
+                    disp = rng.standard_normal((len(shape),) + points) * 3
+                    crop = tuple(slice(2, s - 3) for s in shape)
+                    A = np.eye(len(shape), len(shape) + 1) + rng.standard_normal(
+                        (len(shape), len(shape) + 1)) * 0.05
+                    kw = dict(order=order, mode=mode, cval=0.5, crop=crop, affine=A)
+                    dY = None
+                    if np.dtype(dt).kind == "f":
+                        dY = rng.random(tuple(s - 5 for s in shape)).astype(dt)
+                    yield X, disp, kw, dY

@@ -5,7 +5,8 @@ Generate the golden vectors under tests/golden/ by running the REAL reference
 cases of tests/golden/cases.py.  Only runs in the build container; the fixtures it writes are
 data (inputs are re-created from seeds, only reference OUTPUTS are stored).
 
-    python tests/golden/gen_golden.py            # writes small.npz, big.npz, filters.npz, meta.json
+    python tests/golden/gen_golden.py            # writes small.npz, big.npz, filters.npz, meta.json,
+                                                 # live_reference.npz
 
 The reference has no golden vectors of its own: its tests pin results only
 relationally (vs SciPy map_coordinates, finite differences).  These fixtures pin absolute outputs,
@@ -28,16 +29,55 @@ import cases as C  # noqa: E402
 from oracle import ref_loader  # noqa: E402
 
 
+def live_plan(ref):
+    """The reference's own Python helpers on cases.live_plan_cases(): output offset and inverse affine (absent when
+    the reference computes none).  Keys plan<i>/offset, plan<i>/inverse_affine of live_reference.npz."""
+    import importlib
+    dg = importlib.import_module(ref.__name__ + ".deform_grid")
+    store = {}
+    for i, (X, crop, affine, rotate, zoom) in enumerate(C.live_plan_cases()):
+        Xs = dg._normalize_inputs(X)
+        axis, ds = dg._normalize_axis_list(None, Xs)
+        shapes, off = dg._compute_output_shapes(Xs, axis, ds, crop)
+        inv = dg._compute_inverse_affine(dg._normalize_affine(affine, axis))
+        inv = dg._apply_rotation_and_zoom(rotate, zoom, inv, [shapes[0][d] for d in axis[0]])
+        store["plan%d/offset" % i] = np.asarray(off)
+        if inv is not None:
+            store["plan%d/inverse_affine" % i] = np.asarray(inv)
+    return store
+
+
+def live_deform(ref):
+    """The reference's deform_grid / deform_grid_gradient on cases.live_deform_cases().  Keys deform<i>/out,
+    deform<i>/grad of live_reference.npz."""
+    store = {}
+    for i, (X, disp, kw, dY) in enumerate(C.live_deform_cases()):
+        store["deform%d/out" % i] = ref.deform_grid(X, disp, **kw)
+        if dY is not None:
+            store["deform%d/grad" % i] = ref.deform_grid_gradient(dY, disp, X_shape=X.shape, **kw)
+    return store
+
+
+def write_live(ref):
+    path = os.path.join(HERE, "live_reference.npz")
+    np.savez_compressed(path, **live_plan(ref), **live_deform(ref))
+    print("live_reference.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 def main():
     ref = ref_loader.load_reference()
     ext = ref_loader.load_ref_ext()
     if ref is None or ext is None:
-        print("reference not available (need /root/reference and `make -C oracle ref`); "
+        print("reference not available (need the reference sources and `make -C oracle ref`); "
               "nothing generated")
         return 0
     import scipy
     import scipy.ndimage
 
+    # GOLDEN_ONLY=live: regenerate live_reference.npz only (cases.live_plan_cases / live_deform_cases)
+    if os.environ.get("GOLDEN_ONLY") == "live":
+        write_live(ref)
+        return 0
     # GOLDEN_ONLY=small: regenerate small.npz only (the BASELINE-sized cases take minutes of CPU)
     only_small = os.environ.get("GOLDEN_ONLY") == "small"
     # GOLDEN_CASE=name: recompute that one case and merge it into the existing archive
@@ -125,6 +165,7 @@ def main():
         json.dump(meta, f, indent=1)
     for n in ("small.npz", "big.npz", "filters.npz"):
         print(n, os.path.getsize(os.path.join(HERE, n)) // 1024, "KiB")
+    write_live(ref)
     return 0
 
 

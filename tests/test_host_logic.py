@@ -4,12 +4,16 @@ to the C entry point (deform_grid.py:295-454) and how they fail.  No GPU, no lib
 Expected values come from the oracle's independent restatement (oracle/ed_oracle.py) and, in the
 build container, from the real reference.
 """
+import os
+
 import numpy as np
 import pytest
 
 from elasticdeform_amd import _host
 from oracle import ed_oracle as orc
 from oracle import ref_loader
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _plan(Xs, disp, order=3, mode="constant", cval=0.0, crop=None, axis=None, affine=None,
@@ -114,28 +118,26 @@ def test_public_api_fails_loudly_without_gpu_or_library():
         ed.deform_grid_gradient(np.zeros((4, 4)), np.zeros((2, 3, 3)), crop=(slice(0, 4),) * 2)
 
 
-@pytest.mark.skipif(ref_loader.load_reference() is None,
-                    reason="real reference only exists in the build container")
 def test_plan_matches_live_reference_helpers():
-    import importlib
+    """The plan against the reference's own helpers on the seeded cases of cases.live_plan_cases(): their results as
+    stored in tests/golden/live_reference.npz, and recomputed live where the reference sources are present."""
+    import cases as C
+    import gen_golden
+    stored = np.load(os.path.join(GOLDEN, "live_reference.npz"))
     ref = ref_loader.load_reference()
-    dg = importlib.import_module(ref.__name__ + ".deform_grid")
-    rng = np.random.default_rng(1)
-    X = rng.random((20, 30))
-    for rotate, zoom in ((None, None), (17.0, None), (None, 0.7), (-33, 1.3)):
-        for affine in (None, np.eye(2, 3) + rng.standard_normal((2, 3)) * 0.1):
-            crop = (slice(2, 18), slice(5, 25))
-            p = _plan([X], np.zeros((2, 3, 3)), crop=crop, affine=affine, rotate=rotate, zoom=zoom)
-            Xs = dg._normalize_inputs(X)
-            axis, ds = dg._normalize_axis_list(None, Xs)
-            shapes, off = dg._compute_output_shapes(Xs, axis, ds, crop)
-            inv = dg._compute_inverse_affine(dg._normalize_affine(affine, axis))
-            inv = dg._apply_rotation_and_zoom(rotate, zoom, inv, [shapes[0][d] for d in axis[0]])
-            np.testing.assert_array_equal(p.output_offset, off)
-            if inv is None:
-                assert p.inverse_affine is None
-            else:
-                np.testing.assert_array_equal(p.inverse_affine, inv)
+    if ref is not None:
+        for k, v in gen_golden.live_plan(ref).items():
+            np.testing.assert_array_equal(stored[k], v)
+    n = 0
+    for i, (X, crop, affine, rotate, zoom) in enumerate(C.live_plan_cases()):
+        p = _plan([X], np.zeros((2, 3, 3)), crop=crop, affine=affine, rotate=rotate, zoom=zoom)
+        np.testing.assert_array_equal(p.output_offset, stored["plan%d/offset" % i])
+        if "plan%d/inverse_affine" % i not in stored.files:
+            assert p.inverse_affine is None
+        else:
+            np.testing.assert_array_equal(p.inverse_affine, stored["plan%d/inverse_affine" % i])
+        n += 1
+    assert n == 8
 
 
 def test_crop_window_logic():

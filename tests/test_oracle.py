@@ -4,6 +4,8 @@ outputs of the real reference -- bit for bit, and, where the real reference is p
 container: /root/reference + oracle/_ref), agree with it directly on freshly seeded inputs.
 This is what "parity status: PINNED" in the oracle header rests on.
 """
+import os
+
 import numpy as np
 import pytest
 import scipy.ndimage
@@ -134,30 +136,27 @@ def test_oracle_gradient_is_adjoint():
             assert abs(np.sum(Y * dY) - np.sum(dX * X)) < 1e-9
 
 
-@pytest.mark.skipif(ref_loader.load_reference() is None,
-                    reason="real reference only exists in the build container")
 def test_oracle_vs_live_reference():
-    """Fresh seeds, real reference imported from /root/reference: bit equality."""
+    """Seeded sweep of cases.live_deform_cases() (crop + affine, every order / mode, four dtypes), bit equality with
+    the real reference: its outputs as stored in tests/golden/live_reference.npz, and recomputed live where the
+    reference sources are present."""
+    import gen_golden
+    stored = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_reference.npz"))
     ref = ref_loader.load_reference()
-    rng = np.random.default_rng(123)
+    if ref is not None:
+        for k, v in gen_golden.live_deform(ref).items():
+            assert stored[k].dtype == v.dtype
+            np.testing.assert_array_equal(stored[k], v)
     n = 0
-    for shape, points in (((23, 31), (3, 3)), ((9, 11, 10), (2, 4, 3))):
-        for order in range(6):
-            for mode in C.MODES:
-                for dt in (np.float64, np.float32, np.int16, np.uint8):
-                    X = (rng.random(shape) * 100).astype(dt)
-                    disp = rng.standard_normal((len(shape),) + points) * 3
-                    crop = tuple(slice(2, s - 3) for s in shape)
-                    A = np.eye(len(shape), len(shape) + 1) + rng.standard_normal(
-                        (len(shape), len(shape) + 1)) * 0.05
-                    kw = dict(order=order, mode=mode, cval=0.5, crop=crop, affine=A)
-                    a = ref.deform_grid(X, disp, **kw)
-                    b = orc.deform_grid(X, disp, **kw)
-                    np.testing.assert_array_equal(a, b)
-                    if np.dtype(dt).kind == "f":
-                        dY = rng.random(a.shape).astype(dt)
-                        ga = ref.deform_grid_gradient(dY, disp, X_shape=X.shape, **kw)
-                        gb = orc.deform_grid_gradient(dY, disp, X_shape=X.shape, **kw)
-                        np.testing.assert_array_equal(ga, gb)
-                    n += 1
+    for i, (X, disp, kw, dY) in enumerate(C.live_deform_cases()):
+        a = stored["deform%d/out" % i]
+        b = orc.deform_grid(X, disp, **kw)
+        assert b.dtype == a.dtype
+        np.testing.assert_array_equal(a, b)
+        if dY is not None:
+            ga = stored["deform%d/grad" % i]
+            gb = orc.deform_grid_gradient(dY, disp, X_shape=X.shape, **kw)
+            assert gb.dtype == ga.dtype
+            np.testing.assert_array_equal(ga, gb)
+        n += 1
     assert n == 240

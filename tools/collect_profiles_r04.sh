@@ -15,13 +15,13 @@ done
 cd $R; python tools/pmc_summary.py $O/pmc > $O/pmc_summary.txt
 python tools/hbm_traffic.py $O/pmc "${COMMIT:-unknown}" > $O/hbm_traffic.json
 cp $O/hbm_traffic.json $R/profiles/hbm_traffic.json
-python bench.py --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python bench.py --workload cfg4 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-python bench.py --workload cfg5 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-python bench.py --dtype bf16 > $O/bench_bf16.json 2> $O/bench_bf16.err
-EDHIP_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload cfg5 --batch 8 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg5_2ranks_gloo.json 2> $O/bench_2r.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python bench.py --full --workload cfg4 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+python bench.py --full --workload cfg5 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python bench.py --full --dtype bf16 > $O/bench_bf16.json 2> $O/bench_bf16.err
+EDHIP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --workload cfg5 --batch 8 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg5_2ranks_gloo.json 2> $O/bench_2r.err
 EDHIP_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload cfg5 --batch 8 --steps 5 --warmup 2 --collective > $O/bench_cfg5_collective_gloo.json 2> $O/bench_coll.err
-cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof -o r04 --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stress > $O/prof.log 2>&1
+cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof -o r04 --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-stress > $O/prof.log 2>&1
 cd $R; python tools/kernel_stats_csv.py $O/prof/r04_kernel_stats.csv > $O/kernel_stats.txt
 cd /tmp
 for w in auto off; do

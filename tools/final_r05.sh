@@ -5,8 +5,8 @@ OUTNAME=r05final/pmc bash tools/pmc_k1.sh
 cd $R; cp $O/pmc/summary.txt $O/pmc_summary.txt
 python tools/hbm_traffic.py $O/pmc "${COMMIT:-unknown}" > $O/hbm_traffic.json
 cp $O/hbm_traffic.json $R/profiles/hbm_traffic.json
-python bench.py --steps 20 --warmup 5 2> $O/bench.err | grep '^{' > $O/bench.json
-cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof -o r05 --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stress > $O/prof.log 2>&1
+python bench.py --full --steps 20 --warmup 5 2> $O/bench.err | grep '^{' > $O/bench.json
+cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof -o r05 --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-stress > $O/prof.log 2>&1
 cd $R; python tools/kernel_stats_csv.py $O/prof/r05_kernel_stats.csv > $O/kernel_stats.txt
 timeout 300 python tools/latency_small.py 2>&1 | grep -v amdgpu.ids > $O/host_latency.txt
 timeout 600 python tools/time_matrix.py 2>&1 | grep -v amdgpu.ids > $O/time_matrix.txt
