@@ -299,6 +299,105 @@ __device__ __forceinline__ void spline_weights(double x, int order, double* w)
     w[order] = last;
 }
 
+// d/dx of spline_weights(x, order, .): the derivative of the same closed forms, the last weight's taken
+// from the "1 - sum of the others" rule (so the derivatives sum to zero).  Order 0 writes nothing (the
+// weight is constant); order 1 gives (-1, +1).  At a window change (order 1 at integers, the others at
+// their half-integer / integer switch points) this is the one-sided derivative of the window
+// spline_weights / window_start pick there.  dw must hold order+1 doubles.
+__device__ __forceinline__ void spline_weight_derivatives(double x, int order, double* dw)
+{
+    x -= floor((order & 1) ? x : x + 0.5);
+    const double z = 1.0 - x;
+    double y;
+    switch (order) {
+    case 1: dw[0] = -1.0; break;
+    case 2:
+        dw[1] = -2.0 * x;
+        dw[0] = x - 0.5;
+        break;
+    case 3:
+        dw[1] = x * (1.5 * x - 2.0);
+        dw[2] = -z * (1.5 * z - 2.0);
+        dw[0] = -0.5 * z * z;
+        break;
+    case 4: {
+        // w1 = f(1 + x), w3 = f(1 - x) with f(y) = y(y(y(5 - y)/6 - 5/4) + 5/24) + 55/96
+        auto fp = [](double v) { return v * (v * (2.5 - v * (2.0 / 3.0)) - 2.5) + 5.0 / 24.0; };
+        dw[2] = x * (x * x - 1.25);
+        dw[1] = fp(1.0 + x);
+        dw[3] = -fp(z);
+        y = 0.5 - x;
+        dw[0] = -y * y * y / 6.0;
+        break;
+    }
+    case 5: {
+        // w2 = g(x), w3 = g(1 - x); w1 = h(1 + x), w4 = h(2 - x)
+        auto gp = [](double v) { return v * (v * v * (1.0 - v * (5.0 / 12.0)) - 1.0); };
+        auto hp = [](double v) { return v * (v * (v * (v * (5.0 / 24.0) - 1.5) + 3.75) - 3.5) + 0.625; };
+        dw[2] = gp(x);
+        dw[3] = -gp(z);
+        dw[1] = hp(1.0 + x);
+        dw[4] = -hp(2.0 - x);
+        dw[0] = -z * z * z * z / 24.0;
+        break;
+    }
+    default: return;
+    }
+    double last = 0.0;
+    for (int i = 0; i < order; ++i)
+        last -= dw[i];
+    dw[order] = last;
+}
+
+// d map_coordinate(c, len, mode) / dc: +1 inside the axis and for 'wrap', -1 / +1 on the folds of 'mirror'
+// and 'reflect' (the branch map_coordinate takes for this c), 0 where 'nearest' clamps, on an axis of length
+// 1 and for 'constant' outside the axis (that voxel takes cval).
+__device__ __forceinline__ double map_coordinate_slope(double c, int64_t len, int mode)
+{
+#pragma clang fp contract(off)
+    if (c < 0) {
+        switch (mode) {
+        case EDHIP_MODE_MIRROR: {
+            if (len <= 1)
+                return 0.0;
+            const int64_t period = 2 * len - 2;
+            c = (double)(period * (int64_t)(-c / (double)period)) + c;
+            return c <= (double)(1 - len) ? 1.0 : -1.0;
+        }
+        case EDHIP_MODE_REFLECT: {
+            if (len <= 1)
+                return 0.0;
+            const int64_t period = 2 * len;
+            if (c < (double)(-period))
+                c = (double)(period * (int64_t)(-c / (double)period)) + c;
+            return c < (double)(-len) ? 1.0 : -1.0;
+        }
+        case EDHIP_MODE_WRAP: return len <= 1 ? 0.0 : 1.0;
+        default: return 0.0;      // nearest, constant
+        }
+    } else if (c > (double)(len - 1)) {
+        switch (mode) {
+        case EDHIP_MODE_MIRROR: {
+            if (len <= 1)
+                return 0.0;
+            const int64_t period = 2 * len - 2;
+            c -= (double)(period * (int64_t)(c / (double)period));
+            return c >= (double)len ? -1.0 : 1.0;
+        }
+        case EDHIP_MODE_REFLECT: {
+            if (len <= 1)
+                return 0.0;
+            const int64_t period = 2 * len;
+            c -= (double)(period * (int64_t)(c / (double)period));
+            return c >= (double)len ? -1.0 : 1.0;
+        }
+        case EDHIP_MODE_WRAP: return len <= 1 ? 0.0 : 1.0;
+        default: return 0.0;
+        }
+    }
+    return 1.0;
+}
+
 // control-point coordinate of output index o on one axis -- deform.c:643,655
 __device__ __forceinline__ double control_coordinate(int64_t ncp, int64_t o_plus_off, int64_t in_len)
 {

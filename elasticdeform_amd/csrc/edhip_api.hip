@@ -986,4 +986,211 @@ int edhip_spline_filter_axes(const edhip_array* input, const edhip_array* output
     return EDHIP_OK;
 }
 
+
+// ---- gradient with respect to the control-point displacement (deform_dgrad.hip) ------------------------------
+// nbatch samples at constant byte distances (nbatch == 1: a single call); RAW_DISPLACEMENT batches arrive here
+// one sample at a time.
+static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
+                      const int64_t* output_offset, const edhip_array* doutputs, int naxis, const int32_t* axis,
+                      const int32_t* orders, const int32_t* modes, const double* cvals, const double* affine,
+                      const edhip_array* ddisplacement, uint32_t flags, hipStream_t stream, int nbatch,
+                      int64_t in_bstride, int64_t disp_bstride, int64_t dout_bstride, int64_t ddisp_bstride,
+                      bool dry, char* err, size_t errlen)
+{
+    using namespace ed;
+    // ---- the checks of edhip_deform (_deform_grid.c:121-255), then the dtypes this gradient takes ----------------
+    if (!inputs || !doutputs || ninputs <= 0 || ninputs > EDHIP_MAX_INPUTS)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid number of inputs/outputs");
+    if (!axis || !orders || !modes || !cvals || naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > kMaxAxes)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
+                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
+    for (int i = 0; i < ninputs; ++i) {
+        const edhip_array& in = inputs[i];
+        const edhip_array& out = doutputs[i];
+        if (in.ndim != out.ndim)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "input and output dimensions should match");
+        if (in.ndim < 1 || in.ndim > EDHIP_MAX_DIMS)
+            return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions", EDHIP_MAX_DIMS);
+        // floating-point volumes only: the derivative of an integer volume's rounded result is not defined
+        if (!dtype_ok(in.dtype) || !dtype_ok(out.dtype) || (in.dtype != EDHIP_F32 && in.dtype != EDHIP_F64) ||
+            (out.dtype != EDHIP_F32 && out.dtype != EDHIP_F64))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+        for (int j = 0; j < naxis; ++j) {
+            const int a = axis[i * naxis + j];
+            if (a < 0 || a >= in.ndim)
+                return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
+            if (in.shape[a] != inputs[0].shape[axis[j]])
+                return fail(err, errlen, EDHIP_ERR_INVALID, "all inputs should have the same size");
+            if (out.shape[a] != doutputs[0].shape[axis[j]])
+                return fail(err, errlen, EDHIP_ERR_INVALID, "all outputs should have the same size");
+        }
+        if (orders[i] < 0 || orders[i] > 5)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "spline order not supported");
+        if (modes[i] < 0 || modes[i] > 4)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
+    }
+    if (!displacement || displacement->ndim != naxis + 1 || displacement->shape[0] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (!dtype_ok(displacement->dtype))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    int64_t points = 1;
+    for (int k = 0; k <= naxis; ++k) {
+        if (displacement->shape[k] <= 0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+        points *= displacement->shape[k];
+    }
+    if (!ddisplacement || ddisplacement->ndim != displacement->ndim)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+    for (int k = 0; k <= naxis; ++k)
+        if (ddisplacement->shape[k] != displacement->shape[k])
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+    if (!dtype_ok(ddisplacement->dtype))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    const bool raw = (flags & EDHIP_FLAG_RAW_DISPLACEMENT) != 0;
+    if (raw && points > 4096)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "raw displacement grids are limited to 4096 points");
+    IOView views[EDHIP_MAX_INPUTS];
+    for (int i = 0; i < ninputs; ++i) {
+        const int st = make_view(inputs[i], doutputs[i], naxis, axis + i * naxis, orders[i], modes[i], cvals[i],
+                                 views[i], err, errlen);
+        if (st != EDHIP_OK)
+            return st;
+    }
+    int64_t in_len[kMaxAxes], out_len[kMaxAxes];
+    for (int k = 0; k < naxis; ++k) {
+        in_len[k] = inputs[0].shape[axis[k]];
+        out_len[k] = doutputs[0].shape[axis[k]];
+    }
+    const uint32_t gflags = flags & ~(uint32_t)(EDHIP_FLAG_RAW_DISPLACEMENT | EDHIP_FLAG_GRID_STAYS);
+    GridGeom g;
+    int st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine, gflags, stream, g, err,
+                           errlen);
+    if (st != EDHIP_OK)
+        return st;
+    if (!dgrad_supported(g))
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
+                    "displacement gradient: naxis * (control points along the last axis) is limited to %d",
+                    kDgradMaxK);
+    int64_t rows = 1;
+    for (int k = 0; k < naxis - 1; ++k)
+        rows *= out_len[k];
+    if (nbatch > 65535 || rows > 0x7fffffff)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "displacement gradient: too many rows or samples");
+    if (dry)
+        return EDHIP_OK;
+
+    // ---- scratch, reserved in one piece before anything is enqueued: [grid head | the transposed filter's line
+    //      buffer | dense fp64 dD | partials] -- a later, larger request would move the buffer ----------------------
+    const size_t grid_bytes = ((size_t)points * 8 + 255) & ~(size_t)255;
+    size_t off = kWorkspaceGridBytes;
+    const size_t dp_off = off + (raw ? grid_bytes : 0);
+    const size_t sc_off = dp_off + (raw ? grid_bytes : 0);
+    size_t need = sc_off + dgrad_scratch_bytes(g, nbatch);
+    if (raw && deform_tile_workspace_bytes(g, 1, false) > need)
+        need = deform_tile_workspace_bytes(g, 1, false);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)workspace_reserve(stream, need, &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    if (raw) {
+        // the library's order-3 mirror prefilter of the raw grid, into the workspace head (as edhip_deform does)
+        st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine,
+                           flags & ~(uint32_t)EDHIP_FLAG_GRID_STAYS, stream, g, err, errlen);
+        if (st != EDHIP_OK)
+            return st;
+    }
+    edhip_array dp;                   // dense fp64 dP of a RAW call, filtered in place below
+    memset(&dp, 0, sizeof(dp));
+    dp.data = ws + dp_off;
+    dp.dtype = EDHIP_F64;
+    dp.ndim = naxis + 1;
+    for (int k = naxis, s = 8; k >= 0; --k) {
+        dp.shape[k] = displacement->shape[k];
+        dp.stride_bytes[k] = s;
+        s *= (int)displacement->shape[k];
+    }
+    DgradCall c;
+    memset(&c, 0, sizeof(c));
+    c.g = g;
+    c.ninputs = ninputs;
+    c.views = views;
+    c.nbatch = nbatch;
+    c.in_bstride = in_bstride;
+    c.out_bstride = dout_bstride;
+    c.disp_bstride = disp_bstride;
+    const edhip_array& dst = raw ? dp : *ddisplacement;
+    c.dst = (char*)dst.data;
+    c.dst_dtype = dst.dtype;
+    c.dst_bstride = ddisp_bstride;
+    for (int k = 0; k <= naxis; ++k)
+        c.dst_stride[k] = dst.stride_bytes[k];
+    c.scratch = ws + sc_off;
+    e = launch_deform_dgrad(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "displacement gradient launch");
+    if (raw) {
+        // dD = (order-3 mirror prefilter)^T along the grid axes, in fp64, then one cast into the caller's array
+        for (int k = 1; k <= naxis; ++k) {
+            st = filter1d_impl(&dp, &dp, k, 3, 1, flags & EDHIP_FLAG_EXACT, stream, nullptr, false, err, errlen);
+            if (st != EDHIP_OK)
+                return st;
+        }
+        st = filter1d_impl(&dp, ddisplacement, 0, 0, 0, 0, stream, nullptr, false, err, errlen);
+        if (st != EDHIP_OK)
+            return st;
+    }
+    return EDHIP_OK;
+}
+
+int edhip_deform_displacement_gradient(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
+                                       const int64_t* output_offset, const edhip_array* doutputs, int naxis,
+                                       const int32_t* axis, const int32_t* orders, const int32_t* modes,
+                                       const double* cvals, const double* affine, const edhip_array* ddisplacement,
+                                       uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    ed::StreamGuard guard(stream);
+    if (err && errlen)
+        err[0] = 0;
+    return dgrad_impl(ninputs, inputs, displacement, output_offset, doutputs, naxis, axis, orders, modes, cvals,
+                      affine, ddisplacement, flags, stream, 1, 0, 0, 0, 0, false, err, errlen);
+}
+
+int edhip_deform_displacement_gradient_batch_strided(
+    int nbatch, const edhip_array* input0, int64_t input_batch_stride, const edhip_array* displacement0,
+    int64_t displacement_batch_stride, const int64_t* output_offset, const edhip_array* doutput0,
+    int64_t doutput_batch_stride, int naxis, const int32_t* axis, int32_t order, int32_t mode, double cval,
+    const double* affine, const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride, uint32_t flags,
+    void* hip_stream, char* err, size_t errlen)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || (nbatch > 0 && (!input0 || !displacement0 || !doutput0 || !ddisplacement0)))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (nbatch == 0)
+        return EDHIP_OK;
+    ed::StreamGuard guard(stream);
+    if (!(flags & EDHIP_FLAG_RAW_DISPLACEMENT))
+        return dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval,
+                          affine, ddisplacement0, flags, stream, nbatch, input_batch_stride, displacement_batch_stride,
+                          doutput_batch_stride, ddisplacement_batch_stride, false, err, errlen);
+    // raw grids: each sample's grid is prefiltered into the workspace head, so the samples go one after the other
+    // (every argument is checked before the first launch)
+    int st = dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval, affine,
+                        ddisplacement0, flags, stream, 1, 0, 0, 0, 0, true, err, errlen);
+    for (int b = 0; b < nbatch && st == EDHIP_OK; ++b) {
+        edhip_array in = *input0, disp = *displacement0, dout = *doutput0, ddisp = *ddisplacement0;
+        in.data = (char*)input0->data + (int64_t)b * input_batch_stride;
+        disp.data = (char*)displacement0->data + (int64_t)b * displacement_batch_stride;
+        dout.data = (char*)doutput0->data + (int64_t)b * doutput_batch_stride;
+        ddisp.data = (char*)ddisplacement0->data + (int64_t)b * ddisplacement_batch_stride;
+        st = dgrad_impl(1, &in, &disp, output_offset, &dout, naxis, axis, &order, &mode, &cval, affine, &ddisp, flags,
+                        stream, 1, 0, 0, 0, 0, false, err, errlen);
+    }
+    return st;
+}
+
 }  // extern "C"

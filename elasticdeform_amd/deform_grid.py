@@ -909,3 +909,144 @@ def deform_grid_gradient_batch(dY, displacements, order=3, mode='constant', cval
         if prefilter and o > 1:
             dX = _filter_axes(dX, [a + 1 for a in ax], o, True, device, overwrite=True)
         return _from_device(dX, dY)
+
+
+# ---- gradient with respect to the control-point displacement (no counterpart in the reference) ---------
+
+_FLOAT_VOLUMES = ('float32', 'float64')
+
+
+def _volume_dtype_name(a):
+    return a.dtype.name if isinstance(a, numpy.ndarray) else str(a.dtype).replace('torch.', '')
+
+
+def _check_float_volumes(arrays):
+    """float32 / float64 volumes and dY only -- checked before anything touches the device."""
+    for a in arrays:
+        if _volume_dtype_name(a) not in _FLOAT_VOLUMES:
+            raise RuntimeError('data type not supported')
+
+
+def _dgrad_dtype(displacement):
+    """The result's dtype: the displacement's own when it is floating, float64 otherwise."""
+    torch = _torch()
+    if isinstance(displacement, numpy.ndarray):
+        return displacement.dtype if displacement.dtype.kind == 'f' else numpy.dtype('float64')
+    return displacement.dtype if displacement.dtype.is_floating_point else torch.float64
+
+
+def _dgrad_zeros(displacement, like):
+    """Zeros of the displacement's shape and the result dtype, in the family / on the device of `like`."""
+    dt = _dgrad_dtype(displacement)
+    shape = tuple(int(v) for v in displacement.shape)
+    if isinstance(like, numpy.ndarray):
+        return numpy.zeros(shape, dtype=dt if isinstance(dt, numpy.dtype) else numpy.float64)
+    torch = _torch()
+    if isinstance(dt, numpy.dtype):
+        dt = getattr(torch, dt.name)
+    return torch.zeros(shape, dtype=dt, device=like.device)
+
+
+def _result_tensor_dtype(displacement):
+    torch = _torch()
+    dt = _dgrad_dtype(displacement)
+    return getattr(torch, dt.name) if isinstance(dt, numpy.dtype) else dt
+
+
+def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None,
+                                      prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid` with respect to the control-point ``displacement``: the array
+    ``d(sum_i <dY_i, Y_i>) / d displacement`` where ``Y = deform_grid(X, displacement, ...)`` with the same
+    arguments (the order-3 prefilter of the grid included).  ``X`` and ``dY`` are arrays or lists of arrays
+    (float32 / float64), ``dY[i]`` of the shape of ``Y[i]``.  Returns an array of the displacement's shape, in its
+    dtype when that is floating (float64 otherwise): numpy for a numpy ``dY``, otherwise a tensor on ``dY``'s
+    device.  The sum over the volume runs in fp64 in a fixed order: repeated calls return the same bits.
+    """
+    Xs = _host.normalize_inputs(X)
+    dYs = _host.normalize_inputs(dY)
+    plan = _host.cached_plan(Xs, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
+    if len(dYs) != len(Xs) or [tuple(s) for s in plan.output_shapes] != [tuple(int(v) for v in dy.shape)
+                                                                        for dy in dYs]:
+        raise ValueError("dY does not match the output shape of deform_grid. Expected output shape is %s, "
+                         "but %s given." % (str(plan.output_shapes), str([tuple(dy.shape) for dy in dYs])))
+    _check_float_volumes(list(Xs) + list(dYs))
+    if _host.degenerate_axis([x.shape for x in Xs], plan.axis):
+        # (a deformed axis of length 1: every voxel is the constant, nothing depends on the grid)
+        return _dgrad_zeros(displacement, dYs[0])
+    torch = _torch()
+    device = _device_for(list(dYs) + list(Xs) + [displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        Xf = []
+        for i, x in enumerate(Xs):
+            x = _to_device(x, device)
+            if prefilter and plan.order[i] > 1:
+                x = _filter_axes(x, plan.axis[i], int(plan.order[i]), False, device, stream=stream)
+            Xf.append(x)
+        dYd = [_to_device(dy, device) for dy in dYs]
+        dd = _to_device(displacement, device)
+        out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacement), device=device)
+        if dd.numel() <= _lib.RAW_DISPLACEMENT_MAX_POINTS:
+            _lib.deform_displacement_gradient([_desc(x) for x in Xf], _desc(dd), plan.output_offset,
+                                              [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode,
+                                              plan.cval, plan.inverse_affine, _desc(out),
+                                              _flags | _lib.FLAG_RAW_DISPLACEMENT, stream,
+                                              prepared=_prepared(plan, len(Xf)))
+        else:
+            # a large grid: prefiltered here, the gradient of the prefiltered grid transposed here (fp64 throughout)
+            df = _filter_axes(dd, range(1, dd.ndim), 3, False, device, stream=stream)
+            dp = torch.empty(out.shape, dtype=torch.float64, device=device)
+            _lib.deform_displacement_gradient([_desc(x) for x in Xf], _desc(df), plan.output_offset,
+                                              [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode,
+                                              plan.cval, plan.inverse_affine, _desc(dp), _flags, stream,
+                                              prepared=_prepared(plan, len(Xf)))
+            dp = _filter_axes(dp, range(1, dp.ndim), 3, True, device, overwrite=True, stream=stream)
+            out.copy_(dp)
+        return _from_device(out, dYs[0])
+
+
+def deform_grid_displacement_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None,
+                                            prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_displacement_gradient` over a batch, following :func:`deform_grid_batch`: ``X`` is
+    ``(B, ...)``, ``dY`` the gradient of the batch's output, ``displacements`` ``(B, naxis, n_0, ...)``.  Returns
+    ``(B, naxis, n_0, ...)``; sample ``b`` is the same bits as the single call on sample ``b``."""
+    plan = _batch_plan(X, displacements, order, mode, cval, crop, axis, affine, rotate, zoom)
+    if not _host.is_array(dY) or tuple(int(v) for v in dY.shape) != (int(X.shape[0]),) + tuple(plan.output_shapes[0]):
+        raise ValueError("dY does not match the output shape of deform_grid_batch. Expected output shape is %s, "
+                         "but %s given." % (str((int(X.shape[0]),) + tuple(plan.output_shapes[0])),
+                                            str(tuple(dY.shape) if _host.is_array(dY) else dY)))
+    _check_float_volumes([X, dY])
+    if _host.degenerate_axis([X.shape[1:]], plan.axis):
+        return _dgrad_zeros(displacements, dY)
+    torch = _torch()
+    device = _device_for([dY, X, displacements])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        Xd = _to_device(X, device)
+        o = int(plan.order[0])
+        ax = plan.axis[0]
+        if prefilter and o > 1:
+            Xd = _filter_axes(Xd, [a + 1 for a in ax], o, False, device, stream=stream)
+        dYd = _to_device(dY, device)
+        dd = _to_device(displacements, device)
+        B = int(Xd.shape[0])
+        out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacements), device=device)
+        per_sample = int(numpy.prod([int(v) for v in dd.shape[1:]]))
+        (xd, xs), (yd, ys) = _desc_sample0(Xd), _desc_sample0(dYd)
+        if per_sample <= _lib.RAW_DISPLACEMENT_MAX_POINTS:
+            (gd, gs), (od, os_) = _desc_sample0(dd), _desc_sample0(out)
+            _lib.deform_displacement_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
+                                                            int(plan.mode[0]), float(plan.cval[0]),
+                                                            plan.inverse_affine, od, os_,
+                                                            _flags | _lib.FLAG_RAW_DISPLACEMENT, stream)
+        else:
+            df = _filter_axes(dd, range(2, dd.ndim), 3, False, device, stream=stream)
+            dp = torch.empty(out.shape, dtype=torch.float64, device=device)
+            (gd, gs), (pd, ps) = _desc_sample0(df), _desc_sample0(dp)
+            _lib.deform_displacement_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
+                                                            int(plan.mode[0]), float(plan.cval[0]),
+                                                            plan.inverse_affine, pd, ps, _flags, stream)
+            dp = _filter_axes(dp, range(2, dp.ndim), 3, True, device, overwrite=True, stream=stream)
+            out.copy_(dp)
+        return _from_device(out, dY)

@@ -4,7 +4,8 @@ drop-in for ``elasticdeform.torch.deform_grid`` (/root/reference/elasticdeform/t
 
 Same autograd contract as the reference's ``ElasticDeform`` Function (torch.py:5-29): gradients
 flow to the inputs ``X`` only (the displacement gets none), a list / tuple of inputs gives a
-tuple of outputs.  The difference is the one this build exists for: the reference copies every
+tuple of outputs.  With ``displacement_grad=True`` (keyword-only, an extension) the displacement gets its gradient
+too (``elasticdeform_amd.deform_grid_displacement_gradient``).  The difference is the one this build exists for: the reference copies every
 tensor to the host, runs one CPU thread and copies back (torch.py:13-16,25-29); here CUDA tensors
 stay in HBM and forward / backward are HIP kernels enqueued on the current stream.
 """
@@ -17,6 +18,8 @@ from . import deform_grid as _deform_grid_fn
 from . import deform_grid_gradient as _deform_grid_gradient_fn
 from . import deform_grid_batch as _deform_grid_batch_fn
 from . import deform_grid_gradient_batch as _deform_grid_gradient_batch_fn
+from . import deform_grid_displacement_gradient as _dgrad_fn
+from . import deform_grid_displacement_gradient_batch as _dgrad_batch_fn
 
 
 class ElasticDeform(torch.autograd.Function):
@@ -41,20 +44,51 @@ class ElasticDeform(torch.autograd.Function):
         return (None, None, None) + tuple(dxs)
 
 
-def deform_grid(X, displacement, *args, **kwargs):
+class ElasticDeformDisplacement(torch.autograd.Function):
+    """ElasticDeform with a gradient for the displacement as well (displacement_grad=True): the forward keeps X."""
+
+    @staticmethod
+    def forward(ctx, displacement, deform_args, deform_kwargs, *xs):
+        ctx.save_for_backward(displacement, *xs)
+        ctx.deform_args = deform_args
+        ctx.deform_kwargs = deform_kwargs
+        ctx.x_shapes = [tuple(x.shape) for x in xs]
+        ys = _deform_grid_fn([x.detach() for x in xs], displacement.detach(), *deform_args, **deform_kwargs)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        displacement, *xs = ctx.saved_tensors
+        dys = [dy.detach() for dy in dys]
+        dxs = [None] * len(xs)
+        if any(ctx.needs_input_grad[3:]):
+            dxs = _deform_grid_gradient_fn(dys, displacement.detach(), *ctx.deform_args, X_shape=ctx.x_shapes,
+                                           **ctx.deform_kwargs)
+        ddisp = None
+        if ctx.needs_input_grad[0]:
+            ddisp = _dgrad_fn([x.detach() for x in xs], dys, displacement.detach(), *ctx.deform_args,
+                              **ctx.deform_kwargs)
+            ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+        return (ddisp, None, None) + tuple(dxs)
+
+
+def deform_grid(X, displacement, *args, displacement_grad=False, **kwargs):
     """
     Elastic deformation with a deformation grid, wrapped for PyTorch with a custom gradient.
 
     X : torch.Tensor or list / tuple of torch.Tensors; displacement : tensor or array of control
     point displacements; remaining arguments as for ``elasticdeform_amd.deform_grid``.
     Returns a tensor, or a tuple of tensors for a list / tuple input (torch.py:56-66).
+    displacement_grad : keyword only.  False (the default, the reference's contract): gradients flow to X
+    only.  True: the displacement gets its gradient as well (on its device, in its dtype).
     """
     if not isinstance(X, (list, tuple)):
         X_list = [X]
     else:
         X_list = X
     displacement = torch.as_tensor(displacement)
-    y = ElasticDeform.apply(displacement, args, kwargs, *X_list)
+    fn = ElasticDeformDisplacement if displacement_grad else ElasticDeform
+    y = fn.apply(displacement, args, kwargs, *X_list)
     if isinstance(X, (list, tuple)):
         return y
     else:
@@ -118,13 +152,38 @@ class ElasticDeformBatch(torch.autograd.Function):
         return dx, None, None
 
 
-def deform_grid_batch(X, displacements, **kwargs):
+class ElasticDeformBatchDisplacement(torch.autograd.Function):
+    """ElasticDeformBatch with a gradient for the displacements as well (displacement_grad=True)."""
+
+    @staticmethod
+    def forward(ctx, x, displacements, deform_kwargs):
+        ctx.save_for_backward(x, displacements)
+        ctx.deform_kwargs = deform_kwargs
+        ctx.x_shape = tuple(x.shape[1:])
+        return _deform_grid_batch_fn(x.detach(), displacements.detach(), **deform_kwargs)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, displacements = ctx.saved_tensors
+        dy = dy.detach()
+        dx = ddisp = None
+        if ctx.needs_input_grad[0]:
+            dx = _deform_grid_gradient_batch_fn(dy, displacements.detach(), X_shape=ctx.x_shape, **ctx.deform_kwargs)
+        if ctx.needs_input_grad[1]:
+            ddisp = _dgrad_batch_fn(x.detach(), dy, displacements.detach(), **ctx.deform_kwargs)
+            ddisp = ddisp.to(device=displacements.device, dtype=displacements.dtype)
+        return dx, ddisp, None
+
+
+def deform_grid_batch(X, displacements, *, displacement_grad=False, **kwargs):
     """
     Batched :func:`deform_grid` with one control grid per sample: ``X`` is ``(B, ...)``,
     ``displacements`` is ``(B, naxis, n_0, ...)`` (e.g. from :func:`random_displacement` with
     ``batch=B``); keyword arguments as for ``elasticdeform_amd.deform_grid_batch``.  Differentiable
-    with respect to ``X``.
+    with respect to ``X``; with ``displacement_grad=True`` with respect to the displacements as well.
     """
+    if displacement_grad:
+        return ElasticDeformBatchDisplacement.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)
     return ElasticDeformBatch.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)
 
 

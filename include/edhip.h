@@ -285,6 +285,57 @@ int edhip_deform_batch_strided(int gradient, int nbatch,
                                char* err, size_t errlen);
 
 /*
+ * Gradient of the deformation with respect to the control-point displacement (no counterpart in the
+ * reference, whose wrappers drop this gradient).  Arguments as for edhip_deform(gradient = 0, ...), with
+ *   inputs[ninputs]      the (prefiltered) source arrays C_i the forward read, read.  float32 / float64 only
+ *                        (every other dtype: EDHIP_ERR_DTYPE before any launch).
+ *   doutputs[ninputs]    dY_i, the gradient with respect to the forward's outputs, read; float32 / float64.
+ *   ddisplacement        written: the shape of `displacement`, any dtype / strides (rounded once).
+ * Without EDHIP_FLAG_RAW_DISPLACEMENT `displacement` is the prefiltered grid P and the result is
+ *   dP[h, j] = d(sum_i <dY_i, Y_i>) / dP[h, j]
+ *            = sum_o beta(o, j) sum_i sum_step dY_i[o, step] map'_h sum_k C_i[k, step] w'_h(m_h, k_h) prod_{e!=h} w_e(m_e, k_e)
+ * (beta: the cubic weights of control point j at output voxel o; w': the derivative of the order-p weights of
+ * deform.c:160-268; map': the slope of the boundary map's branch, deform.c:47-128 -- +1 inside and for 'wrap',
+ * -1 on the folds of 'mirror' / 'reflect', 0 where 'nearest' clamps; a 'constant' voxel outside the volume
+ * contributes nothing; at a kink, the one-sided derivative of the branch the forward takes).  With
+ * EDHIP_FLAG_RAW_DISPLACEMENT `displacement` is the RAW grid D (at most 4096 points): the library applies the
+ * order-3 mirror prefilter itself and returns dD = (prefilter)^T dP.  Order 0 gives exact zeros.
+ * Arithmetic: fp64 coordinates and weights, tap sums in the volume's type, fp64 accumulation across voxels in a
+ * fixed order (no atomics): the result is bit-reproducible from run to run.  No host synchronisation beyond the
+ * workspace rule above; the call can be captured into a HIP graph once the stream's workspace is warm.
+ * naxis * (control points along the last deformed axis) is limited to 256 (EDHIP_ERR_UNSUPPORTED beyond).
+ */
+int edhip_deform_displacement_gradient(int ninputs, const edhip_array* inputs,
+                                       const edhip_array* displacement,
+                                       const int64_t* output_offset,
+                                       const edhip_array* doutputs,
+                                       int naxis, const int32_t* axis,
+                                       const int32_t* orders, const int32_t* modes, const double* cvals,
+                                       const double* affine,
+                                       const edhip_array* ddisplacement,
+                                       uint32_t flags, void* hip_stream,
+                                       char* err, size_t errlen);
+
+/*
+ * The same for a batch described once, as edhip_deform_batch_strided: sample b's input, control grid, dY and
+ * result are sample 0's moved by b * stride bytes; axis / order / mode / cval / crop / affine are shared.
+ * Sample b's result is bit-identical to edhip_deform_displacement_gradient on sample b alone.  Prefiltered
+ * grids: one set of launches for the whole batch (the row kernel's grid carries the sample); RAW grids are
+ * prefiltered and transposed sample by sample.
+ */
+int edhip_deform_displacement_gradient_batch_strided(int nbatch,
+                                                     const edhip_array* input0, int64_t input_batch_stride,
+                                                     const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                                     const int64_t* output_offset,
+                                                     const edhip_array* doutput0, int64_t doutput_batch_stride,
+                                                     int naxis, const int32_t* axis,
+                                                     int32_t order, int32_t mode, double cval,
+                                                     const double* affine,
+                                                     const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                                     uint32_t flags, void* hip_stream,
+                                                     char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
