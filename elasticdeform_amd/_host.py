@@ -234,7 +234,7 @@ class Plan(object):
     non-array arguments of _deform_grid.deform_grid (_deform_grid.c:108-118)."""
 
     __slots__ = ("axis", "naxis", "deform_shape", "output_shapes", "output_offset", "order",
-                 "mode", "cval", "inverse_affine", "prepared")
+                 "mode", "cval", "inverse_affine", "prepared", "affine_jacobian")
 
     def __init__(self, Xs, displacement, order, mode, cval, crop, axis, affine, rotate, zoom):
         # same order of checks as deform_grid.py:135-152 / :246-266
@@ -251,6 +251,7 @@ class Plan(object):
         self.inverse_affine = compose_rotation_zoom(
             rotate, zoom, inv, [self.output_shapes[0][d] for d in self.axis[0]])
         self.prepared = None         # ctypes form of the arrays above, attached by the caller
+        self.affine_jacobian = None  # d inverse_affine / d(affine, rotate, zoom), attached by the affine gradient
 
 
 # ---- plan cache ------------------------------------------------------------------------------------

@@ -53,7 +53,8 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_spline_filter_axes', 'edhip_source_window', 'edhip_spline_filter_axes_window',
            'edhip_release_scratch', 'edhip_profile_dominant',
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
-           'edhip_deform_displacement_gradient_batch_strided')
+           'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
+           'edhip_deform_transform_gradient_batch_strided')
 
 
 class EdhipArray(ctypes.Structure):
@@ -154,6 +155,20 @@ def load():
             ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_uint32,
             ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_transform_gradient.restype = ctypes.c_int
+        L.edhip_deform_transform_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.POINTER(EdhipArray), ctypes.POINTER(ctypes.c_int64),
+            ctypes.POINTER(EdhipArray), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(EdhipArray), ctypes.POINTER(EdhipArray), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p,
+            ctypes.c_size_t]
+        L.edhip_deform_transform_gradient_batch_strided.restype = ctypes.c_int
+        L.edhip_deform_transform_gradient_batch_strided.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -318,6 +333,50 @@ def deform_displacement_gradient_batch_strided(nbatch, in_desc, in_bstride, disp
         ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
         int(order), int(mode), float(cval), aff, ctypes.byref(ddisp_desc), int(ddisp_bstride), int(flags),
         ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
+
+
+def _ref(desc):
+    return ctypes.byref(desc) if desc is not None else None
+
+
+def deform_transform_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
+                              inverse_affine, ddisp_desc, dinv_desc, flags, stream, prepared=None):
+    """edhip_deform_transform_gradient: d(sum_i <dY_i, Y_i>) / d(displacement) into `ddisp_desc` and / or
+    d(...) / d(inverse map) into `dinv_desc` (float64, naxis x naxis+1); None = not wanted.  Otherwise as
+    deform_displacement_gradient()."""
+    L = load()
+    n = len(in_descs)
+    a = prepared if prepared is not None else DeformArgs(n, axis, orders, modes, cvals, output_offset,
+                                                         inverse_affine)
+    ins = (EdhipArray * n)(*in_descs)
+    outs = (EdhipArray * n)(*dout_descs)
+    buf = _buf()
+    status = L.edhip_deform_transform_gradient(n, ins, ctypes.byref(disp_desc), a.off, outs, a.naxis, a.axis,
+                                               a.orders, a.modes, a.cvals, a.aff, _ref(ddisp_desc), _ref(dinv_desc),
+                                               int(flags), stream, buf, 256)
+    raise_for_status(status, buf)
+
+
+def deform_transform_gradient_batch_strided(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset,
+                                            dout_desc, dout_bstride, axis, order, mode, cval, inverse_affine,
+                                            ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride, flags, stream):
+    """edhip_deform_transform_gradient_batch_strided: sample 0's descriptors plus byte strides (None = not wanted)."""
+    L = load()
+    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    off = aff = None
+    if output_offset is not None:
+        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
+        off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    if inverse_affine is not None:
+        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
+        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    buf = ctypes.create_string_buffer(256)
+    status = L.edhip_deform_transform_gradient_batch_strided(
+        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
+        ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        int(order), int(mode), float(cval), aff, _ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc),
+        int(dinv_bstride), int(flags), ctypes.c_void_p(stream), buf, 256)
     raise_for_status(status, buf)
 
 

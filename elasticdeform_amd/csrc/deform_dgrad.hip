@@ -17,6 +17,15 @@
 //                          [outer][ncp_d][inner], one wavefront per output, the o_d sum in a fixed order.
 //   dgrad_finish_kernel    [b][j_0..j_{n-2}][h][j_last] -> dP[b][h][j_0..j_{n-1}] in the destination's dtype.
 //
+// Gradient with respect to the inverse map K (n x (n+1)) the coordinate applies, c_h = sum_l K[h,l] o_l + K[h,n] + ...:
+//   dK[h, l] = sum_o g_h(o) o_l        dK[h, n] = sum_o g_h(o)
+// The row kernel (template flag AK) also leaves per row the moments S0_h = sum g_h and S1_h = sum g_h o_{n-1} along
+// the row -> mom[b][row][h][2], built from the LDS copy of g (one xor butterfly per wave, the waves' sums in their
+// own LDS slots chunk after chunk, the waves added in order at the end); then
+//   dgrad_affine_reduce_kernel  256 rows per workgroup: dK[h, l < n-1] = o_l S0_h, dK[h, n-1] = S1_h, dK[h, n] = S0_h
+//                               summed by a butterfly per wave and the waves in order -> one partial per workgroup
+//   dgrad_affine_store_kernel   one wavefront per (output, sample): the partials in a fixed order -> dK (fp64)
+//
 // No atomics, no counters: every sum has one fixed order, so the result is the same bits from run to run, and a
 // sample of a batch is the same bits as the single call.  No host synchronisation; the launches are capturable.
 #include <cstring>
@@ -33,12 +42,22 @@ constexpr int kRowThreads = 256;          // largest row workgroup (the LDS arra
 struct RowArgs {
     GridGeom g;
     IOView v;
-    double* part;                         // [nbatch][rows][K]
+    double* part;                         // [nbatch][rows][K]; nullptr (AK kernels only): no displacement result
     int64_t rows;
     int K;                                // naxis * ncp_{naxis-1}
     int accumulate;                       // add to part (second and later inputs) instead of overwriting it
     int64_t in_bstride, out_bstride, disp_bstride;
+    double* mom;                          // AK kernels: [nbatch][rows][naxis][2] row moments (S0_h, S1_h)
 };
+
+// sum over the 64 lanes of a wavefront by a fixed xor butterfly (every lane ends with the same bits)
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        v += __shfl_xor(v, m, 64);
+    return v;
+}
 
 // pick a[t] for a runtime t without indexing a register array dynamically
 template <typename T, int M>
@@ -234,13 +253,16 @@ __device__ __forceinline__ void voxel_input(const RowArgs& a, const char* in, co
 
 // P > 0: one order and one volume type (T) per kernel -- the 2- and 3-axis kernels, each with the registers of its
 // own tap loop; P == 0: every order and both types behind a runtime switch (1 and 4..7 axes)
-template <int N, int P, typename T>
+// AK: also the row moments of g for the inverse map's gradient (a.mom); a.part may then be nullptr
+template <int N, int P, typename T, bool AK>
 __global__ __launch_bounds__(kRowThreads) void dgrad_rows_kernel(RowArgs a)
 {
     __shared__ double s_q[kDgradMaxK];                    // the row's displacement coefficients Q[h][j_last]
     __shared__ double s_g[kMaxAxes * kRowThreads];        // g_h of the chunk's voxels; at the end: the wave partials
     __shared__ double s_bw[4 * kRowThreads];              // b_{n-1} weights of the chunk's voxels
     __shared__ int64_t s_st[kRowThreads];                 // their first control index (unfolded)
+    __shared__ double s_mom[AK ? 2 * N * (kRowThreads / 64) : 1];   // AK: per wave, its moments summed over chunks
+    const bool want_part = !AK || a.part != nullptr;
     const GridGeom& g = a.g;
     const int tid = threadIdx.x;
     const int nt = blockDim.x;
@@ -276,6 +298,10 @@ __global__ __launch_bounds__(kRowThreads) void dgrad_rows_kernel(RowArgs a)
             s_rw[4 * d + t] = w[t];
             s_ri[4 * d + t] = mirror_index(s + t, g.ncp[d]) * g.disp_stride[d + 1];
         }
+    }
+    if constexpr (AK) {
+        if (tid < 2 * N * ((nt + 63) >> 6))
+            s_mom[tid] = 0.0;
     }
     __syncthreads();
     for (int k = tid; k < K; k += nt) {
@@ -364,12 +390,27 @@ __global__ __launch_bounds__(kRowThreads) void dgrad_rows_kernel(RowArgs a)
         for (int h = 0; h < N; ++h)
             s_g[h * kRowThreads + tid] = gv[h];
         __syncthreads();
+        if constexpr (AK) {
+            // the row moments from the LDS copy (a voxel past the row's end holds g = 0): S0_h = sum g_h,
+            // S1_h = sum g_h o_{n-1} over the wave's 64 voxels, added to the wave's own slot in chunk order
+            const double ol = (double)(c0 + tid);
+#pragma unroll
+            for (int h = 0; h < N; ++h) {
+                const double gh = s_g[h * kRowThreads + tid];
+                const double s0 = wave_sum(gh);
+                const double s1 = wave_sum(gh * ol);
+                if (lane == 0) {
+                    s_mom[(wave * N + h) * 2] += s0;
+                    s_mom[(wave * N + h) * 2 + 1] += s1;
+                }
+            }
+        }
         // wave `wave` contracts its own 64 voxels: lane q -> (hj = q % K, group q / K), groups in ascending order
         const int64_t vend = L - c0 < (int64_t)nt ? L - c0 : (int64_t)nt;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int q = lane + 64 * r;
-            if (q < K * G) {
+            if (want_part && q < K * G) {
                 const int hj = q % K, grp = q / K;
                 const int h = hj / (int)nl;
                 const int64_t j = hj % nl;
@@ -394,6 +435,19 @@ __global__ __launch_bounds__(kRowThreads) void dgrad_rows_kernel(RowArgs a)
             }
         }
         __syncthreads();
+    }
+
+    if constexpr (AK) {
+        // the waves' moments in wave order (their last additions are behind the chunk loop's final barrier)
+        if (tid < 2 * N) {
+            double sum = 0.0;
+            for (int w = 0; w < nw; ++w)
+                sum += s_mom[w * 2 * N + tid];
+            double* dst = a.mom + ((int64_t)b * a.rows + row) * 2 * N + tid;
+            *dst = a.accumulate ? *dst + sum : sum;
+        }
+        if (!want_part)
+            return;
     }
 
     // ---- partials of the waves and groups, summed in a fixed order ----
@@ -501,32 +555,150 @@ __global__ __launch_bounds__(256) void dgrad_finish_kernel(FinishArgs f)
     store_cast(f.dst + b * f.dst_bstride + doff, f.dst_dtype, f.in[i]);
 }
 
-template <int N, int P, typename T>
+// rows -> one partial of every dK entry per workgroup of kAffineRows rows: thread t takes row 256 * x + t, the
+// entries are summed by a butterfly per wave, then the waves in order.  part[b][chunk][h][0..n].
+constexpr int kAffineRows = 256;
+
+struct AffineReduceArgs {
+    const double* mom;            // [nbatch][rows][n][2]
+    double* part;                 // [nbatch][nchunk][n][n+1]
+    int64_t rows, nchunk;
+    int64_t out_len[kMaxAxes];
+};
+
+template <int N>
+__global__ __launch_bounds__(kAffineRows) void dgrad_affine_reduce_kernel(AffineReduceArgs r)
+{
+    constexpr int M = N * (N + 1);
+    constexpr int NW = kAffineRows / 64;
+    __shared__ double s_w[NW * M];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t chunk = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int64_t row = chunk * kAffineRows + tid;
+    double v[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k)
+        v[k] = 0.0;
+    if (row < r.rows) {
+        double o[N];
+        int64_t q = row;
+        o[N - 1] = 0.0;
+#pragma unroll
+        for (int d = N - 2; d >= 0; --d) {
+            o[d] = (double)(q % r.out_len[d]);
+            q /= r.out_len[d];
+        }
+        const double* m = r.mom + (b * r.rows + row) * 2 * N;
+#pragma unroll
+        for (int h = 0; h < N; ++h) {
+            const double s0 = m[2 * h], s1 = m[2 * h + 1];
+#pragma unroll
+            for (int l = 0; l < N - 1; ++l)
+                v[h * (N + 1) + l] = o[l] * s0;
+            v[h * (N + 1) + N - 1] = s1;
+            v[h * (N + 1) + N] = s0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0)
+            s_w[wave * M + k] = s;
+    }
+    __syncthreads();
+    if (tid < M) {
+        double sum = 0.0;
+        for (int w = 0; w < NW; ++w)
+            sum += s_w[w * M + tid];
+        r.part[(b * r.nchunk + chunk) * M + tid] = sum;
+    }
+}
+
+// one wavefront per (dK entry, sample): lane l sums the partials l, l + 64, ... in order, then a butterfly
+struct AffineStoreArgs {
+    const double* part;           // [nbatch][nchunk][n][n+1]; nchunk == 0: nothing contributes, dK = 0
+    int64_t nchunk;
+    int naxis;
+    char* dst;                    // float64 (n, n+1), any strides
+    int64_t dst_stride[2];
+    int64_t dst_bstride;
+};
+
+__global__ __launch_bounds__(64) void dgrad_affine_store_kernel(AffineStoreArgs s)
+{
+    const int lane = threadIdx.x;
+    const int k = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int M = s.naxis * (s.naxis + 1);
+    double acc = 0.0;
+    for (int64_t c = lane; c < s.nchunk; c += 64)
+        acc += s.part[(b * s.nchunk + c) * M + k];
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        const int h = k / (s.naxis + 1), l = k % (s.naxis + 1);
+        *(double*)(s.dst + b * s.dst_bstride + h * s.dst_stride[0] + l * s.dst_stride[1]) = acc;
+    }
+}
+
+template <int N, int P, typename T, bool AK>
 hipError_t launch_rows_one(const RowArgs& a, int block, int nbatch, hipStream_t stream)
 {
-    hipLaunchKernelGGL((dgrad_rows_kernel<N, P, T>), dim3((unsigned)a.rows, (unsigned)nbatch), dim3(block), 0, stream,
-                       a);
+    hipLaunchKernelGGL((dgrad_rows_kernel<N, P, T, AK>), dim3((unsigned)a.rows, (unsigned)nbatch), dim3(block), 0,
+                       stream, a);
     return hipGetLastError();
 }
 
-template <int N>
+template <int N, bool AK>
 hipError_t launch_rows(const RowArgs& a, int block, int nbatch, hipStream_t stream)
 {
     if constexpr (N == 2 || N == 3) {
         const bool f32 = a.v.in_dtype == EDHIP_F32;
         switch (a.v.order) {
-        case 1: return f32 ? launch_rows_one<N, 1, float>(a, block, nbatch, stream) : launch_rows_one<N, 1, double>(a, block, nbatch, stream);
-        case 2: return f32 ? launch_rows_one<N, 2, float>(a, block, nbatch, stream) : launch_rows_one<N, 2, double>(a, block, nbatch, stream);
-        case 3: return f32 ? launch_rows_one<N, 3, float>(a, block, nbatch, stream) : launch_rows_one<N, 3, double>(a, block, nbatch, stream);
-        case 4: return f32 ? launch_rows_one<N, 4, float>(a, block, nbatch, stream) : launch_rows_one<N, 4, double>(a, block, nbatch, stream);
-        default: return f32 ? launch_rows_one<N, 5, float>(a, block, nbatch, stream) : launch_rows_one<N, 5, double>(a, block, nbatch, stream);
+        case 1: return f32 ? launch_rows_one<N, 1, float, AK>(a, block, nbatch, stream) : launch_rows_one<N, 1, double, AK>(a, block, nbatch, stream);
+        case 2: return f32 ? launch_rows_one<N, 2, float, AK>(a, block, nbatch, stream) : launch_rows_one<N, 2, double, AK>(a, block, nbatch, stream);
+        case 3: return f32 ? launch_rows_one<N, 3, float, AK>(a, block, nbatch, stream) : launch_rows_one<N, 3, double, AK>(a, block, nbatch, stream);
+        case 4: return f32 ? launch_rows_one<N, 4, float, AK>(a, block, nbatch, stream) : launch_rows_one<N, 4, double, AK>(a, block, nbatch, stream);
+        default: return f32 ? launch_rows_one<N, 5, float, AK>(a, block, nbatch, stream) : launch_rows_one<N, 5, double, AK>(a, block, nbatch, stream);
         }
     } else {
-        return launch_rows_one<N, 0, double>(a, block, nbatch, stream);
+        return launch_rows_one<N, 0, double, AK>(a, block, nbatch, stream);
     }
 }
 
+template <int N>
+hipError_t launch_rows_ak(const RowArgs& a, int block, int nbatch, hipStream_t stream)
+{
+    return a.mom ? launch_rows<N, true>(a, block, nbatch, stream) : launch_rows<N, false>(a, block, nbatch, stream);
+}
+
+template <int N>
+hipError_t launch_affine_reduce(const AffineReduceArgs& r, int nbatch, hipStream_t stream)
+{
+    hipLaunchKernelGGL((dgrad_affine_reduce_kernel<N>), dim3((unsigned)r.nchunk, (unsigned)nbatch), dim3(kAffineRows),
+                       0, stream, r);
+    return hipGetLastError();
+}
+
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int64_t affine_chunks(int64_t rows) { return (rows + kAffineRows - 1) / kAffineRows; }
+
+// the inverse map's scratch: the row moments, then the reduce kernel's partials
+size_t affine_scratch_bytes(const GridGeom& g, int nbatch, int64_t rows)
+{
+    const size_t n = (size_t)g.naxis;
+    return align256((size_t)nbatch * (size_t)rows * n * 2 * 8) +
+           align256((size_t)nbatch * (size_t)affine_chunks(rows) * n * (n + 1) * 8);
+}
+
+int64_t row_count(const GridGeom& g)
+{
+    int64_t rows = 1;
+    for (int d = 0; d < g.naxis - 1; ++d)
+        rows *= g.out_len[d];
+    return rows;
+}
 
 // the two contraction buffers: the largest intermediate [b][o_0..o_{d-1}][j_d..j_{n-2}][K]
 size_t stage_elems(const GridGeom& g, int nbatch, int d)
@@ -544,33 +716,41 @@ bool dgrad_supported(const GridGeom& g)
     return g.naxis >= 1 && g.naxis <= kMaxAxes && (int64_t)g.naxis * g.ncp[g.naxis - 1] <= kDgradMaxK;
 }
 
-size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch)
+size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch, bool dp, bool dk)
 {
-    // part (d = n-1: every o_0..o_{n-2}) + the largest later stage, twice
+    // dP: part (d = n-1: every o_0..o_{n-2}) + the largest later stage, twice; dK: the row moments + partials
     size_t big = 0;
     for (int d = 0; d < g.naxis - 1; ++d)
         big = stage_elems(g, nbatch, d) > big ? stage_elems(g, nbatch, d) : big;
     big = stage_elems(g, nbatch, 0) > big ? stage_elems(g, nbatch, 0) : big;
-    return align256(stage_elems(g, nbatch, g.naxis - 1) * 8) + 2 * align256(big * 8);
+    const size_t dp_bytes = dp ? align256(stage_elems(g, nbatch, g.naxis - 1) * 8) + 2 * align256(big * 8) : 0;
+    return dp_bytes + (dk ? affine_scratch_bytes(g, nbatch, row_count(g)) : 0);
 }
 
 hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream)
 {
     const GridGeom& g = c.g;
     const int n = g.naxis;
-    if (!dgrad_supported(g))
+    if (!dgrad_supported(g) || (!c.dst && !c.dK))
         return hipErrorNotSupported;
+    const bool want_dp = c.dst != nullptr, want_dk = c.dK != nullptr;
     const int K = n * (int)g.ncp[n - 1];
-    int64_t rows = 1;
-    for (int d = 0; d < n - 1; ++d)
-        rows *= g.out_len[d];
-    double* part = (double*)c.scratch;
+    const int64_t rows = row_count(g);
+    // scratch: [part | buf0 | buf1] (dP wanted) [mom | affine partials] (dK wanted)
     size_t big = 0;
     for (int d = 0; d < n - 1; ++d)
         big = stage_elems(g, c.nbatch, d) > big ? stage_elems(g, c.nbatch, d) : big;
     big = stage_elems(g, c.nbatch, 0) > big ? stage_elems(g, c.nbatch, 0) : big;
-    double* buf[2] = {(double*)(c.scratch + align256(stage_elems(g, c.nbatch, n - 1) * 8)), nullptr};
-    buf[1] = (double*)((char*)buf[0] + align256(big * 8));
+    double* part = want_dp ? (double*)c.scratch : nullptr;
+    double* buf[2] = {nullptr, nullptr};
+    char* tail = c.scratch;
+    if (want_dp) {
+        buf[0] = (double*)(c.scratch + align256(stage_elems(g, c.nbatch, n - 1) * 8));
+        buf[1] = (double*)((char*)buf[0] + align256(big * 8));
+        tail = (char*)buf[1] + align256(big * 8);
+    }
+    double* mom = want_dk ? (double*)tail : nullptr;
+    double* apart = want_dk ? (double*)(tail + align256((size_t)c.nbatch * (size_t)rows * (size_t)n * 2 * 8)) : nullptr;
 
     hipError_t e = hipSuccess;
     const int64_t L = g.out_len[n - 1];
@@ -586,6 +766,7 @@ hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream)
             a.g = g;
             a.v = v;
             a.part = part;
+            a.mom = mom;
             a.rows = rows;
             a.K = K;
             a.accumulate = any ? 1 : 0;
@@ -593,13 +774,13 @@ hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream)
             a.out_bstride = c.out_bstride;
             a.disp_bstride = c.disp_bstride;
             switch (n) {
-            case 1: e = launch_rows<1>(a, block, c.nbatch, stream); break;
-            case 2: e = launch_rows<2>(a, block, c.nbatch, stream); break;
-            case 3: e = launch_rows<3>(a, block, c.nbatch, stream); break;
-            case 4: e = launch_rows<4>(a, block, c.nbatch, stream); break;
-            case 5: e = launch_rows<5>(a, block, c.nbatch, stream); break;
-            case 6: e = launch_rows<6>(a, block, c.nbatch, stream); break;
-            default: e = launch_rows<7>(a, block, c.nbatch, stream); break;
+            case 1: e = launch_rows_ak<1>(a, block, c.nbatch, stream); break;
+            case 2: e = launch_rows_ak<2>(a, block, c.nbatch, stream); break;
+            case 3: e = launch_rows_ak<3>(a, block, c.nbatch, stream); break;
+            case 4: e = launch_rows_ak<4>(a, block, c.nbatch, stream); break;
+            case 5: e = launch_rows_ak<5>(a, block, c.nbatch, stream); break;
+            case 6: e = launch_rows_ak<6>(a, block, c.nbatch, stream); break;
+            default: e = launch_rows_ak<7>(a, block, c.nbatch, stream); break;
             }
             any = true;
         }
@@ -608,6 +789,46 @@ hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream)
     }
     if (e != hipSuccess)
         return e;
+
+    if (want_dk) {
+        // dK: rows -> per-workgroup partials -> dK; nothing contributes: the store kernel writes exact zeros
+        AffineReduceArgs r;
+        memset(&r, 0, sizeof(r));
+        r.mom = mom;
+        r.part = apart;
+        r.rows = rows;
+        r.nchunk = any ? affine_chunks(rows) : 0;
+        for (int d = 0; d < n; ++d)
+            r.out_len[d] = g.out_len[d];
+        if (any) {
+            switch (n) {
+            case 1: e = launch_affine_reduce<1>(r, c.nbatch, stream); break;
+            case 2: e = launch_affine_reduce<2>(r, c.nbatch, stream); break;
+            case 3: e = launch_affine_reduce<3>(r, c.nbatch, stream); break;
+            case 4: e = launch_affine_reduce<4>(r, c.nbatch, stream); break;
+            case 5: e = launch_affine_reduce<5>(r, c.nbatch, stream); break;
+            case 6: e = launch_affine_reduce<6>(r, c.nbatch, stream); break;
+            default: e = launch_affine_reduce<7>(r, c.nbatch, stream); break;
+            }
+            if (e != hipSuccess)
+                return e;
+        }
+        AffineStoreArgs s;
+        memset(&s, 0, sizeof(s));
+        s.part = apart;
+        s.nchunk = r.nchunk;
+        s.naxis = n;
+        s.dst = c.dK;
+        s.dst_stride[0] = c.dK_stride[0];
+        s.dst_stride[1] = c.dK_stride[1];
+        s.dst_bstride = c.dK_bstride;
+        hipLaunchKernelGGL(dgrad_affine_store_kernel, dim3((unsigned)(n * (n + 1)), (unsigned)c.nbatch), dim3(64), 0,
+                           stream, s);
+        e = hipGetLastError();
+        if (e != hipSuccess || !want_dp)
+            return e;
+    }
+
     const double* cur = part;
     if (!any) {
         // nothing contributes (no output voxel, order 0, empty step axes): dP = 0

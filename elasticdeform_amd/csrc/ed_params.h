@@ -161,20 +161,25 @@ hipError_t launch_grid_prefilter(const GridPrefilter& p, hipStream_t stream);
 // Row kernel (one workgroup per output row along the last deformed axis; blockIdx.y = sample) -> fp64 partials
 // per (row, h, j_last) in `part`; one contraction launch per remaining deformed axis (fixed summation order, no
 // atomics); a last launch writes dP with the layout / dtype of `dst`.  All scratch comes from the caller.
+// With `dK` the same row pass also leaves per-row moments of g, reduced in a fixed order to dK[h, l] =
+// d(sum <dY, Y>) / d(inverse map)[h, l] (float64, naxis x (naxis+1) per sample).  At least one of dst / dK.
 struct DgradCall {
     GridGeom g;                   // g.disp: the prefiltered grid of sample 0
     int ninputs;
     const IOView* views;          // host array: v.in = C_i (read), v.out = dY_i (read); orders 1..5 only
     int nbatch;
     int64_t in_bstride, out_bstride, disp_bstride, dst_bstride;   // bytes between samples
-    char* dst;                    // dP, shape (naxis, ncp_0, ...) per sample
+    char* dst;                    // dP, shape (naxis, ncp_0, ...) per sample; nullptr: not wanted
     int dst_dtype;
     int64_t dst_stride[kMaxAxes + 1];
-    char* scratch;                // dgrad_scratch_bytes(g, nbatch) bytes of device scratch
+    char* dK;                     // float64 dK, shape (naxis, naxis+1) per sample; nullptr: not wanted
+    int64_t dK_stride[2];
+    int64_t dK_bstride;
+    char* scratch;                // dgrad_scratch_bytes(g, nbatch, dst != nullptr, dK != nullptr) bytes of device scratch
 };
 constexpr int kDgradMaxK = 256;   // naxis * ncp_{naxis-1}: the row kernel's per-row band of the last grid axis
 bool dgrad_supported(const GridGeom& g);
-size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch);
+size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch, bool dp = true, bool dk = false);
 hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream);
 
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid

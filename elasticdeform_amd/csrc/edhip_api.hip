@@ -987,15 +987,15 @@ int edhip_spline_filter_axes(const edhip_array* input, const edhip_array* output
 }
 
 
-// ---- gradient with respect to the control-point displacement (deform_dgrad.hip) ------------------------------
+// ---- gradient with respect to the control-point displacement and the inverse map (deform_dgrad.hip) ---------
 // nbatch samples at constant byte distances (nbatch == 1: a single call); RAW_DISPLACEMENT batches arrive here
-// one sample at a time.
+// one sample at a time.  ddisplacement / dinverse_affine: nullptr = not wanted (not both).
 static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
                       const int64_t* output_offset, const edhip_array* doutputs, int naxis, const int32_t* axis,
                       const int32_t* orders, const int32_t* modes, const double* cvals, const double* affine,
-                      const edhip_array* ddisplacement, uint32_t flags, hipStream_t stream, int nbatch,
-                      int64_t in_bstride, int64_t disp_bstride, int64_t dout_bstride, int64_t ddisp_bstride,
-                      bool dry, char* err, size_t errlen)
+                      const edhip_array* ddisplacement, const edhip_array* dinverse_affine, uint32_t flags,
+                      hipStream_t stream, int nbatch, int64_t in_bstride, int64_t disp_bstride, int64_t dout_bstride,
+                      int64_t ddisp_bstride, int64_t dinv_bstride, bool dry, char* err, size_t errlen)
 {
     using namespace ed;
     // ---- the checks of edhip_deform (_deform_grid.c:121-255), then the dtypes this gradient takes ----------------
@@ -1041,13 +1041,23 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
             return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
         points *= displacement->shape[k];
     }
-    if (!ddisplacement || ddisplacement->ndim != displacement->ndim)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-    for (int k = 0; k <= naxis; ++k)
-        if (ddisplacement->shape[k] != displacement->shape[k])
+    if (!ddisplacement && !dinverse_affine)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
+    if (ddisplacement) {
+        if (ddisplacement->ndim != displacement->ndim)
             return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-    if (!dtype_ok(ddisplacement->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+        for (int k = 0; k <= naxis; ++k)
+            if (ddisplacement->shape[k] != displacement->shape[k])
+                return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        if (!dtype_ok(ddisplacement->dtype))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    }
+    if (dinverse_affine) {
+        if (dinverse_affine->ndim != 2 || dinverse_affine->shape[0] != naxis || dinverse_affine->shape[1] != naxis + 1)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
     const bool raw = (flags & EDHIP_FLAG_RAW_DISPLACEMENT) != 0;
     if (raw && points > 4096)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "raw displacement grids are limited to 4096 points");
@@ -1087,7 +1097,7 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
     size_t off = kWorkspaceGridBytes;
     const size_t dp_off = off + (raw ? grid_bytes : 0);
     const size_t sc_off = dp_off + (raw ? grid_bytes : 0);
-    size_t need = sc_off + dgrad_scratch_bytes(g, nbatch);
+    size_t need = sc_off + dgrad_scratch_bytes(g, nbatch, ddisplacement != nullptr, dinverse_affine != nullptr);
     if (raw && deform_tile_workspace_bytes(g, 1, false) > need)
         need = deform_tile_workspace_bytes(g, 1, false);
     hipError_t e = hipSuccess;
@@ -1120,17 +1130,25 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
     c.in_bstride = in_bstride;
     c.out_bstride = dout_bstride;
     c.disp_bstride = disp_bstride;
-    const edhip_array& dst = raw ? dp : *ddisplacement;
-    c.dst = (char*)dst.data;
-    c.dst_dtype = dst.dtype;
-    c.dst_bstride = ddisp_bstride;
-    for (int k = 0; k <= naxis; ++k)
-        c.dst_stride[k] = dst.stride_bytes[k];
+    if (ddisplacement) {
+        const edhip_array& dst = raw ? dp : *ddisplacement;
+        c.dst = (char*)dst.data;
+        c.dst_dtype = dst.dtype;
+        c.dst_bstride = ddisp_bstride;
+        for (int k = 0; k <= naxis; ++k)
+            c.dst_stride[k] = dst.stride_bytes[k];
+    }
+    if (dinverse_affine) {
+        c.dK = (char*)dinverse_affine->data;
+        c.dK_stride[0] = dinverse_affine->stride_bytes[0];
+        c.dK_stride[1] = dinverse_affine->stride_bytes[1];
+        c.dK_bstride = dinv_bstride;
+    }
     c.scratch = ws + sc_off;
     e = launch_deform_dgrad(c, stream);
     if (e != hipSuccess)
         return hip_fail(err, errlen, e, "displacement gradient launch");
-    if (raw) {
+    if (raw && ddisplacement) {
         // dD = (order-3 mirror prefilter)^T along the grid axes, in fp64, then one cast into the caller's array
         for (int k = 1; k <= naxis; ++k) {
             st = filter1d_impl(&dp, &dp, k, 3, 1, flags & EDHIP_FLAG_EXACT, stream, nullptr, false, err, errlen);
@@ -1144,18 +1162,98 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
     return EDHIP_OK;
 }
 
-int edhip_deform_displacement_gradient(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
-                                       const int64_t* output_offset, const edhip_array* doutputs, int naxis,
-                                       const int32_t* axis, const int32_t* orders, const int32_t* modes,
-                                       const double* cvals, const double* affine, const edhip_array* ddisplacement,
-                                       uint32_t flags, void* hip_stream, char* err, size_t errlen)
+// the two pairs of entry points: edhip_deform_displacement_gradient* = edhip_deform_transform_gradient* without
+// the inverse map's result
+static int transform_gradient_batch(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                                    const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                    const int64_t* output_offset, const edhip_array* doutput0,
+                                    int64_t doutput_batch_stride, int naxis, const int32_t* axis, int32_t order,
+                                    int32_t mode, double cval, const double* affine,
+                                    const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                    const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                    uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || (nbatch > 0 && (!input0 || !displacement0 || !doutput0)))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (!ddisplacement0 && !dinverse_affine0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
+    if (nbatch == 0)
+        return EDHIP_OK;
+    ed::StreamGuard guard(stream);
+    if (!(flags & EDHIP_FLAG_RAW_DISPLACEMENT))
+        return dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval,
+                          affine, ddisplacement0, dinverse_affine0, flags, stream, nbatch, input_batch_stride,
+                          displacement_batch_stride, doutput_batch_stride, ddisplacement_batch_stride,
+                          dinverse_affine_batch_stride, false, err, errlen);
+    // raw grids: each sample's grid is prefiltered into the workspace head, so the samples go one after the other
+    // (every argument is checked before the first launch)
+    int st = dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval, affine,
+                        ddisplacement0, dinverse_affine0, flags, stream, 1, 0, 0, 0, 0, 0, true, err, errlen);
+    for (int b = 0; b < nbatch && st == EDHIP_OK; ++b) {
+        edhip_array in = *input0, disp = *displacement0, dout = *doutput0, ddisp, dinv;
+        in.data = (char*)input0->data + (int64_t)b * input_batch_stride;
+        disp.data = (char*)displacement0->data + (int64_t)b * displacement_batch_stride;
+        dout.data = (char*)doutput0->data + (int64_t)b * doutput_batch_stride;
+        if (ddisplacement0) {
+            ddisp = *ddisplacement0;
+            ddisp.data = (char*)ddisplacement0->data + (int64_t)b * ddisplacement_batch_stride;
+        }
+        if (dinverse_affine0) {
+            dinv = *dinverse_affine0;
+            dinv.data = (char*)dinverse_affine0->data + (int64_t)b * dinverse_affine_batch_stride;
+        }
+        st = dgrad_impl(1, &in, &disp, output_offset, &dout, naxis, axis, &order, &mode, &cval, affine,
+                        ddisplacement0 ? &ddisp : nullptr, dinverse_affine0 ? &dinv : nullptr, flags, stream, 1, 0, 0,
+                        0, 0, 0, false, err, errlen);
+    }
+    return st;
+}
+
+int edhip_deform_transform_gradient(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
+                                    const int64_t* output_offset, const edhip_array* doutputs, int naxis,
+                                    const int32_t* axis, const int32_t* orders, const int32_t* modes,
+                                    const double* cvals, const double* affine, const edhip_array* ddisplacement,
+                                    const edhip_array* dinverse_affine, uint32_t flags, void* hip_stream, char* err,
+                                    size_t errlen)
 {
     hipStream_t stream = (hipStream_t)hip_stream;
     ed::StreamGuard guard(stream);
     if (err && errlen)
         err[0] = 0;
     return dgrad_impl(ninputs, inputs, displacement, output_offset, doutputs, naxis, axis, orders, modes, cvals,
-                      affine, ddisplacement, flags, stream, 1, 0, 0, 0, 0, false, err, errlen);
+                      affine, ddisplacement, dinverse_affine, flags, stream, 1, 0, 0, 0, 0, 0, false, err, errlen);
+}
+
+int edhip_deform_transform_gradient_batch_strided(
+    int nbatch, const edhip_array* input0, int64_t input_batch_stride, const edhip_array* displacement0,
+    int64_t displacement_batch_stride, const int64_t* output_offset, const edhip_array* doutput0,
+    int64_t doutput_batch_stride, int naxis, const int32_t* axis, int32_t order, int32_t mode, double cval,
+    const double* affine, const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+    const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride, uint32_t flags, void* hip_stream,
+    char* err, size_t errlen)
+{
+    return transform_gradient_batch(nbatch, input0, input_batch_stride, displacement0, displacement_batch_stride,
+                                    output_offset, doutput0, doutput_batch_stride, naxis, axis, order, mode, cval,
+                                    affine, ddisplacement0, ddisplacement_batch_stride, dinverse_affine0,
+                                    dinverse_affine_batch_stride, flags, hip_stream, err, errlen);
+}
+
+int edhip_deform_displacement_gradient(int ninputs, const edhip_array* inputs, const edhip_array* displacement,
+                                       const int64_t* output_offset, const edhip_array* doutputs, int naxis,
+                                       const int32_t* axis, const int32_t* orders, const int32_t* modes,
+                                       const double* cvals, const double* affine, const edhip_array* ddisplacement,
+                                       uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    if (err && errlen)
+        err[0] = 0;
+    if (!ddisplacement)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+    return edhip_deform_transform_gradient(ninputs, inputs, displacement, output_offset, doutputs, naxis, axis, orders,
+                                           modes, cvals, affine, ddisplacement, nullptr, flags, hip_stream, err,
+                                           errlen);
 }
 
 int edhip_deform_displacement_gradient_batch_strided(
@@ -1165,32 +1263,16 @@ int edhip_deform_displacement_gradient_batch_strided(
     const double* affine, const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride, uint32_t flags,
     void* hip_stream, char* err, size_t errlen)
 {
-    hipStream_t stream = (hipStream_t)hip_stream;
     if (err && errlen)
         err[0] = 0;
-    if (nbatch < 0 || (nbatch > 0 && (!input0 || !displacement0 || !doutput0 || !ddisplacement0)))
+    if (nbatch < 0 || (nbatch > 0 && !ddisplacement0))
         return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
     if (nbatch == 0)
         return EDHIP_OK;
-    ed::StreamGuard guard(stream);
-    if (!(flags & EDHIP_FLAG_RAW_DISPLACEMENT))
-        return dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval,
-                          affine, ddisplacement0, flags, stream, nbatch, input_batch_stride, displacement_batch_stride,
-                          doutput_batch_stride, ddisplacement_batch_stride, false, err, errlen);
-    // raw grids: each sample's grid is prefiltered into the workspace head, so the samples go one after the other
-    // (every argument is checked before the first launch)
-    int st = dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval, affine,
-                        ddisplacement0, flags, stream, 1, 0, 0, 0, 0, true, err, errlen);
-    for (int b = 0; b < nbatch && st == EDHIP_OK; ++b) {
-        edhip_array in = *input0, disp = *displacement0, dout = *doutput0, ddisp = *ddisplacement0;
-        in.data = (char*)input0->data + (int64_t)b * input_batch_stride;
-        disp.data = (char*)displacement0->data + (int64_t)b * displacement_batch_stride;
-        dout.data = (char*)doutput0->data + (int64_t)b * doutput_batch_stride;
-        ddisp.data = (char*)ddisplacement0->data + (int64_t)b * ddisplacement_batch_stride;
-        st = dgrad_impl(1, &in, &disp, output_offset, &dout, naxis, axis, &order, &mode, &cval, affine, &ddisp, flags,
-                        stream, 1, 0, 0, 0, 0, false, err, errlen);
-    }
-    return st;
+    return transform_gradient_batch(nbatch, input0, input_batch_stride, displacement0, displacement_batch_stride,
+                                    output_offset, doutput0, doutput_batch_stride, naxis, axis, order, mode, cval,
+                                    affine, ddisplacement0, ddisplacement_batch_stride, nullptr, 0, flags, hip_stream,
+                                    err, errlen);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@ output is cval everywhere, the gradient zero -- decided on the host (the C ABI i
 
 There is no CPU fallback: without a GPU or without the built library the call raises.
 """
+import collections
 import os
 import sys
 import threading
@@ -953,16 +954,11 @@ def _result_tensor_dtype(displacement):
     return getattr(torch, dt.name) if isinstance(dt, numpy.dtype) else dt
 
 
-def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None,
-                                      prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
-    """
-    Gradient of :func:`deform_grid` with respect to the control-point ``displacement``: the array
-    ``d(sum_i <dY_i, Y_i>) / d displacement`` where ``Y = deform_grid(X, displacement, ...)`` with the same
-    arguments (the order-3 prefilter of the grid included).  ``X`` and ``dY`` are arrays or lists of arrays
-    (float32 / float64), ``dY[i]`` of the shape of ``Y[i]``.  Returns an array of the displacement's shape, in its
-    dtype when that is floating (float64 otherwise): numpy for a numpy ``dY``, otherwise a tensor on ``dY``'s
-    device.  The sum over the volume runs in fp64 in a fixed order: repeated calls return the same bits.
-    """
+def _transform_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                        axis=None, affine=None, rotate=None, zoom=None, want_disp=True, want_map=False):
+    """One library call for the gradients with respect to the displacement (`want_disp`) and to the inverse map
+    (`want_map`).  Returns (plan, dYs, d displacement or None, dK or None): the displacement's result in the family
+    of dY, dK a float64 tensor (naxis, naxis+1) on the device."""
     Xs = _host.normalize_inputs(X)
     dYs = _host.normalize_inputs(dY)
     plan = _host.cached_plan(Xs, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
@@ -971,10 +967,17 @@ def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='consta
         raise ValueError("dY does not match the output shape of deform_grid. Expected output shape is %s, "
                          "but %s given." % (str(plan.output_shapes), str([tuple(dy.shape) for dy in dYs])))
     _check_float_volumes(list(Xs) + list(dYs))
-    if _host.degenerate_axis([x.shape for x in Xs], plan.axis):
-        # (a deformed axis of length 1: every voxel is the constant, nothing depends on the grid)
-        return _dgrad_zeros(displacement, dYs[0])
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
     torch = _torch()
+    n = plan.naxis
+    if _host.degenerate_axis([x.shape for x in Xs], plan.axis):
+        # (a deformed axis of length 1: every voxel is the constant, nothing depends on the grid or the map)
+        dk = None
+        if want_map:
+            dk = torch.zeros((n, n + 1), dtype=torch.float64,
+                             device=dYs[0].device if torch.is_tensor(dYs[0]) else 'cpu')
+        return plan, dYs, (_dgrad_zeros(displacement, dYs[0]) if want_disp else None), dk
     device = _device_for(list(dYs) + list(Xs) + [displacement])
     with torch.cuda.device(device):
         stream = _stream(device)
@@ -986,40 +989,59 @@ def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='consta
             Xf.append(x)
         dYd = [_to_device(dy, device) for dy in dYs]
         dd = _to_device(displacement, device)
-        out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacement), device=device)
-        if dd.numel() <= _lib.RAW_DISPLACEMENT_MAX_POINTS:
-            _lib.deform_displacement_gradient([_desc(x) for x in Xf], _desc(dd), plan.output_offset,
-                                              [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode,
-                                              plan.cval, plan.inverse_affine, _desc(out),
-                                              _flags | _lib.FLAG_RAW_DISPLACEMENT, stream,
-                                              prepared=_prepared(plan, len(Xf)))
-        else:
-            # a large grid: prefiltered here, the gradient of the prefiltered grid transposed here (fp64 throughout)
-            df = _filter_axes(dd, range(1, dd.ndim), 3, False, device, stream=stream)
-            dp = torch.empty(out.shape, dtype=torch.float64, device=device)
-            _lib.deform_displacement_gradient([_desc(x) for x in Xf], _desc(df), plan.output_offset,
-                                              [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode,
-                                              plan.cval, plan.inverse_affine, _desc(dp), _flags, stream,
-                                              prepared=_prepared(plan, len(Xf)))
+        dk = torch.empty((n, n + 1), dtype=torch.float64, device=device) if want_map else None
+        out = None
+        if want_disp:
+            out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacement), device=device)
+        raw = dd.numel() <= _lib.RAW_DISPLACEMENT_MAX_POINTS
+        # a large grid: prefiltered here, the gradient of the prefiltered grid transposed here (fp64 throughout)
+        df = dd if raw else _filter_axes(dd, range(1, dd.ndim), 3, False, device, stream=stream)
+        dp = out if (raw or out is None) else torch.empty(out.shape, dtype=torch.float64, device=device)
+        _lib.deform_transform_gradient([_desc(x) for x in Xf], _desc(df), plan.output_offset,
+                                       [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode, plan.cval,
+                                       plan.inverse_affine, _desc(dp) if dp is not None else None,
+                                       _desc(dk) if dk is not None else None,
+                                       _flags | (_lib.FLAG_RAW_DISPLACEMENT if raw else 0), stream,
+                                       prepared=_prepared(plan, len(Xf)))
+        if out is not None and not raw:
             dp = _filter_axes(dp, range(1, dp.ndim), 3, True, device, overwrite=True, stream=stream)
             out.copy_(dp)
-        return _from_device(out, dYs[0])
+        return plan, dYs, (_from_device(out, dYs[0]) if out is not None else None), dk
 
 
-def deform_grid_displacement_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None,
-                                            prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
-    """:func:`deform_grid_displacement_gradient` over a batch, following :func:`deform_grid_batch`: ``X`` is
-    ``(B, ...)``, ``dY`` the gradient of the batch's output, ``displacements`` ``(B, naxis, n_0, ...)``.  Returns
-    ``(B, naxis, n_0, ...)``; sample ``b`` is the same bits as the single call on sample ``b``."""
+def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None,
+                                      prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid` with respect to the control-point ``displacement``: the array
+    ``d(sum_i <dY_i, Y_i>) / d displacement`` where ``Y = deform_grid(X, displacement, ...)`` with the same
+    arguments (the order-3 prefilter of the grid included).  ``X`` and ``dY`` are arrays or lists of arrays
+    (float32 / float64), ``dY[i]`` of the shape of ``Y[i]``.  Returns an array of the displacement's shape, in its
+    dtype when that is floating (float64 otherwise): numpy for a numpy ``dY``, otherwise a tensor on ``dY``'s
+    device.  The sum over the volume runs in fp64 in a fixed order: repeated calls return the same bits.
+    """
+    return _transform_gradient(X, dY, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                               True, False)[2]
+
+
+def _transform_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                              axis=None, affine=None, rotate=None, zoom=None, want_disp=True, want_map=False):
+    """The batch form of _transform_gradient: (plan, d displacements or None, dK (B, naxis, naxis+1) or None)."""
     plan = _batch_plan(X, displacements, order, mode, cval, crop, axis, affine, rotate, zoom)
     if not _host.is_array(dY) or tuple(int(v) for v in dY.shape) != (int(X.shape[0]),) + tuple(plan.output_shapes[0]):
         raise ValueError("dY does not match the output shape of deform_grid_batch. Expected output shape is %s, "
                          "but %s given." % (str((int(X.shape[0]),) + tuple(plan.output_shapes[0])),
                                             str(tuple(dY.shape) if _host.is_array(dY) else dY)))
     _check_float_volumes([X, dY])
-    if _host.degenerate_axis([X.shape[1:]], plan.axis):
-        return _dgrad_zeros(displacements, dY)
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
     torch = _torch()
+    n = plan.naxis
+    B = int(X.shape[0])
+    if _host.degenerate_axis([X.shape[1:]], plan.axis):
+        dk = None
+        if want_map:
+            dk = torch.zeros((B, n, n + 1), dtype=torch.float64, device=dY.device if torch.is_tensor(dY) else 'cpu')
+        return plan, (_dgrad_zeros(displacements, dY) if want_disp else None), dk
     device = _device_for([dY, X, displacements])
     with torch.cuda.device(device):
         stream = _stream(device)
@@ -1030,23 +1052,126 @@ def deform_grid_displacement_gradient_batch(X, dY, displacements, order=3, mode=
             Xd = _filter_axes(Xd, [a + 1 for a in ax], o, False, device, stream=stream)
         dYd = _to_device(dY, device)
         dd = _to_device(displacements, device)
-        B = int(Xd.shape[0])
-        out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacements), device=device)
+        out = None
+        if want_disp:
+            out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacements), device=device)
+        dk = torch.empty((B, n, n + 1), dtype=torch.float64, device=device) if want_map else None
         per_sample = int(numpy.prod([int(v) for v in dd.shape[1:]]))
+        raw = per_sample <= _lib.RAW_DISPLACEMENT_MAX_POINTS
         (xd, xs), (yd, ys) = _desc_sample0(Xd), _desc_sample0(dYd)
-        if per_sample <= _lib.RAW_DISPLACEMENT_MAX_POINTS:
-            (gd, gs), (od, os_) = _desc_sample0(dd), _desc_sample0(out)
-            _lib.deform_displacement_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
-                                                            int(plan.mode[0]), float(plan.cval[0]),
-                                                            plan.inverse_affine, od, os_,
-                                                            _flags | _lib.FLAG_RAW_DISPLACEMENT, stream)
-        else:
-            df = _filter_axes(dd, range(2, dd.ndim), 3, False, device, stream=stream)
-            dp = torch.empty(out.shape, dtype=torch.float64, device=device)
-            (gd, gs), (pd, ps) = _desc_sample0(df), _desc_sample0(dp)
-            _lib.deform_displacement_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
-                                                            int(plan.mode[0]), float(plan.cval[0]),
-                                                            plan.inverse_affine, pd, ps, _flags, stream)
+        df = dd if raw else _filter_axes(dd, range(2, dd.ndim), 3, False, device, stream=stream)
+        dp = out if (raw or out is None) else torch.empty(out.shape, dtype=torch.float64, device=device)
+        (gd, gs) = _desc_sample0(df)
+        (pd, ps) = _desc_sample0(dp) if dp is not None else (None, 0)
+        (kd, ks) = _desc_sample0(dk) if dk is not None else (None, 0)
+        _lib.deform_transform_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
+                                                     int(plan.mode[0]), float(plan.cval[0]), plan.inverse_affine,
+                                                     pd, ps, kd, ks,
+                                                     _flags | (_lib.FLAG_RAW_DISPLACEMENT if raw else 0), stream)
+        if out is not None and not raw:
             dp = _filter_axes(dp, range(2, dp.ndim), 3, True, device, overwrite=True, stream=stream)
             out.copy_(dp)
-        return _from_device(out, dY)
+        return plan, (_from_device(out, dY) if out is not None else None), dk
+
+
+def deform_grid_displacement_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None,
+                                            prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_displacement_gradient` over a batch, following :func:`deform_grid_batch`: ``X`` is
+    ``(B, ...)``, ``dY`` the gradient of the batch's output, ``displacements`` ``(B, naxis, n_0, ...)``.  Returns
+    ``(B, naxis, n_0, ...)``; sample ``b`` is the same bits as the single call on sample ``b``."""
+    return _transform_gradient_batch(X, dY, displacements, order, mode, cval, crop, prefilter, axis, affine, rotate,
+                                     zoom, True, False)[1]
+
+
+# ---- gradient with respect to affine, rotate and zoom (no counterpart in the reference) -------------------------
+
+AffineGradient = collections.namedtuple('AffineGradient', ['affine', 'rotate', 'zoom', 'inverse_map'])
+
+
+def _affine_jacobian(plan, affine, rotate, zoom, device):
+    """(J, shape of the affine gradient) of the plan -- J = d inverse_map / d(affine, rotate, zoom), formed once per
+    plan on the host (_affine_grad.jacobian); with a device: J as a float64 tensor there, kept with the plan so that a
+    repeated call (and a HIP graph capture after warm-up) copies nothing to the device."""
+    if plan.affine_jacobian is None:
+        from . import _affine_grad
+        J, ashape = _affine_grad.jacobian(affine, rotate, zoom, plan.naxis,
+                                          [plan.output_shapes[0][d] for d in plan.axis[0]])
+        plan.affine_jacobian = (J, ashape, {})
+    J, ashape, on_device = plan.affine_jacobian
+    if device is None:
+        return J, ashape
+    key = str(device)
+    if key not in on_device:
+        on_device[key] = _torch().from_numpy(J).to(device)
+    return on_device[key], ashape
+
+
+def _affine_result(dk, plan, affine, rotate, zoom, numpy_out):
+    """dK (naxis, naxis+1) -> AffineGradient: theta = J^T vec(dK), split into the affine (its own shape), rotate and
+    zoom; numpy / floats when `numpy_out`, otherwise float64 tensors on dK's device."""
+    torch = _torch()
+    if numpy_out:
+        g = dk.cpu().numpy() if torch.is_tensor(dk) else numpy.asarray(dk)
+        J, ashape = _affine_jacobian(plan, affine, rotate, zoom, None)
+        theta = numpy.dot(J.T, g.reshape(-1))
+    else:
+        g = dk
+        J, ashape = _affine_jacobian(plan, affine, rotate, zoom, dk.device)
+        theta = (J * g.reshape(-1, 1)).sum(0)
+    na = int(numpy.prod(ashape))
+    k = na
+    rot = zm = None
+    if rotate is not None:
+        rot = float(theta[k]) if numpy_out else theta[k]
+        k += 1
+    if zoom is not None:
+        zm = float(theta[k]) if numpy_out else theta[k]
+    return AffineGradient(theta[:na].reshape(ashape), rot, zm, g)
+
+
+def deform_grid_affine_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                                axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid` with respect to its affine part: ``L = sum_i <dY_i, Y_i>`` differentiated with
+    respect to ``affine``, ``rotate`` and ``zoom``.  Arguments and checks as for
+    :func:`deform_grid_displacement_gradient`.  Returns ``AffineGradient(affine, rotate, zoom, inverse_map)``:
+
+    * ``affine``: dL / d affine in the shape given (the homogeneous 3 x 3 in 2-D included); with ``affine=None`` the
+      gradient at the identity, shape (naxis, naxis+1).
+    * ``rotate`` (per degree) / ``zoom``: when they are given, otherwise None (2-D only, as in the reference;
+      ``zoom=0`` means "no zoom" there and raises ValueError here).
+    * ``inverse_map``: dL / dK for the map K the kernels apply to the crop-local output index, c = K [o; 1] + offset
+      + displacement (what a spatial transformer parameterises directly).
+
+    numpy (floats for rotate / zoom) for a numpy ``dY``, otherwise float64 tensors on ``dY``'s device.  dK is summed
+    in fp64 in a fixed order on the GPU (repeated calls return the same bits); the chain rule to the parameters is
+    the Jacobian of a float64 restatement of the reference's matrix algebra.
+    """
+    plan, dYs, _, dk = _transform_gradient(X, dY, displacement, order, mode, cval, crop, prefilter, axis, affine,
+                                           rotate, zoom, False, True)
+    return _affine_result(dk, plan, affine, rotate, zoom, isinstance(dYs[0], numpy.ndarray))
+
+
+def _sum_in_order(parts):
+    total = parts[0]
+    for p in parts[1:]:
+        total = total + p
+    return total
+
+
+def _affine_result_batch(dk, plan, affine, rotate, zoom, numpy_out):
+    """per-sample AffineGradients of dK (B, naxis, naxis+1), summed over b = 0, 1, ... in that order"""
+    per = [_affine_result(dk[b], plan, affine, rotate, zoom, numpy_out) for b in range(int(dk.shape[0]))]
+    return AffineGradient(*[None if getattr(per[0], f) is None else _sum_in_order([getattr(r, f) for r in per])
+                            for f in AffineGradient._fields])
+
+
+def deform_grid_affine_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None,
+                                      prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_affine_gradient` over a batch (:func:`deform_grid_batch`: ``X`` ``(B, ...)``,
+    ``displacements`` ``(B, naxis, n_0, ...)``).  ``affine`` / ``rotate`` / ``zoom`` are shared by the batch, so the
+    result is the SUM over the samples: every field is each sample's value (the single call on that sample, same
+    bits) added in fp64 in sample order, b = 0, 1, ..., B-1."""
+    plan, _, dk = _transform_gradient_batch(X, dY, displacements, order, mode, cval, crop, prefilter, axis, affine,
+                                            rotate, zoom, False, True)
+    return _affine_result_batch(dk, plan, affine, rotate, zoom, isinstance(dY, numpy.ndarray))

@@ -5,7 +5,8 @@ drop-in for ``elasticdeform.torch.deform_grid`` (/root/reference/elasticdeform/t
 Same autograd contract as the reference's ``ElasticDeform`` Function (torch.py:5-29): gradients
 flow to the inputs ``X`` only (the displacement gets none), a list / tuple of inputs gives a
 tuple of outputs.  With ``displacement_grad=True`` (keyword-only, an extension) the displacement gets its gradient
-too (``elasticdeform_amd.deform_grid_displacement_gradient``).  The difference is the one this build exists for: the reference copies every
+too (``elasticdeform_amd.deform_grid_displacement_gradient``); with ``affine_grad=True`` ``affine``, ``rotate`` and
+``zoom`` as well (``elasticdeform_amd.deform_grid_affine_gradient``).  The difference is the one this build exists for: the reference copies every
 tensor to the host, runs one CPU thread and copies back (torch.py:13-16,25-29); here CUDA tensors
 stay in HBM and forward / backward are HIP kernels enqueued on the current stream.
 """
@@ -20,6 +21,9 @@ from . import deform_grid_batch as _deform_grid_batch_fn
 from . import deform_grid_gradient_batch as _deform_grid_gradient_batch_fn
 from . import deform_grid_displacement_gradient as _dgrad_fn
 from . import deform_grid_displacement_gradient_batch as _dgrad_batch_fn
+import importlib  # noqa: E402
+
+_api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)
 
 
 class ElasticDeform(torch.autograd.Function):
@@ -72,7 +76,86 @@ class ElasticDeformDisplacement(torch.autograd.Function):
         return (ddisp, None, None) + tuple(dxs)
 
 
-def deform_grid(X, displacement, *args, displacement_grad=False, **kwargs):
+_AFFINE_ARGS = ('affine', 'rotate', 'zoom')
+_AFFINE_POS = 6            # deform_grid(X, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom)
+
+
+def _host_value(v):
+    """a parameter as the forward's NumPy algebra takes it (tensors leave the graph here)"""
+    if torch.is_tensor(v):
+        v = v.detach().cpu()
+        return float(v) if v.dim() == 0 else v.double().numpy()
+    return v
+
+
+def _param_grads(needs, params, grads):
+    """the affine / rotate / zoom gradients for the autograd inputs that need one, in their dtype, on their device"""
+    out = []
+    for need, p, g in zip(needs, params, grads):
+        if need and g is not None:
+            out.append(torch.as_tensor(g, dtype=torch.float64).to(device=p.device, dtype=p.dtype).reshape(p.shape))
+        else:
+            out.append(None)
+    return out
+
+
+class ElasticDeformTransform(torch.autograd.Function):
+    """ElasticDeform with gradients for affine / rotate / zoom (affine_grad=True) and, with displacement_grad=True,
+    for the displacement: both from one library call (deform_grid.py _transform_gradient)."""
+
+    @staticmethod
+    def forward(ctx, displacement, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, *xs):
+        ctx.save_for_backward(displacement, *xs)
+        ctx.params = (affine, rotate, zoom)
+        ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, (affine, rotate, zoom))}
+        ctx.deform_args = deform_args
+        ctx.deform_kwargs = deform_kwargs
+        ctx.disp_grad = disp_grad
+        ctx.x_shapes = [tuple(x.shape) for x in xs]
+        ys = _deform_grid_fn([x.detach() for x in xs], displacement.detach(), *deform_args, **ctx.host,
+                             **deform_kwargs)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        displacement, *xs = ctx.saved_tensors
+        dys = [dy.detach() for dy in dys]
+        kw = dict(ctx.deform_kwargs, **ctx.host)
+        dxs = [None] * len(xs)
+        if any(ctx.needs_input_grad[7:]):
+            dxs = _deform_grid_gradient_fn(dys, displacement.detach(), *ctx.deform_args, X_shape=ctx.x_shapes, **kw)
+        want_disp = ctx.disp_grad and ctx.needs_input_grad[0]
+        want_map = any(ctx.needs_input_grad[1:4])
+        ddisp = None
+        grads = [None, None, None]
+        if want_disp or want_map:
+            plan, _, ddisp, dk = _api._transform_gradient([x.detach() for x in xs], dys, displacement.detach(),
+                                                          *ctx.deform_args, **dict(kw, want_disp=want_disp,
+                                                                                   want_map=want_map))
+            if ddisp is not None:
+                ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+            if dk is not None:
+                r = _api._affine_result(dk, plan, ctx.host['affine'], ctx.host['rotate'], ctx.host['zoom'], False)
+                grads = _param_grads(ctx.needs_input_grad[1:4], ctx.params, r[:3])
+        return (ddisp,) + tuple(grads) + (None, None, None) + tuple(dxs)
+
+
+def _split_affine(args, kwargs):
+    """(args without affine / rotate / zoom, kwargs without them, [affine, rotate, zoom]) -- by keyword or position"""
+    args = list(args)
+    params = []
+    for k, name in enumerate(_AFFINE_ARGS):
+        pos = _AFFINE_POS + k
+        if name in kwargs:
+            params.append(kwargs.pop(name))
+        elif pos < len(args):
+            params.append(args[pos])
+        else:
+            params.append(None)
+    return tuple(args[:_AFFINE_POS]), kwargs, params
+
+
+def deform_grid(X, displacement, *args, displacement_grad=False, affine_grad=False, **kwargs):
     """
     Elastic deformation with a deformation grid, wrapped for PyTorch with a custom gradient.
 
@@ -81,14 +164,22 @@ def deform_grid(X, displacement, *args, displacement_grad=False, **kwargs):
     Returns a tensor, or a tuple of tensors for a list / tuple input (torch.py:56-66).
     displacement_grad : keyword only.  False (the default, the reference's contract): gradients flow to X
     only.  True: the displacement gets its gradient as well (on its device, in its dtype).
+    affine_grad : keyword only.  True: ``affine``, ``rotate`` and ``zoom`` (by keyword or position) may be tensors
+    and get their gradients (in their dtype, on their device); with displacement_grad as well, one library call
+    gives both.  False (the default): they are taken as values, as in the reference.
     """
     if not isinstance(X, (list, tuple)):
         X_list = [X]
     else:
         X_list = X
     displacement = torch.as_tensor(displacement)
-    fn = ElasticDeformDisplacement if displacement_grad else ElasticDeform
-    y = fn.apply(displacement, args, kwargs, *X_list)
+    if affine_grad:
+        args, kwargs, (affine, rotate, zoom) = _split_affine(args, dict(kwargs))
+        y = ElasticDeformTransform.apply(displacement, affine, rotate, zoom, args, kwargs, bool(displacement_grad),
+                                         *X_list)
+    else:
+        fn = ElasticDeformDisplacement if displacement_grad else ElasticDeform
+        y = fn.apply(displacement, args, kwargs, *X_list)
     if isinstance(X, (list, tuple)):
         return y
     else:
@@ -175,13 +266,56 @@ class ElasticDeformBatchDisplacement(torch.autograd.Function):
         return dx, ddisp, None
 
 
-def deform_grid_batch(X, displacements, *, displacement_grad=False, **kwargs):
+class ElasticDeformBatchTransform(torch.autograd.Function):
+    """ElasticDeformBatch with gradients for the shared affine / rotate / zoom (affine_grad=True) -- summed over the
+    samples -- and, with displacement_grad=True, for the displacements, from one library call."""
+
+    @staticmethod
+    def forward(ctx, x, displacements, affine, rotate, zoom, deform_kwargs, disp_grad):
+        ctx.save_for_backward(x, displacements)
+        ctx.params = (affine, rotate, zoom)
+        ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, (affine, rotate, zoom))}
+        ctx.deform_kwargs = deform_kwargs
+        ctx.disp_grad = disp_grad
+        ctx.x_shape = tuple(x.shape[1:])
+        return _deform_grid_batch_fn(x.detach(), displacements.detach(), **ctx.host, **deform_kwargs)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, displacements = ctx.saved_tensors
+        dy = dy.detach()
+        kw = dict(ctx.deform_kwargs, **ctx.host)
+        dx = ddisp = None
+        grads = [None, None, None]
+        if ctx.needs_input_grad[0]:
+            dx = _deform_grid_gradient_batch_fn(dy, displacements.detach(), X_shape=ctx.x_shape, **kw)
+        want_disp = ctx.disp_grad and ctx.needs_input_grad[1]
+        want_map = any(ctx.needs_input_grad[2:5])
+        if want_disp or want_map:
+            plan, ddisp, dk = _api._transform_gradient_batch(x.detach(), dy, displacements.detach(),
+                                                             **dict(kw, want_disp=want_disp, want_map=want_map))
+            if ddisp is not None:
+                ddisp = ddisp.to(device=displacements.device, dtype=displacements.dtype)
+            if dk is not None:
+                r = _api._affine_result_batch(dk, plan, ctx.host['affine'], ctx.host['rotate'], ctx.host['zoom'],
+                                              False)
+                grads = _param_grads(ctx.needs_input_grad[2:5], ctx.params, r[:3])
+        return (dx, ddisp) + tuple(grads) + (None, None)
+
+
+def deform_grid_batch(X, displacements, *, displacement_grad=False, affine_grad=False, **kwargs):
     """
     Batched :func:`deform_grid` with one control grid per sample: ``X`` is ``(B, ...)``,
     ``displacements`` is ``(B, naxis, n_0, ...)`` (e.g. from :func:`random_displacement` with
     ``batch=B``); keyword arguments as for ``elasticdeform_amd.deform_grid_batch``.  Differentiable
-    with respect to ``X``; with ``displacement_grad=True`` with respect to the displacements as well.
+    with respect to ``X``; with ``displacement_grad=True`` with respect to the displacements as well; with
+    ``affine_grad=True`` with respect to the shared ``affine`` / ``rotate`` / ``zoom`` keywords (tensors allowed).
     """
+    if affine_grad:
+        kwargs = dict(kwargs)
+        affine, rotate, zoom = (kwargs.pop(k, None) for k in _AFFINE_ARGS)
+        return ElasticDeformBatchTransform.apply(X, torch.as_tensor(displacements, device=X.device), affine, rotate,
+                                                 zoom, kwargs, bool(displacement_grad))
     if displacement_grad:
         return ElasticDeformBatchDisplacement.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)
     return ElasticDeformBatch.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)

@@ -336,6 +336,51 @@ int edhip_deform_displacement_gradient_batch_strided(int nbatch,
                                                      char* err, size_t errlen);
 
 /*
+ * Gradient with respect to the displacement AND the inverse map.  Arguments as for
+ * edhip_deform_displacement_gradient, with ddisplacement nullable and
+ *   dinverse_affine      written (NULL: not wanted): float64 device array of shape naxis x (naxis+1), any strides,
+ *                        dK[h, l] = d(sum_i <dY_i, Y_i>) / dK[h, l] for the map the coordinate applies,
+ *                          c_h(o) = sum_l K[h, l] o_l + K[h, naxis] + offset_h + displacement_h(o)
+ *                        (o: the crop-local output index, deform.c:771-781; K = `affine` as passed, the identity
+ *                        when `affine` is NULL), i.e. dK[h, l < naxis] = sum_o g_h(o) o_l, dK[h, naxis] = sum_o g_h(o)
+ *                        with g_h the per-voxel field of the displacement gradient above.
+ * Both NULL: EDHIP_ERR_INVALID.  A wrong shape (EDHIP_ERR_INVALID) or dtype (EDHIP_ERR_DTYPE) of dinverse_affine is
+ * refused before any launch.  When both are requested they come from one pass of the row kernel per input;
+ * ddisplacement is then the same bits as edhip_deform_displacement_gradient's.  dK is summed in fp64 in a fixed
+ * order (bit-reproducible, no atomics); order 0, empty step axes and no output voxels give exact zeros.
+ */
+int edhip_deform_transform_gradient(int ninputs, const edhip_array* inputs,
+                                    const edhip_array* displacement,
+                                    const int64_t* output_offset,
+                                    const edhip_array* doutputs,
+                                    int naxis, const int32_t* axis,
+                                    const int32_t* orders, const int32_t* modes, const double* cvals,
+                                    const double* affine,
+                                    const edhip_array* ddisplacement,
+                                    const edhip_array* dinverse_affine,
+                                    uint32_t flags, void* hip_stream,
+                                    char* err, size_t errlen);
+
+/*
+ * The same for a batch described once (edhip_deform_displacement_gradient_batch_strided): sample b's dK is written
+ * dinverse_affine_batch_stride bytes after sample 0's and is bit-identical to edhip_deform_transform_gradient on
+ * sample b alone.
+ */
+int edhip_deform_transform_gradient_batch_strided(int nbatch,
+                                                  const edhip_array* input0, int64_t input_batch_stride,
+                                                  const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                                  const int64_t* output_offset,
+                                                  const edhip_array* doutput0, int64_t doutput_batch_stride,
+                                                  int naxis, const int32_t* axis,
+                                                  int32_t order, int32_t mode, double cval,
+                                                  const double* affine,
+                                                  const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                                  const edhip_array* dinverse_affine0,
+                                                  int64_t dinverse_affine_batch_stride,
+                                                  uint32_t flags, void* hip_stream,
+                                                  char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """
 bench_dgrad.py -- times deform_grid_displacement_gradient against deform_grid and deform_grid_gradient on the
-same arguments, with device events after warm-up:
+same arguments, with device events after warm-up, and the gradient with respect to the affine part: affine only
+(deform_grid_affine_gradient) and combined (displacement and affine from one library call):
 
     cfg2   256^3 float32, 5^3 grid, sigma 5, order 3, mirror
     cfg3   128^3 float32, same grid
     2d     512^2 float32, 5^2 grid
 
-    python tools/bench_dgrad.py [--iters N] [--out profiles/dgrad_bench.txt]
+    python tools/bench_dgrad.py [--iters N] [--out profiles/dgrad_bench.txt] [--affine]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_dgrad.py --iters 5 --trace
 
 Prints one line per case (mean / min call time in microseconds) and, for the displacement gradient's row
@@ -25,6 +26,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import elasticdeform_amd as ed  # noqa: E402
+import importlib  # noqa: E402
+
+_dg = importlib.import_module("elasticdeform_amd.deform_grid")
 
 CASES = {
     "cfg2": ((256, 256, 256), (5, 5, 5)),
@@ -68,6 +72,8 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--out", default=None)
     p.add_argument("--trace", action="store_true", help="a short run for rocprofv3 (no model lines)")
+    p.add_argument("--affine", action="store_true",
+                   help="displacement-only vs affine-only vs combined (profiles/agrad_bench.txt)")
     args = p.parse_args()
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
@@ -78,12 +84,26 @@ def main():
         D = torch.from_numpy(rng.standard_normal((len(shape),) + ncp) * 5).cuda()
         kw = dict(order=3, mode="mirror")
         res = {"case": name, "shape": list(shape), "grid": list(ncp)}
-        for label, fn in (("deform_grid", lambda: ed.deform_grid(X, D, **kw)),
-                          ("deform_grid_gradient", lambda: ed.deform_grid_gradient(dY, D, **kw)),
-                          ("displacement_gradient", lambda: ed.deform_grid_displacement_gradient(X, dY, D, **kw))):
+        n = len(shape)
+        A = np.concatenate([np.eye(n) + 0.01 * rng.standard_normal((n, n)), 0.3 * rng.standard_normal((n, 1))], 1)
+        akw = dict(kw, affine=A)
+        cases = (("deform_grid", lambda: ed.deform_grid(X, D, **kw)),
+                 ("deform_grid_gradient", lambda: ed.deform_grid_gradient(dY, D, **kw)),
+                 ("displacement_gradient", lambda: ed.deform_grid_displacement_gradient(X, dY, D, **kw)))
+        if args.affine:
+            cases = (("displacement_gradient", lambda: ed.deform_grid_displacement_gradient(X, dY, D, **akw)),
+                     ("affine_gradient", lambda: ed.deform_grid_affine_gradient(X, dY, D, **akw)),
+                     ("combined", lambda: _dg._transform_gradient(X, dY, D, want_disp=True, want_map=True, **akw)))
+        for label, fn in cases:
             mean, best = time_call(fn, args.iters)
             res[label + "_us"] = round(mean, 1)
             res[label + "_min_us"] = round(best, 1)
+        if args.affine:
+            res["affine_vs_displacement"] = round(res["affine_gradient_us"] / res["displacement_gradient_us"], 3)
+            res["combined_vs_displacement"] = round(res["combined_us"] / res["displacement_gradient_us"], 3)
+            lines.append(json.dumps(res))
+            print(lines[-1], flush=True)
+            continue
         res["ratio_vs_deform_grid"] = round(res["displacement_gradient_us"] / res["deform_grid_us"], 2)
         if not args.trace:
             res["model"] = {k: (round(v, 1) if isinstance(v, float) else v) for k, v in model(shape, ncp).items()}
