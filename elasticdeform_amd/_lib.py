@@ -250,28 +250,17 @@ def deform(gradient, in_descs, disp_desc, output_offset, out_descs, axis, orders
     return status
 
 
-def deform_batch(gradient, in_descs, disp_descs, output_offset, out_descs, axis, order, mode, cval,
-                 inverse_affine, flags, stream):
-    """edhip_deform_batch: one volume and one control grid per item, shared parameters."""
-    L = load()
-    n = len(in_descs)
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
-    ins = (EdhipArray * n)(*in_descs)
-    disps = (EdhipArray * n)(*disp_descs)
-    outs = (EdhipArray * n)(*out_descs)
-    off = aff = None
+def _offset_affine(output_offset, inverse_affine):
+    """(int64 pointer to the crop offsets, double pointer to the inverse affine, the arrays behind them) -- None for
+    an argument that is None.  The caller holds on to the third value until its library call has returned."""
+    off = aff = off_arr = aff_arr = None
     if output_offset is not None:
         off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
         off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
     if inverse_affine is not None:
         aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
         aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    buf = ctypes.create_string_buffer(256)
-    status = L.edhip_deform_batch(
-        int(bool(gradient)), n, ins, disps, off, outs, len(axis),
-        axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(order), int(mode), float(cval), aff,
-        int(flags), ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    return off, aff, (off_arr, aff_arr)
 
 
 def deform_batch_strided(gradient, nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset,
@@ -280,13 +269,7 @@ def deform_batch_strided(gradient, nbatch, in_desc, in_bstride, disp_desc, disp_
     distance between consecutive samples of each stacked array."""
     L = load()
     axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
-    off = aff = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
     buf = ctypes.create_string_buffer(256)
     status = L.edhip_deform_batch_strided(
         int(bool(gradient)), int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc),
@@ -296,48 +279,55 @@ def deform_batch_strided(gradient, nbatch, in_desc, in_bstride, disp_desc, disp_
     raise_for_status(status, buf)
 
 
-def deform_displacement_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
-                                 inverse_affine, ddisp_desc, flags, stream, prepared=None):
-    """edhip_deform_displacement_gradient: d(sum_i <dY_i, Y_i>) / d(displacement) into `ddisp_desc`.  `in_descs`
-    are the (prefiltered) inputs the forward read, `dout_descs` the dY arrays; the other arguments as for
-    deform()."""
-    L = load()
+def _ref(desc):
+    return ctypes.byref(desc) if desc is not None else None
+
+
+def _grid_gradient(entry, in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals, inverse_affine,
+                   results, flags, stream, prepared):
+    """The list form of the two gradient entry points: `entry` is the C function, `results` its result descriptors
+    (by reference), which follow the inverse affine in both signatures."""
     n = len(in_descs)
     a = prepared if prepared is not None else DeformArgs(n, axis, orders, modes, cvals, output_offset,
                                                          inverse_affine)
     ins = (EdhipArray * n)(*in_descs)
     outs = (EdhipArray * n)(*dout_descs)
     buf = _buf()
-    status = L.edhip_deform_displacement_gradient(n, ins, ctypes.byref(disp_desc), a.off, outs, a.naxis, a.axis,
-                                                  a.orders, a.modes, a.cvals, a.aff, ctypes.byref(ddisp_desc),
-                                                  int(flags), stream, buf, 256)
+    status = entry(n, ins, ctypes.byref(disp_desc), a.off, outs, a.naxis, a.axis, a.orders, a.modes, a.cvals, a.aff,
+                   *results, int(flags), stream, buf, 256)
     raise_for_status(status, buf)
+
+
+def _grid_gradient_batch_strided(entry, nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, dout_desc,
+                                 dout_bstride, axis, order, mode, cval, inverse_affine, results, flags, stream):
+    """The batch form of the two gradient entry points: `results` are (descriptor by reference, byte stride) pairs,
+    flattened."""
+    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    buf = ctypes.create_string_buffer(256)
+    status = entry(
+        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
+        ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        int(order), int(mode), float(cval), aff, *results, int(flags), ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
+
+
+def deform_displacement_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
+                                 inverse_affine, ddisp_desc, flags, stream, prepared=None):
+    """edhip_deform_displacement_gradient: d(sum_i <dY_i, Y_i>) / d(displacement) into `ddisp_desc`.  `in_descs`
+    are the (prefiltered) inputs the forward read, `dout_descs` the dY arrays; the other arguments as for
+    deform()."""
+    _grid_gradient(load().edhip_deform_displacement_gradient, in_descs, disp_desc, output_offset, dout_descs, axis,
+                   orders, modes, cvals, inverse_affine, (ctypes.byref(ddisp_desc),), flags, stream, prepared)
 
 
 def deform_displacement_gradient_batch_strided(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset,
                                                dout_desc, dout_bstride, axis, order, mode, cval, inverse_affine,
                                                ddisp_desc, ddisp_bstride, flags, stream):
     """edhip_deform_displacement_gradient_batch_strided: sample 0's descriptors plus byte strides."""
-    L = load()
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
-    off = aff = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    buf = ctypes.create_string_buffer(256)
-    status = L.edhip_deform_displacement_gradient_batch_strided(
-        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
-        ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        int(order), int(mode), float(cval), aff, ctypes.byref(ddisp_desc), int(ddisp_bstride), int(flags),
-        ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
-
-
-def _ref(desc):
-    return ctypes.byref(desc) if desc is not None else None
+    _grid_gradient_batch_strided(load().edhip_deform_displacement_gradient_batch_strided, nbatch, in_desc, in_bstride,
+                                 disp_desc, disp_bstride, output_offset, dout_desc, dout_bstride, axis, order, mode,
+                                 cval, inverse_affine, (ctypes.byref(ddisp_desc), int(ddisp_bstride)), flags, stream)
 
 
 def deform_transform_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
@@ -345,39 +335,19 @@ def deform_transform_gradient(in_descs, disp_desc, output_offset, dout_descs, ax
     """edhip_deform_transform_gradient: d(sum_i <dY_i, Y_i>) / d(displacement) into `ddisp_desc` and / or
     d(...) / d(inverse map) into `dinv_desc` (float64, naxis x naxis+1); None = not wanted.  Otherwise as
     deform_displacement_gradient()."""
-    L = load()
-    n = len(in_descs)
-    a = prepared if prepared is not None else DeformArgs(n, axis, orders, modes, cvals, output_offset,
-                                                         inverse_affine)
-    ins = (EdhipArray * n)(*in_descs)
-    outs = (EdhipArray * n)(*dout_descs)
-    buf = _buf()
-    status = L.edhip_deform_transform_gradient(n, ins, ctypes.byref(disp_desc), a.off, outs, a.naxis, a.axis,
-                                               a.orders, a.modes, a.cvals, a.aff, _ref(ddisp_desc), _ref(dinv_desc),
-                                               int(flags), stream, buf, 256)
-    raise_for_status(status, buf)
+    _grid_gradient(load().edhip_deform_transform_gradient, in_descs, disp_desc, output_offset, dout_descs, axis,
+                   orders, modes, cvals, inverse_affine, (_ref(ddisp_desc), _ref(dinv_desc)), flags, stream, prepared)
 
 
 def deform_transform_gradient_batch_strided(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset,
                                             dout_desc, dout_bstride, axis, order, mode, cval, inverse_affine,
                                             ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride, flags, stream):
     """edhip_deform_transform_gradient_batch_strided: sample 0's descriptors plus byte strides (None = not wanted)."""
-    L = load()
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
-    off = aff = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    buf = ctypes.create_string_buffer(256)
-    status = L.edhip_deform_transform_gradient_batch_strided(
-        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
-        ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        int(order), int(mode), float(cval), aff, _ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc),
-        int(dinv_bstride), int(flags), ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    _grid_gradient_batch_strided(load().edhip_deform_transform_gradient_batch_strided, nbatch, in_desc, in_bstride,
+                                 disp_desc, disp_bstride, output_offset, dout_desc, dout_bstride, axis, order, mode,
+                                 cval, inverse_affine,
+                                 (_ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc), int(dinv_bstride)), flags,
+                                 stream)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):
@@ -388,13 +358,7 @@ def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags,
     out_len = numpy.ascontiguousarray(out_len, dtype=numpy.int64)
     naxis = len(in_len)
     p64 = ctypes.POINTER(ctypes.c_int64)
-    off = aff = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(p64)
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
     box = numpy.zeros((naxis, 2), dtype=numpy.int64)
     buf = ctypes.create_string_buffer(256)
     status = L.edhip_source_box(ctypes.byref(disp_desc), in_len.ctypes.data_as(p64),
@@ -414,13 +378,7 @@ def source_window(disp_desc, in_len, out_len, output_offset, inverse_affine, sha
     shape = numpy.ascontiguousarray(shape, dtype=numpy.int64)
     naxis = len(in_len)
     p64 = ctypes.POINTER(ctypes.c_int64)
-    off = aff = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(p64)
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
     buf = _buf()
     status = L.edhip_source_window(ctypes.byref(disp_desc), in_len.ctypes.data_as(p64),
                                    out_len.ctypes.data_as(p64), off, naxis, aff, len(shape),

@@ -23,6 +23,7 @@ output is cval everywhere, the gradient zero -- decided on the host (the C ABI i
 There is no CPU fallback: without a GPU or without the built library the call raises.
 """
 import collections
+import math
 import os
 import sys
 import threading
@@ -560,6 +561,34 @@ def _inverse_perm(p):
     return inv
 
 
+def _relayout_detour(arrays, perms, plan, device, call):
+    """The detour of deform_grid / deform_grid_gradient for `perms` (_relayout_perms): the arrays go to the device
+    and are brought to "step axes first"; `call(arrays, axis)` is the public function itself on them, with the
+    trailing axes as the deformed ones; its results come back in the caller's layout and array family."""
+    with _torch().cuda.device(device):
+        moved = [_to_device(x, device) for x in arrays]
+        moved = [x.permute(p).contiguous() if p is not None else x for x, p in zip(moved, perms)]
+        axis_p = [tuple(range(x.dim() - plan.naxis, x.dim())) if p is not None else tuple(ax)
+                  for x, p, ax in zip(moved, perms, plan.axis)]
+        outs = call(moved, axis_p)
+        outs = [o.permute(_inverse_perm(p)).contiguous() if p is not None else o for o, p in zip(outs, perms)]
+        return [_from_device(o, x) for o, x in zip(outs, arrays)]
+
+
+def _deform_may_decline(gradient, ins, df, outs, plan, flags, stream, fast16, widen):
+    """edhip_deform with `ins` / `outs` in the C ABI's roles (the gradient call: dX / dY).  `fast16`: 16-bit volumes
+    stay in 16 bits (EDHIP_FLAG_FAST), which the library may decline with nothing launched; `widen()` then replaces
+    the contents of the two lists by what the float32 route takes, and the call is repeated without the flag."""
+    def call(extra, may_decline):
+        return _lib.deform(gradient, [_desc(t) for t in ins], _desc(df), plan.output_offset,
+                           [_desc(t) for t in outs], plan.axis, plan.order, plan.mode, plan.cval,
+                           plan.inverse_affine, flags | extra, stream, prepared=_prepared(plan, len(ins)),
+                           may_decline=may_decline)
+    if call(_lib.FLAG_FAST if fast16 else 0, fast16) != 0:
+        widen()
+        call(0, False)
+
+
 def deform_random_grid(X, sigma=25, points=3, order=3, mode='constant', cval=0.0,
                        crop=None, prefilter=True, axis=None,
                        affine=None, rotate=None, zoom=None):
@@ -605,15 +634,8 @@ def deform_grid(X, displacement, order=3, mode='constant', cval=0.0, crop=None, 
     perms = _relayout_perms(plan, Xs)
     if perms is not None:
         # (every argument has passed the reference's checks above, with the caller's own axes)
-        with torch.cuda.device(device):
-            Xp = [_to_device(x, device) for x in Xs]
-            Xp = [x.permute(p).contiguous() if p is not None else x for x, p in zip(Xp, perms)]
-            axis_p = [tuple(range(x.dim() - plan.naxis, x.dim())) if p is not None else tuple(ax)
-                      for x, p, ax in zip(Xp, perms, plan.axis)]
-            outs = deform_grid(Xp, _to_device(displacement, device), order, mode, cval, crop, prefilter, axis_p,
-                               affine, rotate, zoom)
-            outs = [o.permute(_inverse_perm(p)).contiguous() if p is not None else o for o, p in zip(outs, perms)]
-            res = [_from_device(o, x) for o, x in zip(outs, Xs)]
+        res = _relayout_detour(Xs, perms, plan, device, lambda Xp, axis_p: deform_grid(
+            Xp, _to_device(displacement, device), order, mode, cval, crop, prefilter, axis_p, affine, rotate, zoom))
         return res if isinstance(X, list) else res[0]
     with torch.cuda.device(device):
         stream = _stream(device)
@@ -630,7 +652,7 @@ def deform_grid(X, displacement, order=3, mode='constant', cval=0.0, crop=None, 
         # window of it that the cropped output can reach
         df, dflag = _prefilter_displacement(dd, device)
         wins = _crop_windows(plan, Xd, _desc(df), dflag, crop, prefilter, device, stream)
-        Xf, in_descs = [], []
+        Xf = []
         for i, x in enumerate(Xd):
             xf = None
             if direct[i]:
@@ -654,8 +676,7 @@ def deform_grid(X, displacement, order=3, mode='constant', cval=0.0, crop=None, 
                     xf = None           # (outside the tile kernels' envelope: nothing was launched)
             if xf is None:
                 xf = _filter_axes(x, plan.axis[i], int(plan.order[i]), False, device, stream=stream)
-            in_descs.append(_desc(xf))
-            Xf.append(xf)                  # keeps the buffers alive until the launch is enqueued
+            Xf.append(xf)
 
         # every output element is written by the kernel (value or cval), so no zero fill is needed
         # (a 16-bit volume that stayed in 16 bits: K1 reads the float32 coefficients and narrows at its store)
@@ -665,18 +686,14 @@ def deform_grid(X, displacement, order=3, mode='constant', cval=0.0, crop=None, 
         bflag = _box_flag_forward(displacement, df, device, stream)
         if dflag and any(w is not None for w in wins):
             bflag |= _lib.FLAG_GRID_STAYS        # (edhip_source_window has just filtered this very grid on this stream)
-        fast16 = _lib.FLAG_FAST if any(direct) else 0
-        if _lib.deform(False, in_descs, _desc(df), plan.output_offset,
-                       [_desc(o) for o in outs], plan.axis, plan.order, plan.mode, plan.cval,
-                       plan.inverse_affine, _flags | dflag | bflag | fast16 | _route_flags(), stream, prepared=_prepared(plan, len(Xd)),
-                       may_decline=bool(fast16)) != 0:
+
+        def widen():
             # the library declined the 16-bit stores: float32 outputs, narrowed by a cast like the other route
-            outs = [torch.empty(o.shape, dtype=torch.float32, device=device) if d else o for o, d in zip(outs, direct)]
-            wide = [xf if d else w for xf, d, w in zip(Xf, direct, wide)]
-            direct = [False] * len(direct)
-            _lib.deform(False, in_descs, _desc(df), plan.output_offset,
-                        [_desc(o) for o in outs], plan.axis, plan.order, plan.mode, plan.cval,
-                        plan.inverse_affine, _flags | dflag | bflag | _route_flags(), stream, prepared=_prepared(plan, len(Xd)))
+            outs[:] = [torch.empty(o.shape, dtype=torch.float32, device=device) if d else o
+                       for o, d in zip(outs, direct)]
+            wide[:] = [xf if d else w for xf, d, w in zip(Xf, direct, wide)]
+        _deform_may_decline(False, Xf, df, outs, plan, _flags | dflag | bflag | _route_flags(), stream, any(direct),
+                            widen)
         outs = [_narrow(o, xs) if w is not None else o for o, xs, w in zip(outs, Xs_dev, wide)]
         res = [_from_device(o, x) for o, x in zip(outs, Xs)]
         if sig is not None:
@@ -722,16 +739,10 @@ def deform_grid_gradient(dY, displacement, order=3, mode='constant', cval=0.0, c
     device = _device_for(list(dYs) + [displacement])
     perms = _relayout_perms(plan, [_host.ShapeOnly(sh) for sh in X_shape])
     if perms is not None:
-        with torch.cuda.device(device):
-            dYp = [_to_device(dy, device) for dy in dYs]
-            dYp = [dy.permute(p).contiguous() if p is not None else dy for dy, p in zip(dYp, perms)]
-            axis_p = [tuple(range(dy.dim() - plan.naxis, dy.dim())) if p is not None else tuple(ax)
-                      for dy, p, ax in zip(dYp, perms, plan.axis)]
-            shape_p = [tuple(int(sh[a]) for a in p) if p is not None else tuple(sh) for sh, p in zip(X_shape, perms)]
-            dXs = deform_grid_gradient(dYp, _to_device(displacement, device), order, mode, cval, crop, prefilter,
-                                       axis_p, shape_p, affine, rotate, zoom)
-            dXs = [g.permute(_inverse_perm(p)).contiguous() if p is not None else g for g, p in zip(dXs, perms)]
-            res = [_from_device(g, dy) for g, dy in zip(dXs, dYs)]
+        shape_p = [tuple(int(sh[a]) for a in p) if p is not None else tuple(sh) for sh, p in zip(X_shape, perms)]
+        res = _relayout_detour(dYs, perms, plan, device, lambda dYp, axis_p: deform_grid_gradient(
+            dYp, _to_device(displacement, device), order, mode, cval, crop, prefilter, axis_p, shape_p, affine, rotate,
+            zoom))
         return res if isinstance(dY, list) else res[0]
     with torch.cuda.device(device):
         dY_dev = [_to_device(dy, device) for dy in dYs]
@@ -753,17 +764,13 @@ def deform_grid_gradient(dY, displacement, order=3, mode='constant', cval=0.0, c
         if _grad_accumulation == 'float':
             # floating-point atomics in the array's own type (set_gradient_accumulation): the exact kernel's scatter
             gflags = (gflags & ~(_lib.FLAG_FAST | _lib.FLAG_AUTO)) | _lib.FLAG_EXACT
-        if _lib.deform(True, [_desc(x) for x in dXs], _desc(df), plan.output_offset,
-                       [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode, plan.cval,
-                       plan.inverse_affine, gflags | (_lib.FLAG_FAST if any(direct) else 0),
-                       stream, prepared=_prepared(plan, len(dXs)), may_decline=any(direct)) != 0:
+
+        def widen():
             # the library declined the 16-bit loads: widen dY with a cast, like the other route
-            wide = [dy.to(torch.float32) if d else w for dy, d, w in zip(dY_dev, direct, wide)]
-            dYd = [w if w is not None else dy for w, dy in zip(wide, dY_dev)]
-            direct = [False] * len(direct)
-            _lib.deform(True, [_desc(x) for x in dXs], _desc(df), plan.output_offset,
-                        [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode, plan.cval,
-                        plan.inverse_affine, gflags, stream, prepared=_prepared(plan, len(dXs)))
+            wide[:] = [dy.to(torch.float32) if d else w for dy, d, w in zip(dY_dev, direct, wide)]
+            dYd[:] = [w if w is not None else dy for w, dy in zip(wide, dY_dev)]
+            direct[:] = [False] * len(direct)
+        _deform_may_decline(True, dXs, df, dYd, plan, gflags, stream, any(direct), widen)
 
         # gradient of the prefilter: its transpose along each deformed axis (deform_grid.py:276-286).
         # With a crop the scatter only touched a box of dX: the transposed filter runs on that box
@@ -803,15 +810,17 @@ def deform_grid_gradient(dY, displacement, order=3, mode='constant', cval=0.0, c
 def _batch_plan(X, displacements, order, mode, cval, crop, axis, affine, rotate, zoom):
     """Normalise a batched call: X is (B, ...) -- sample b is X[b] -- and displacements is
     (B, naxis, n_0, ...).  `axis` counts the axes of ONE sample (like deform_grid's).  Returns the
-    Plan of a single sample (shared by the whole batch)."""
-    if not _host.is_array(X) or X.ndim < 2:
+    Plan of a single sample (shared by the whole batch).  The gradient call, which has no X, gives its shape
+    (_host.ShapeOnly) after checking its dY itself."""
+    if not isinstance(X, _host.ShapeOnly) and (not _host.is_array(X) or X.ndim < 2):
         raise Exception('X should be an array with a leading batch axis.')
     if not _host.is_array(displacements) or displacements.ndim < 3:
         raise Exception('displacements should be an array of shape (batch, naxis, n_0, ...).')
     assert displacements.shape[0] == X.shape[0], 'One displacement grid per sample is required.'
     assert not isinstance(order, (list, tuple)) and not isinstance(mode, (list, tuple)) and \
         not isinstance(cval, (list, tuple)), 'order, mode and cval are shared by the batch.'
-    return _host.Plan([X[0]], displacements[0], order, mode, cval, crop, axis, affine, rotate, zoom)
+    return _host.Plan([_host.ShapeOnly(X.shape[1:])], displacements[0], order, mode, cval, crop, axis, affine, rotate,
+                      zoom)
 
 
 def deform_grid_batch(X, displacements, order=3, mode='constant', cval=0.0, crop=None,
@@ -868,13 +877,8 @@ def deform_grid_gradient_batch(dY, displacements, order=3, mode='constant', cval
         if crop is not None:
             raise ValueError("X_shape is required if the crop parameter is given.")
         X_shape = tuple(dY.shape[1:])
-    if not _host.is_array(displacements) or displacements.ndim < 3:
-        raise Exception('displacements should be an array of shape (batch, naxis, n_0, ...).')
-    assert displacements.shape[0] == dY.shape[0], 'One displacement grid per sample is required.'
-    assert not isinstance(order, (list, tuple)) and not isinstance(mode, (list, tuple)) and \
-        not isinstance(cval, (list, tuple)), 'order, mode and cval are shared by the batch.'
-    plan = _host.Plan([_host.ShapeOnly(X_shape)], displacements[0], order, mode, cval, crop, axis,
-                      affine, rotate, zoom)
+    plan = _batch_plan(_host.ShapeOnly((dY.shape[0],) + tuple(X_shape)), displacements, order, mode, cval, crop, axis,
+                       affine, rotate, zoom)
     if tuple(plan.output_shapes[0]) != tuple(dY.shape[1:]):
         raise ValueError("X_shape does not match output shape and cropping. "
                          "Expected output shape is %s, but %s given."
@@ -954,6 +958,50 @@ def _result_tensor_dtype(displacement):
     return getattr(torch, dt.name) if isinstance(dt, numpy.dtype) else dt
 
 
+def _transform_gradient_run(plan, Xs, axes, dYs, displacement, grid_axis, dk_shape, prefilter, zoom, want_disp,
+                            want_map, call):
+    """What _transform_gradient and _transform_gradient_batch share, so that a batch sample cannot differ from the
+    single call: the checks, the prefilter of the inputs `Xs` along `axes`, the results' allocation, the control grid
+    raw or filtered here (its grid axes start at `grid_axis`: 1, or 2 behind a batch axis), the ONE library call
+    `call(Xf, dYd, df, dp, dk, flags, stream)` on device tensors (dp / dk: None = not wanted) and the transposed grid
+    filter.  Returns (d displacement in the family of dYs[0] or None, dK of `dk_shape` or None)."""
+    _check_float_volumes(list(Xs) + list(dYs))
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
+    torch = _torch()
+    if _host.degenerate_axis([x.shape for x in Xs], axes):
+        # (a deformed axis of length 1: every voxel is the constant, nothing depends on the grid or the map)
+        dk = None
+        if want_map:
+            dk = torch.zeros(dk_shape, dtype=torch.float64, device=dYs[0].device if torch.is_tensor(dYs[0]) else 'cpu')
+        return (_dgrad_zeros(displacement, dYs[0]) if want_disp else None), dk
+    device = _device_for(list(dYs) + list(Xs) + [displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        Xf = []
+        for i, x in enumerate(Xs):
+            x = _to_device(x, device)
+            if prefilter and plan.order[i] > 1:
+                x = _filter_axes(x, axes[i], int(plan.order[i]), False, device, stream=stream)
+            Xf.append(x)
+        dYd = [_to_device(dy, device) for dy in dYs]
+        dd = _to_device(displacement, device)
+        dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
+        out = None
+        if want_disp:
+            out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacement), device=device)
+        grid_axes = range(grid_axis, dd.ndim)
+        raw = math.prod(dd.shape[grid_axis - 1:]) <= _lib.RAW_DISPLACEMENT_MAX_POINTS     # (points per grid)
+        # a large grid: prefiltered here, the gradient of the prefiltered grid transposed here (fp64 throughout)
+        df = dd if raw else _filter_axes(dd, grid_axes, 3, False, device, stream=stream)
+        dp = out if (raw or out is None) else torch.empty(out.shape, dtype=torch.float64, device=device)
+        call(Xf, dYd, df, dp, dk, _flags | (_lib.FLAG_RAW_DISPLACEMENT if raw else 0), stream)
+        if out is not None and not raw:
+            dp = _filter_axes(dp, grid_axes, 3, True, device, overwrite=True, stream=stream)
+            out.copy_(dp)
+        return (_from_device(out, dYs[0]) if out is not None else None), dk
+
+
 def _transform_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
                         axis=None, affine=None, rotate=None, zoom=None, want_disp=True, want_map=False):
     """One library call for the gradients with respect to the displacement (`want_disp`) and to the inverse map
@@ -966,47 +1014,17 @@ def _transform_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0,
                                                                         for dy in dYs]:
         raise ValueError("dY does not match the output shape of deform_grid. Expected output shape is %s, "
                          "but %s given." % (str(plan.output_shapes), str([tuple(dy.shape) for dy in dYs])))
-    _check_float_volumes(list(Xs) + list(dYs))
-    if want_map and zoom is not None and float(zoom) == 0:
-        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
-    torch = _torch()
-    n = plan.naxis
-    if _host.degenerate_axis([x.shape for x in Xs], plan.axis):
-        # (a deformed axis of length 1: every voxel is the constant, nothing depends on the grid or the map)
-        dk = None
-        if want_map:
-            dk = torch.zeros((n, n + 1), dtype=torch.float64,
-                             device=dYs[0].device if torch.is_tensor(dYs[0]) else 'cpu')
-        return plan, dYs, (_dgrad_zeros(displacement, dYs[0]) if want_disp else None), dk
-    device = _device_for(list(dYs) + list(Xs) + [displacement])
-    with torch.cuda.device(device):
-        stream = _stream(device)
-        Xf = []
-        for i, x in enumerate(Xs):
-            x = _to_device(x, device)
-            if prefilter and plan.order[i] > 1:
-                x = _filter_axes(x, plan.axis[i], int(plan.order[i]), False, device, stream=stream)
-            Xf.append(x)
-        dYd = [_to_device(dy, device) for dy in dYs]
-        dd = _to_device(displacement, device)
-        dk = torch.empty((n, n + 1), dtype=torch.float64, device=device) if want_map else None
-        out = None
-        if want_disp:
-            out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacement), device=device)
-        raw = dd.numel() <= _lib.RAW_DISPLACEMENT_MAX_POINTS
-        # a large grid: prefiltered here, the gradient of the prefiltered grid transposed here (fp64 throughout)
-        df = dd if raw else _filter_axes(dd, range(1, dd.ndim), 3, False, device, stream=stream)
-        dp = out if (raw or out is None) else torch.empty(out.shape, dtype=torch.float64, device=device)
+
+    def call(Xf, dYd, df, dp, dk, flags, stream):
         _lib.deform_transform_gradient([_desc(x) for x in Xf], _desc(df), plan.output_offset,
                                        [_desc(dy) for dy in dYd], plan.axis, plan.order, plan.mode, plan.cval,
                                        plan.inverse_affine, _desc(dp) if dp is not None else None,
-                                       _desc(dk) if dk is not None else None,
-                                       _flags | (_lib.FLAG_RAW_DISPLACEMENT if raw else 0), stream,
+                                       _desc(dk) if dk is not None else None, flags, stream,
                                        prepared=_prepared(plan, len(Xf)))
-        if out is not None and not raw:
-            dp = _filter_axes(dp, range(1, dp.ndim), 3, True, device, overwrite=True, stream=stream)
-            out.copy_(dp)
-        return plan, dYs, (_from_device(out, dYs[0]) if out is not None else None), dk
+    n = plan.naxis
+    ddisp, dk = _transform_gradient_run(plan, Xs, plan.axis, dYs, displacement, 1, (n, n + 1), prefilter, zoom,
+                                        want_disp, want_map, call)
+    return plan, dYs, ddisp, dk
 
 
 def deform_grid_displacement_gradient(X, dY, displacement, order=3, mode='constant', cval=0.0, crop=None,
@@ -1031,47 +1049,21 @@ def _transform_gradient_batch(X, dY, displacements, order=3, mode='constant', cv
         raise ValueError("dY does not match the output shape of deform_grid_batch. Expected output shape is %s, "
                          "but %s given." % (str((int(X.shape[0]),) + tuple(plan.output_shapes[0])),
                                             str(tuple(dY.shape) if _host.is_array(dY) else dY)))
-    _check_float_volumes([X, dY])
-    if want_map and zoom is not None and float(zoom) == 0:
-        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
-    torch = _torch()
-    n = plan.naxis
     B = int(X.shape[0])
-    if _host.degenerate_axis([X.shape[1:]], plan.axis):
-        dk = None
-        if want_map:
-            dk = torch.zeros((B, n, n + 1), dtype=torch.float64, device=dY.device if torch.is_tensor(dY) else 'cpu')
-        return plan, (_dgrad_zeros(displacements, dY) if want_disp else None), dk
-    device = _device_for([dY, X, displacements])
-    with torch.cuda.device(device):
-        stream = _stream(device)
-        Xd = _to_device(X, device)
-        o = int(plan.order[0])
-        ax = plan.axis[0]
-        if prefilter and o > 1:
-            Xd = _filter_axes(Xd, [a + 1 for a in ax], o, False, device, stream=stream)
-        dYd = _to_device(dY, device)
-        dd = _to_device(displacements, device)
-        out = None
-        if want_disp:
-            out = torch.empty(tuple(int(v) for v in dd.shape), dtype=_result_tensor_dtype(displacements), device=device)
-        dk = torch.empty((B, n, n + 1), dtype=torch.float64, device=device) if want_map else None
-        per_sample = int(numpy.prod([int(v) for v in dd.shape[1:]]))
-        raw = per_sample <= _lib.RAW_DISPLACEMENT_MAX_POINTS
-        (xd, xs), (yd, ys) = _desc_sample0(Xd), _desc_sample0(dYd)
-        df = dd if raw else _filter_axes(dd, range(2, dd.ndim), 3, False, device, stream=stream)
-        dp = out if (raw or out is None) else torch.empty(out.shape, dtype=torch.float64, device=device)
-        (gd, gs) = _desc_sample0(df)
+    ax = plan.axis[0]
+
+    def call(Xf, dYd, df, dp, dk, flags, stream):
+        (xd, xs), (yd, ys), (gd, gs) = _desc_sample0(Xf[0]), _desc_sample0(dYd[0]), _desc_sample0(df)
         (pd, ps) = _desc_sample0(dp) if dp is not None else (None, 0)
         (kd, ks) = _desc_sample0(dk) if dk is not None else (None, 0)
-        _lib.deform_transform_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax, o,
-                                                     int(plan.mode[0]), float(plan.cval[0]), plan.inverse_affine,
-                                                     pd, ps, kd, ks,
-                                                     _flags | (_lib.FLAG_RAW_DISPLACEMENT if raw else 0), stream)
-        if out is not None and not raw:
-            dp = _filter_axes(dp, range(2, dp.ndim), 3, True, device, overwrite=True, stream=stream)
-            out.copy_(dp)
-        return plan, (_from_device(out, dY) if out is not None else None), dk
+        _lib.deform_transform_gradient_batch_strided(B, xd, xs, gd, gs, plan.output_offset, yd, ys, ax,
+                                                     int(plan.order[0]), int(plan.mode[0]), float(plan.cval[0]),
+                                                     plan.inverse_affine, pd, ps, kd, ks, flags, stream)
+    n = plan.naxis
+    # (the batch axis is just another outer axis of the stacked arrays: the deformed axes and the grid's move up by one)
+    ddisp, dk = _transform_gradient_run(plan, [X], [[a + 1 for a in ax]], [dY], displacements, 2, (B, n, n + 1),
+                                        prefilter, zoom, want_disp, want_map, call)
+    return plan, ddisp, dk
 
 
 def deform_grid_displacement_gradient_batch(X, dY, displacements, order=3, mode='constant', cval=0.0, crop=None,

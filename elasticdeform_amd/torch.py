@@ -19,8 +19,7 @@ from . import deform_grid as _deform_grid_fn
 from . import deform_grid_gradient as _deform_grid_gradient_fn
 from . import deform_grid_batch as _deform_grid_batch_fn
 from . import deform_grid_gradient_batch as _deform_grid_gradient_batch_fn
-from . import deform_grid_displacement_gradient as _dgrad_fn
-from . import deform_grid_displacement_gradient_batch as _dgrad_batch_fn
+from . import _host
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)
@@ -48,34 +47,6 @@ class ElasticDeform(torch.autograd.Function):
         return (None, None, None) + tuple(dxs)
 
 
-class ElasticDeformDisplacement(torch.autograd.Function):
-    """ElasticDeform with a gradient for the displacement as well (displacement_grad=True): the forward keeps X."""
-
-    @staticmethod
-    def forward(ctx, displacement, deform_args, deform_kwargs, *xs):
-        ctx.save_for_backward(displacement, *xs)
-        ctx.deform_args = deform_args
-        ctx.deform_kwargs = deform_kwargs
-        ctx.x_shapes = [tuple(x.shape) for x in xs]
-        ys = _deform_grid_fn([x.detach() for x in xs], displacement.detach(), *deform_args, **deform_kwargs)
-        return tuple(ys)
-
-    @staticmethod
-    def backward(ctx, *dys):
-        displacement, *xs = ctx.saved_tensors
-        dys = [dy.detach() for dy in dys]
-        dxs = [None] * len(xs)
-        if any(ctx.needs_input_grad[3:]):
-            dxs = _deform_grid_gradient_fn(dys, displacement.detach(), *ctx.deform_args, X_shape=ctx.x_shapes,
-                                           **ctx.deform_kwargs)
-        ddisp = None
-        if ctx.needs_input_grad[0]:
-            ddisp = _dgrad_fn([x.detach() for x in xs], dys, displacement.detach(), *ctx.deform_args,
-                              **ctx.deform_kwargs)
-            ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
-        return (ddisp, None, None) + tuple(dxs)
-
-
 _AFFINE_ARGS = ('affine', 'rotate', 'zoom')
 _AFFINE_POS = 6            # deform_grid(X, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom)
 
@@ -99,45 +70,62 @@ def _param_grads(needs, params, grads):
     return out
 
 
-class ElasticDeformTransform(torch.autograd.Function):
-    """ElasticDeform with gradients for affine / rotate / zoom (affine_grad=True) and, with displacement_grad=True,
-    for the displacement: both from one library call (deform_grid.py _transform_gradient)."""
+def _extended_forward(ctx, displacement, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, xs):
+    """what both extended Functions keep for backward: X as well as the displacement, and affine / rotate / zoom both
+    as given (they receive the gradients) and as host values (the keywords of every library call)"""
+    ctx.save_for_backward(displacement, *xs)
+    ctx.params = (affine, rotate, zoom)
+    ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, ctx.params) if v is not None}
+    ctx.deform_args = deform_args
+    ctx.deform_kwargs = deform_kwargs
+    ctx.disp_grad = disp_grad
+
+
+def _extended_backward(ctx, batch, dys):
+    """backward of both extended Functions (inputs: displacement, affine, rotate, zoom, three non-tensors, X...):
+    dX from deform_grid_gradient(_batch) when an X needs it; the displacement's and the parameters' gradients from ONE
+    library call (deform_grid.py _transform_gradient(_batch)) when either is needed."""
+    displacement, *xs = (t.detach() for t in ctx.saved_tensors)
+    dys = [dy.detach() for dy in dys]
+    x, dy = (xs[0], dys[0]) if batch else (xs, dys)
+    kw = dict(ctx.deform_kwargs, **ctx.host)
+    dxs = [None] * len(xs)
+    if any(ctx.needs_input_grad[7:]):
+        gradient = _deform_grid_gradient_batch_fn if batch else _deform_grid_gradient_fn
+        dxs = gradient(dy, displacement, *ctx.deform_args, X_shape=ctx.x_shape, **kw)
+        dxs = [dxs] if batch else dxs
+    want_disp = ctx.disp_grad and ctx.needs_input_grad[0]
+    want_map = any(ctx.needs_input_grad[1:4])
+    ddisp = None
+    grads = [None, None, None]
+    if want_disp or want_map:
+        transform = _api._transform_gradient_batch if batch else _api._transform_gradient
+        plan, *_, ddisp, dk = transform(x, dy, displacement, *ctx.deform_args,
+                                        **dict(kw, want_disp=want_disp, want_map=want_map))
+        if ddisp is not None:
+            ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+        if dk is not None:
+            result = _api._affine_result_batch if batch else _api._affine_result
+            r = result(dk, plan, ctx.host.get('affine'), ctx.host.get('rotate'), ctx.host.get('zoom'), False)
+            grads = _param_grads(ctx.needs_input_grad[1:4], ctx.params, r[:3])
+    return (ddisp,) + tuple(grads) + (None, None, None) + tuple(dxs)
+
+
+class ElasticDeformExtended(torch.autograd.Function):
+    """ElasticDeform with a gradient for the displacement (displacement_grad=True) and / or for affine / rotate / zoom
+    (affine_grad=True, where they arrive as inputs of their own instead of inside the arguments): the forward keeps X."""
 
     @staticmethod
     def forward(ctx, displacement, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, *xs):
-        ctx.save_for_backward(displacement, *xs)
-        ctx.params = (affine, rotate, zoom)
-        ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, (affine, rotate, zoom))}
-        ctx.deform_args = deform_args
-        ctx.deform_kwargs = deform_kwargs
-        ctx.disp_grad = disp_grad
-        ctx.x_shapes = [tuple(x.shape) for x in xs]
+        _extended_forward(ctx, displacement, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, xs)
+        ctx.x_shape = [tuple(x.shape) for x in xs]
         ys = _deform_grid_fn([x.detach() for x in xs], displacement.detach(), *deform_args, **ctx.host,
                              **deform_kwargs)
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
-        displacement, *xs = ctx.saved_tensors
-        dys = [dy.detach() for dy in dys]
-        kw = dict(ctx.deform_kwargs, **ctx.host)
-        dxs = [None] * len(xs)
-        if any(ctx.needs_input_grad[7:]):
-            dxs = _deform_grid_gradient_fn(dys, displacement.detach(), *ctx.deform_args, X_shape=ctx.x_shapes, **kw)
-        want_disp = ctx.disp_grad and ctx.needs_input_grad[0]
-        want_map = any(ctx.needs_input_grad[1:4])
-        ddisp = None
-        grads = [None, None, None]
-        if want_disp or want_map:
-            plan, _, ddisp, dk = _api._transform_gradient([x.detach() for x in xs], dys, displacement.detach(),
-                                                          *ctx.deform_args, **dict(kw, want_disp=want_disp,
-                                                                                   want_map=want_map))
-            if ddisp is not None:
-                ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
-            if dk is not None:
-                r = _api._affine_result(dk, plan, ctx.host['affine'], ctx.host['rotate'], ctx.host['zoom'], False)
-                grads = _param_grads(ctx.needs_input_grad[1:4], ctx.params, r[:3])
-        return (ddisp,) + tuple(grads) + (None, None, None) + tuple(dxs)
+        return _extended_backward(ctx, False, dys)
 
 
 def _split_affine(args, kwargs):
@@ -175,11 +163,13 @@ def deform_grid(X, displacement, *args, displacement_grad=False, affine_grad=Fal
     displacement = torch.as_tensor(displacement)
     if affine_grad:
         args, kwargs, (affine, rotate, zoom) = _split_affine(args, dict(kwargs))
-        y = ElasticDeformTransform.apply(displacement, affine, rotate, zoom, args, kwargs, bool(displacement_grad),
-                                         *X_list)
+        y = ElasticDeformExtended.apply(displacement, affine, rotate, zoom, args, kwargs, bool(displacement_grad),
+                                        *X_list)
+    elif displacement_grad:
+        # (affine / rotate / zoom stay inside the arguments, as values)
+        y = ElasticDeformExtended.apply(displacement, None, None, None, args, kwargs, True, *X_list)
     else:
-        fn = ElasticDeformDisplacement if displacement_grad else ElasticDeform
-        y = fn.apply(displacement, args, kwargs, *X_list)
+        y = ElasticDeform.apply(displacement, args, kwargs, *X_list)
     if isinstance(X, (list, tuple)):
         return y
     else:
@@ -204,6 +194,13 @@ def random_displacement(naxis, points=3, sigma=25, batch=None, device=None, dtyp
     return torch.randn(shape, device=device, dtype=dtype, generator=generator) * sigma
 
 
+def _random_grid_hint(sigma, points, deform_shape):
+    """deform_grid.py's hint for a grid drawn here (a strong field by construction -> the z-walk route)"""
+    if not isinstance(points, (list, tuple)):
+        points = [points] * len(deform_shape)
+    return _api._random_grid_hint(sigma, points, deform_shape)
+
+
 def deform_random_grid(X, sigma=25, points=3, order=3, mode='constant', cval=0.0, crop=None,
                        prefilter=True, axis=None, affine=None, rotate=None, zoom=None,
                        generator=None):
@@ -213,15 +210,11 @@ def deform_random_grid(X, sigma=25, points=3, order=3, mode='constant', cval=0.0
     (:func:`random_displacement`) and the result stays there, with the autograd contract of
     :func:`deform_grid`.  ``generator``: an optional ``torch.Generator`` of that device.
     """
-    from . import _host
     Xs = list(X) if isinstance(X, (list, tuple)) else [X]
     _, deform_shape = _host.normalize_axis_list(axis, Xs)
     displacement = random_displacement(len(deform_shape), points, sigma, device=Xs[0].device,
                                        generator=generator)
-    import importlib
-    _dgm = importlib.import_module("elasticdeform_amd.deform_grid")
-    pts = points if isinstance(points, (list, tuple)) else [points] * len(deform_shape)
-    with _dgm._random_grid_hint(sigma, pts, deform_shape):       # (a strong field by construction -> the z-walk route)
+    with _random_grid_hint(sigma, points, deform_shape):
         return deform_grid(X, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom)
 
 
@@ -243,64 +236,19 @@ class ElasticDeformBatch(torch.autograd.Function):
         return dx, None, None
 
 
-class ElasticDeformBatchDisplacement(torch.autograd.Function):
-    """ElasticDeformBatch with a gradient for the displacements as well (displacement_grad=True)."""
+class ElasticDeformBatchExtended(torch.autograd.Function):
+    """ElasticDeformBatch with a gradient for the displacements (displacement_grad=True) and / or for the shared
+    affine / rotate / zoom (affine_grad=True) -- summed over the samples; same inputs as ElasticDeformExtended."""
 
     @staticmethod
-    def forward(ctx, x, displacements, deform_kwargs):
-        ctx.save_for_backward(x, displacements)
-        ctx.deform_kwargs = deform_kwargs
-        ctx.x_shape = tuple(x.shape[1:])
-        return _deform_grid_batch_fn(x.detach(), displacements.detach(), **deform_kwargs)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, displacements = ctx.saved_tensors
-        dy = dy.detach()
-        dx = ddisp = None
-        if ctx.needs_input_grad[0]:
-            dx = _deform_grid_gradient_batch_fn(dy, displacements.detach(), X_shape=ctx.x_shape, **ctx.deform_kwargs)
-        if ctx.needs_input_grad[1]:
-            ddisp = _dgrad_batch_fn(x.detach(), dy, displacements.detach(), **ctx.deform_kwargs)
-            ddisp = ddisp.to(device=displacements.device, dtype=displacements.dtype)
-        return dx, ddisp, None
-
-
-class ElasticDeformBatchTransform(torch.autograd.Function):
-    """ElasticDeformBatch with gradients for the shared affine / rotate / zoom (affine_grad=True) -- summed over the
-    samples -- and, with displacement_grad=True, for the displacements, from one library call."""
-
-    @staticmethod
-    def forward(ctx, x, displacements, affine, rotate, zoom, deform_kwargs, disp_grad):
-        ctx.save_for_backward(x, displacements)
-        ctx.params = (affine, rotate, zoom)
-        ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, (affine, rotate, zoom))}
-        ctx.deform_kwargs = deform_kwargs
-        ctx.disp_grad = disp_grad
+    def forward(ctx, displacements, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, x):
+        _extended_forward(ctx, displacements, affine, rotate, zoom, deform_args, deform_kwargs, disp_grad, (x,))
         ctx.x_shape = tuple(x.shape[1:])
         return _deform_grid_batch_fn(x.detach(), displacements.detach(), **ctx.host, **deform_kwargs)
 
     @staticmethod
     def backward(ctx, dy):
-        x, displacements = ctx.saved_tensors
-        dy = dy.detach()
-        kw = dict(ctx.deform_kwargs, **ctx.host)
-        dx = ddisp = None
-        grads = [None, None, None]
-        if ctx.needs_input_grad[0]:
-            dx = _deform_grid_gradient_batch_fn(dy, displacements.detach(), X_shape=ctx.x_shape, **kw)
-        want_disp = ctx.disp_grad and ctx.needs_input_grad[1]
-        want_map = any(ctx.needs_input_grad[2:5])
-        if want_disp or want_map:
-            plan, ddisp, dk = _api._transform_gradient_batch(x.detach(), dy, displacements.detach(),
-                                                             **dict(kw, want_disp=want_disp, want_map=want_map))
-            if ddisp is not None:
-                ddisp = ddisp.to(device=displacements.device, dtype=displacements.dtype)
-            if dk is not None:
-                r = _api._affine_result_batch(dk, plan, ctx.host['affine'], ctx.host['rotate'], ctx.host['zoom'],
-                                              False)
-                grads = _param_grads(ctx.needs_input_grad[2:5], ctx.params, r[:3])
-        return (dx, ddisp) + tuple(grads) + (None, None)
+        return _extended_backward(ctx, True, (dy,))
 
 
 def deform_grid_batch(X, displacements, *, displacement_grad=False, affine_grad=False, **kwargs):
@@ -311,26 +259,23 @@ def deform_grid_batch(X, displacements, *, displacement_grad=False, affine_grad=
     with respect to ``X``; with ``displacement_grad=True`` with respect to the displacements as well; with
     ``affine_grad=True`` with respect to the shared ``affine`` / ``rotate`` / ``zoom`` keywords (tensors allowed).
     """
+    displacements = torch.as_tensor(displacements, device=X.device)
     if affine_grad:
         kwargs = dict(kwargs)
         affine, rotate, zoom = (kwargs.pop(k, None) for k in _AFFINE_ARGS)
-        return ElasticDeformBatchTransform.apply(X, torch.as_tensor(displacements, device=X.device), affine, rotate,
-                                                 zoom, kwargs, bool(displacement_grad))
+        return ElasticDeformBatchExtended.apply(displacements, affine, rotate, zoom, (), kwargs,
+                                                bool(displacement_grad), X)
     if displacement_grad:
-        return ElasticDeformBatchDisplacement.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)
-    return ElasticDeformBatch.apply(X, torch.as_tensor(displacements, device=X.device), kwargs)
+        return ElasticDeformBatchExtended.apply(displacements, None, None, None, (), kwargs, True, X)
+    return ElasticDeformBatch.apply(X, displacements, kwargs)
 
 
 def deform_random_grid_batch(X, sigma=25, points=3, axis=None, generator=None, **kwargs):
     """Per-sample random deformation of a batch ``X`` of shape ``(B, ...)``: draws ``B`` grids on
     the device and applies one to each sample (the augmentation step of a data loader, without a
     host round trip).  ``axis`` counts the axes of one sample."""
-    from . import _host
     _, deform_shape = _host.normalize_axis_list(axis, [X[0]])
     disp = random_displacement(len(deform_shape), points, sigma, batch=X.shape[0], device=X.device,
                                generator=generator)
-    import importlib
-    _dgm = importlib.import_module("elasticdeform_amd.deform_grid")
-    pts = points if isinstance(points, (list, tuple)) else [points] * len(deform_shape)
-    with _dgm._random_grid_hint(sigma, pts, deform_shape):
+    with _random_grid_hint(sigma, points, deform_shape):
         return deform_grid_batch(X, disp, axis=axis, **kwargs)
