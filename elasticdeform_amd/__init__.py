@@ -16,13 +16,16 @@ batch of samples with one control grid each.
 ``deform_grid_displacement_gradient`` / ``deform_grid_displacement_gradient_batch`` (no counterpart in the
 reference either) differentiate with respect to the control-point displacement,
 ``deform_grid_affine_gradient`` / ``deform_grid_affine_gradient_batch`` with respect to affine, rotate and zoom.
+``deform_grid_coordinates`` / ``deform_points`` (and their ``_batch`` forms) map positions through the deformation:
+the coordinate map of ``deform_grid`` at real positions with its Jacobian, and where source points land in the output.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
                           set_reduced_precision, set_crop_identity, set_gradient_accumulation,
                           set_field_strength, deform_grid_displacement_gradient,
                           deform_grid_displacement_gradient_batch, deform_grid_affine_gradient,
-                          deform_grid_affine_gradient_batch, AffineGradient)
+                          deform_grid_affine_gradient_batch, AffineGradient, deform_grid_coordinates,
+                          deform_points, deform_grid_coordinates_batch, deform_points_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

@@ -54,7 +54,7 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_release_scratch', 'edhip_profile_dominant',
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
-           'edhip_deform_transform_gradient_batch_strided')
+           'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points')
 
 
 class EdhipArray(ctypes.Structure):
@@ -169,6 +169,13 @@ def load():
             ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_points.restype = ctypes.c_int
+        L.edhip_deform_points.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -348,6 +355,28 @@ def deform_transform_gradient_batch_strided(nbatch, in_desc, in_bstride, disp_de
                                  cval, inverse_affine,
                                  (_ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc), int(dinv_bstride)), flags,
                                  stream)
+
+
+def deform_points(inverse, nbatch, pts_desc, pts_bstride, disp_desc, disp_bstride, in_len, output_offset,
+                  inverse_affine, forward_linear, res_desc, res_bstride, jac_desc, jac_bstride, status_desc,
+                  status_bstride, max_iter, tol, flags, stream):
+    """edhip_deform_points: the coordinate map r(q) at the points (inverse false; `jac_desc`: also its Jacobian) or
+    the q with r(q) = point (inverse true; `status_desc`: 1 where solved).  Sample 0's descriptors plus byte strides;
+    `disp_desc` is the PREFILTERED control grid; None = not wanted / not given."""
+    L = load()
+    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    lin = lin_arr = None
+    if forward_linear is not None:
+        lin_arr = numpy.ascontiguousarray(forward_linear, dtype=numpy.float64)
+        lin = lin_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    buf = _buf()
+    status = L.edhip_deform_points(
+        int(bool(inverse)), int(nbatch), ctypes.byref(pts_desc), int(pts_bstride), ctypes.byref(disp_desc),
+        int(disp_bstride), in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, lin,
+        ctypes.byref(res_desc), int(res_bstride), _ref(jac_desc), int(jac_bstride), _ref(status_desc),
+        int(status_bstride), int(max_iter), float(tol), int(flags), ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):

@@ -1,0 +1,554 @@
+// deform_points.hip -- the coordinate map of the deformation at arbitrary real positions, and its inverse.
+//
+// For a real, crop-local output position q (n deformed axes; P the prefiltered control grid, K the inverse map the
+// image kernels apply, the identity without affine / rotate / zoom):
+//   cp_k   = (ncp_k - 1) (q_k + off_k) / (I_k - 1)
+//   d_h(q) = sum_{l in {0..3}^n} P[h, m(floor(cp) - 1 + l)] prod_k w_k[l_k]      (w: cubic weights, m: mirror tap map)
+//   r_h(q) = sum_l K[h, l] q_l + K[h, n] + off_h + d_h(q)
+//   J[h,l] = K[h, l] + (ncp_l - 1) / (I_l - 1) sum P[h, .] w'_l[.] prod_{k != l} w_k[.]
+// At integer q, r is the coordinate of the image kernels before their boundary map (ed_exact_coord.h).  No boundary
+// mode is applied: the mirror tap map extends the spline to every real q, r is C2 and J continuous.
+//
+//   points_kernel<N, LDS, false>   r(q), optionally J, for every point
+//   points_kernel<N, LDS, true>    q with r(q) = p by a damped Newton iteration from q0 = M (p - off - K[:, n]):
+//                                  step from the analytic J (adjugate for n <= 3, Gaussian elimination with partial
+//                                  pivoting beyond), halved while the residual's max-norm does not decrease (at most
+//                                  10 halvings), stop at |r(q) - p|_inf <= tol.  max_iter steps, an exhausted
+//                                  backtrack, a singular J or a non-finite input: NaN in every component, status 0.
+//
+// One thread per point (grid-stride beyond the launch's range), blockIdx.y = sample, fp64 throughout; float32 points
+// are widened at the load and float32 results rounded once at the store.  The control grid (any dtype, any strides)
+// is staged in LDS as doubles when it has at most kPointsLdsValues values (stage_grid_lds) and read from global
+// memory beyond.  No atomics and no cross-lane operations: a point's result depends on that point and the call's
+// arguments only, so a sample of a batch, a slice of the points and a repeated call give the same bits.  The 1- to
+// 3-axis instances keep everything in registers (the tap sum unrolled, but for the outermost of three tap loops);
+// 4 to 7 axes run an odometer over the 4^n taps.
+#include <cmath>
+#include <cstring>
+
+#include "ed_device.h"
+#include "ed_exact_coord.h"
+#include "ed_params.h"
+
+namespace ed {
+
+namespace {
+
+constexpr int kPointsThreads = 256;
+constexpr int kPointsMaxBlocks = 2048;        // per sample; points beyond blocks * threads: grid-stride loop
+constexpr int kPointsMaxHalvings = 10;
+constexpr double kPointsMaxCoordinate = 4e15; // |control coordinate| below 2^52: floor() and the tap index are exact
+
+struct PointsArgs {
+    GridGeom g;                               // g.disp: the prefiltered grid of sample 0; out_len / nvox unused
+    int64_t disp_bstride;
+    const char* pts;                          // (npts, naxis) float32 / float64
+    int pts_f32;
+    int64_t pts_stride[2], pts_bstride;
+    char* res;                                // (npts, naxis) float32 / float64
+    int res_f32;
+    int64_t res_stride[2], res_bstride;
+    char* jac;                                // forward: (npts, naxis, naxis) float64, or nullptr
+    int64_t jac_stride[3], jac_bstride;
+    unsigned char* status;                    // inverse: (npts) uint8, or nullptr
+    int64_t status_stride, status_bstride;
+    int64_t npts;
+    double scale[kMaxAxes];                   // (ncp_k - 1) / (I_k - 1)
+    double minv[kMaxAxes * kMaxAxes];         // inverse: M = (K[:, :n])^-1, row-major (identity without affine)
+    int max_iter;
+    double tol;
+};
+
+constexpr int ipow4(int e) { return e == 0 ? 1 : 4 * ipow4(e - 1); }
+
+// a[t] for a runtime t without indexing a register array dynamically
+template <typename T>
+__device__ __forceinline__ T pick4(const T (&a)[4], int t)
+{
+    T r = a[0];
+    r = t == 1 ? a[1] : r;
+    r = t == 2 ? a[2] : r;
+    r = t == 3 ? a[3] : r;
+    return r;
+}
+
+// the control grid as the evaluator reads it: doubles in LDS (component-major, C order) or the caller's array
+struct LdsGrid {
+    typedef int Off;                          // tap offsets: elements of the LDS copy
+    const double* s;
+    int per;
+    __device__ __forceinline__ double operator()(int h, int off) const { return s[h * per + off]; }
+};
+struct GlobalGrid {
+    typedef int64_t Off;                      // bytes of the caller's array
+    const char* base;
+    int64_t hstride;
+    int dtype;
+    __device__ __forceinline__ double operator()(int h, int64_t off) const
+    {
+        return load_as_double(base + h * hstride + off, dtype);
+    }
+};
+
+// Separable tap sum over grid axes D..N-1 (every loop unrolled but the outermost of three):
+//   v     = sum_t C[t] prod_e w_e
+//   dv[l] = sum_t C[t] dw_l prod_{e != l} w_e        (l >= D)
+template <int N, int D, typename Grid>
+__device__ __forceinline__ void grid_taps(const Grid& grid, int h, typename Grid::Off off,
+                                          const typename Grid::Off (&toff)[N][4],
+                                          const double (&w)[N][4], const double (&dw)[N][4], double& v,
+                                          double (&dv)[N])
+{
+    if constexpr (D == N) {
+        v = grid(h, off);
+    } else {
+        v = 0.0;
+#pragma unroll
+        for (int l = D; l < N; ++l)
+            dv[l] = 0.0;
+        if constexpr (N - D >= 3) {
+            // the outermost tap loop of the 3-axis sum stays rolled: 16 grid reads per turn.  Unrolled too, the
+            // compiler issues all 64 x 3 reads in front of the arithmetic and takes every register there is (256 + 122
+            // accumulation registers, one wave per SIMD).  The turn's weights and offset rotate through scalars: a
+            // select on the loop counter is turned back into an indexed read, which puts the arrays into scratch.
+            double w0 = w[D][0], w1 = w[D][1], w2 = w[D][2], w3 = w[D][3];
+            double d0 = dw[D][0], d1 = dw[D][1], d2 = dw[D][2], d3 = dw[D][3];
+            typename Grid::Off o0 = toff[D][0], o1 = toff[D][1], o2 = toff[D][2], o3 = toff[D][3];
+#pragma unroll 1
+            for (int t = 0; t < 4; ++t) {
+                double sv;
+                double sdv[N];
+                grid_taps<N, D + 1>(grid, h, off + o0, toff, w, dw, sv, sdv);
+                v += w0 * sv;
+                dv[D] += d0 * sv;
+#pragma unroll
+                for (int l = D + 1; l < N; ++l)
+                    dv[l] += w0 * sdv[l];
+                const double wr = w0, dr = d0;
+                const typename Grid::Off orot = o0;
+                w0 = w1, w1 = w2, w2 = w3, w3 = wr;
+                d0 = d1, d1 = d2, d2 = d3, d3 = dr;
+                o0 = o1, o1 = o2, o2 = o3, o3 = orot;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                double sv;
+                double sdv[N];
+                grid_taps<N, D + 1>(grid, h, off + toff[D][t], toff, w, dw, sv, sdv);
+                v += w[D][t] * sv;
+                dv[D] += dw[D][t] * sv;
+#pragma unroll
+                for (int l = D + 1; l < N; ++l)
+                    dv[l] += w[D][t] * sdv[l];
+            }
+        }
+    }
+}
+
+// r(q) and J(q).  tstride[k]: distance between neighbours along grid axis k in the units Grid takes (elements of the
+// LDS copy, bytes of the caller's array).
+template <int N, typename Grid>
+__device__ __forceinline__ void eval_map(const PointsArgs& a, const Grid& grid, const int64_t (&tstride)[N],
+                                         const double (&q)[N], double (&r)[N], double (&J)[N][N])
+{
+    const GridGeom& g = a.g;
+    typename Grid::Off toff[N][4];
+    double w[N][4], dw[N][4];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double cpq = (double)(g.ncp[k] - 1) * (q[k] + (double)g.off[k]) / (double)(g.in_len[k] - 1);
+        // a position that is not finite, or too far out for the tap index to be an exact integer: the taps of
+        // position 0 (inside the grid) with NaN weights, so that the result is NaN and nothing is read out of range
+        const bool sane = fabs(cpq) < kPointsMaxCoordinate;
+        const double cp = sane ? cpq : 0.0;
+        const int64_t start = window_start(cp, 3);
+        spline_weights(cp, 3, w[k]);
+        spline_weight_derivatives(cp, 3, dw[k]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            toff[k][t] = (typename Grid::Off)(mirror_index(start + t, g.ncp[k]) * tstride[k]);
+            w[k][t] = sane ? w[k][t] : NAN;
+            dw[k][t] = sane ? dw[k][t] * a.scale[k] : NAN;
+        }
+    }
+    double d[N];
+    if constexpr (N <= 3) {
+#pragma unroll
+        for (int h = 0; h < N; ++h)
+            grid_taps<N, 0>(grid, h, 0, toff, w, dw, d[h], J[h]);
+    } else {
+        // many axes (performance does not matter there): an odometer over the 4^N taps
+#pragma unroll
+        for (int h = 0; h < N; ++h) {
+            d[h] = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+                J[h][l] = 0.0;
+        }
+        int t[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            t[k] = 0;
+        for (int tap = 0; tap < ipow4(N); ++tap) {
+            typename Grid::Off off = 0;
+            double wv[N], dwv[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                off += pick4(toff[k], t[k]);
+                wv[k] = pick4(w[k], t[k]);
+                dwv[k] = pick4(dw[k], t[k]);
+            }
+            double prod = 1.0;
+            double dprod[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k)
+                prod *= wv[k];
+#pragma unroll
+            for (int l = 0; l < N; ++l) {
+                double p = dwv[l];
+#pragma unroll
+                for (int e = 0; e < N; ++e)
+                    if (e != l)
+                        p *= wv[e];
+                dprod[l] = p;
+            }
+#pragma unroll
+            for (int h = 0; h < N; ++h) {
+                const double c = grid(h, off);
+                d[h] += c * prod;
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    J[h][l] += c * dprod[l];
+            }
+            bool carry = true;
+#pragma unroll
+            for (int k = N - 1; k >= 0; --k) {
+                if (carry) {
+                    t[k] = t[k] < 3 ? t[k] + 1 : 0;
+                    carry = t[k] == 0;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        double cc;
+        if (g.has_affine) {
+            cc = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l) {
+                cc += g.affine[h * (N + 1) + l] * q[l];
+                J[h][l] += g.affine[h * (N + 1) + l];
+            }
+            cc += g.affine[h * (N + 1) + N];
+        } else {
+            cc = q[h];
+            J[h][h] += 1.0;
+        }
+        r[h] = cc + (double)g.off[h] + d[h];
+    }
+}
+
+// s with J s = b; false when J is singular (or not finite)
+template <int N>
+__device__ __forceinline__ bool solve(const double (&J)[N][N], const double (&b)[N], double (&s)[N])
+{
+    if constexpr (N == 1) {
+        s[0] = b[0] / J[0][0];
+        return J[0][0] != 0.0 && isfinite(s[0]);
+    } else if constexpr (N == 2) {
+        const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        s[0] = (J[1][1] * b[0] - J[0][1] * b[1]) / det;
+        s[1] = (J[0][0] * b[1] - J[1][0] * b[0]) / det;
+        return det != 0.0 && isfinite(s[0]) && isfinite(s[1]);
+    } else if constexpr (N == 3) {
+        // adjugate: cofactors of J, expanded along the first row
+        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+        const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+        const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+        const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+        const double c10 = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+        const double c11 = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+        const double c12 = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+        const double c20 = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+        const double c21 = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+        const double c22 = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        s[0] = (c00 * b[0] + c10 * b[1] + c20 * b[2]) / det;
+        s[1] = (c01 * b[0] + c11 * b[1] + c21 * b[2]) / det;
+        s[2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) / det;
+        return det != 0.0 && isfinite(s[0]) && isfinite(s[1]) && isfinite(s[2]);
+    } else {
+        // Gaussian elimination with partial pivoting on the augmented matrix
+        double A[N][N + 1];
+        for (int i = 0; i < N; ++i) {
+            for (int j = 0; j < N; ++j)
+                A[i][j] = J[i][j];
+            A[i][N] = b[i];
+        }
+        for (int c = 0; c < N; ++c) {
+            int piv = c;
+            double best = fabs(A[c][c]);
+            for (int i = c + 1; i < N; ++i) {
+                const double v = fabs(A[i][c]);
+                if (v > best) {
+                    best = v;
+                    piv = i;
+                }
+            }
+            if (!(best > 0.0) || !isfinite(best))
+                return false;
+            if (piv != c) {
+                for (int j = c; j <= N; ++j) {
+                    const double tmp = A[c][j];
+                    A[c][j] = A[piv][j];
+                    A[piv][j] = tmp;
+                }
+            }
+            for (int i = c + 1; i < N; ++i) {
+                const double f = A[i][c] / A[c][c];
+                for (int j = c; j <= N; ++j)
+                    A[i][j] -= f * A[c][j];
+            }
+        }
+        bool ok = true;
+        for (int i = N - 1; i >= 0; --i) {
+            double acc = A[i][N];
+            for (int j = i + 1; j < N; ++j)
+                acc -= A[i][j] * s[j];
+            s[i] = acc / A[i][i];
+            ok = ok && isfinite(s[i]);
+        }
+        return ok;
+    }
+}
+
+template <int N>
+__device__ __forceinline__ double max_norm_diff(const double (&r)[N], const double (&p)[N])
+{
+    double m = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        const double e = fabs(r[h] - p[h]);
+        bad = bad || !(e == e);
+        m = e > m ? e : m;
+    }
+    return bad ? INFINITY : m;
+}
+
+// q with r(q) = p; false: no solution reached (see the head of the file)
+template <int N, typename Grid>
+__device__ __forceinline__ bool invert_map(const PointsArgs& a, const Grid& grid, const int64_t (&tstride)[N],
+                                           const double (&p)[N], double (&q)[N])
+{
+    const GridGeom& g = a.g;
+    double b[N], s[N], trial[N];
+    bool finite = true;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        finite = finite && isfinite(p[h]);
+        b[h] = p[h] - (double)g.off[h] - (g.has_affine ? g.affine[h * (N + 1) + N] : 0.0);
+    }
+    if (!finite)
+        return false;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        if (g.has_affine) {
+            double acc = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+                acc += a.minv[h * N + l] * b[l];
+            trial[h] = acc;
+        } else {
+            trial[h] = b[h];
+        }
+        s[h] = 0.0;
+    }
+    double res = INFINITY, lambda = 1.0;
+    int steps = 0, halvings = 0;
+    bool first = true;
+    // one evaluation per turn: of the start, of a full Newton step, or of a halved one
+    for (;;) {
+        double r[N], J[N][N];
+        eval_map<N>(a, grid, tstride, trial, r, J);
+        const double rt = max_norm_diff<N>(r, p);
+        if (rt < res) {
+            // accepted (the start, or a step that lowers the residual)
+#pragma unroll
+            for (int h = 0; h < N; ++h)
+                q[h] = trial[h];
+            res = rt;
+            if (res <= a.tol)
+                return true;
+            if (steps == a.max_iter)
+                return false;
+            double e[N];
+#pragma unroll
+            for (int h = 0; h < N; ++h)
+                e[h] = r[h] - p[h];
+            if (!solve<N>(J, e, s))
+                return false;
+            ++steps;
+            lambda = 1.0;
+            halvings = 0;
+        } else {
+            if (first || halvings == kPointsMaxHalvings)
+                return false;             // a start that is not finite, or an exhausted backtrack
+            ++halvings;
+            lambda *= 0.5;
+        }
+        first = false;
+#pragma unroll
+        for (int h = 0; h < N; ++h)
+            trial[h] = q[h] - lambda * s[h];
+    }
+}
+
+template <int N, bool LDS, bool INVERSE>
+__global__ __launch_bounds__(kPointsThreads) void points_kernel(PointsArgs a)
+{
+    extern __shared__ double s_grid[];        // LDS: [N][ncp_0]...[ncp_{N-1}]
+    const int64_t b = blockIdx.y;
+    a.g.disp += b * a.disp_bstride;           // this sample's control grid
+    const GridGeom& g = a.g;
+    int64_t tstride[N];
+    int per = 0;
+    if constexpr (LDS) {
+        per = stage_grid_lds<N>(g, s_grid);
+        __syncthreads();
+        int64_t cs = 1;
+#pragma unroll
+        for (int k = N - 1; k >= 0; --k) {
+            tstride[k] = cs;
+            cs *= g.ncp[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            tstride[k] = g.disp_stride[k + 1];
+    }
+    const char* pts = a.pts + b * a.pts_bstride;
+    char* res = a.res + b * a.res_bstride;
+
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.npts;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        double p[N], out[N];
+#pragma unroll
+        for (int h = 0; h < N; ++h) {
+            const char* src = pts + i * a.pts_stride[0] + h * a.pts_stride[1];
+            p[h] = a.pts_f32 ? (double)*(const float*)src : *(const double*)src;
+        }
+        if constexpr (INVERSE) {
+            bool ok;
+            if constexpr (LDS)
+                ok = invert_map<N>(a, LdsGrid{s_grid, per}, tstride, p, out);
+            else
+                ok = invert_map<N>(a, GlobalGrid{g.disp, g.disp_stride[0], g.disp_dtype}, tstride, p, out);
+            if (!ok) {
+#pragma unroll
+                for (int h = 0; h < N; ++h)
+                    out[h] = NAN;
+            }
+            if (a.status)
+                a.status[b * a.status_bstride + i * a.status_stride] = ok ? 1 : 0;
+        } else {
+            double J[N][N];
+            if constexpr (LDS)
+                eval_map<N>(a, LdsGrid{s_grid, per}, tstride, p, out, J);
+            else
+                eval_map<N>(a, GlobalGrid{g.disp, g.disp_stride[0], g.disp_dtype}, tstride, p, out, J);
+            if (a.jac) {
+                char* dst = a.jac + b * a.jac_bstride + i * a.jac_stride[0];
+#pragma unroll
+                for (int h = 0; h < N; ++h)
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                        *(double*)(dst + h * a.jac_stride[1] + l * a.jac_stride[2]) = J[h][l];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < N; ++h) {
+            char* dst = res + i * a.res_stride[0] + h * a.res_stride[1];
+            if (a.res_f32)
+                *(float*)dst = (float)out[h];
+            else
+                *(double*)dst = out[h];
+        }
+    }
+}
+
+template <int N>
+hipError_t launch_points(const PointsArgs& a, bool inverse, int nbatch, size_t lds, hipStream_t stream)
+{
+    const int64_t want = (a.npts + kPointsThreads - 1) / kPointsThreads;
+    const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
+    const dim3 block(kPointsThreads);
+    if (lds) {
+        if (inverse)
+            hipLaunchKernelGGL((points_kernel<N, true, true>), grid, block, lds, stream, a);
+        else
+            hipLaunchKernelGGL((points_kernel<N, true, false>), grid, block, lds, stream, a);
+    } else {
+        if (inverse)
+            hipLaunchKernelGGL((points_kernel<N, false, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((points_kernel<N, false, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_deform_points(const PointsCall& c, hipStream_t stream)
+{
+    const GridGeom& g = c.g;
+    const int n = g.naxis;
+    if (n < 1 || n > kMaxAxes || c.nbatch > 65535)
+        return hipErrorNotSupported;
+    if (c.npts <= 0 || c.nbatch <= 0)
+        return hipSuccess;                    // nothing to launch
+    PointsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g = g;
+    a.disp_bstride = c.disp_bstride;
+    a.pts = c.pts;
+    a.pts_f32 = c.pts_dtype == EDHIP_F32;
+    a.pts_bstride = c.pts_bstride;
+    a.res = c.res;
+    a.res_f32 = c.res_dtype == EDHIP_F32;
+    a.res_bstride = c.res_bstride;
+    for (int k = 0; k < 2; ++k) {
+        a.pts_stride[k] = c.pts_stride[k];
+        a.res_stride[k] = c.res_stride[k];
+    }
+    a.jac = c.inverse ? nullptr : c.jac;
+    for (int k = 0; k < 3; ++k)
+        a.jac_stride[k] = c.jac_stride[k];
+    a.jac_bstride = c.jac_bstride;
+    a.status = c.inverse ? c.status : nullptr;
+    a.status_stride = c.status_stride;
+    a.status_bstride = c.status_bstride;
+    a.npts = c.npts;
+    a.max_iter = c.max_iter;
+    a.tol = c.tol;
+    int64_t values = n;
+    for (int k = 0; k < n; ++k) {
+        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
+        values *= g.ncp[k];
+        for (int l = 0; l < n; ++l)
+            a.minv[k * n + l] = c.forward_linear ? c.forward_linear[k * n + l] : (k == l ? 1.0 : 0.0);
+    }
+    const size_t lds = values <= kPointsLdsValues ? (size_t)values * sizeof(double) : 0;
+    switch (n) {
+    case 1: return launch_points<1>(a, c.inverse, c.nbatch, lds, stream);
+    case 2: return launch_points<2>(a, c.inverse, c.nbatch, lds, stream);
+    case 3: return launch_points<3>(a, c.inverse, c.nbatch, lds, stream);
+    case 4: return launch_points<4>(a, c.inverse, c.nbatch, lds, stream);
+    case 5: return launch_points<5>(a, c.inverse, c.nbatch, lds, stream);
+    case 6: return launch_points<6>(a, c.inverse, c.nbatch, lds, stream);
+    default: return launch_points<7>(a, c.inverse, c.nbatch, lds, stream);
+    }
+}
+
+}  // namespace ed

@@ -182,6 +182,31 @@ bool dgrad_supported(const GridGeom& g);
 size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch, bool dp = true, bool dk = false);
 hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream);
 
+// The coordinate map at arbitrary real positions and its inverse (deform_points.hip): one thread per point,
+// blockIdx.y = sample, fp64; no scratch, no synchronisation.  Sample b's arrays sit b * bstride bytes after sample 0's.
+struct PointsCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len >= 2 on every axis
+    int inverse;                  // 0: r(q) (and J); 1: q with r(q) = p
+    int nbatch;
+    int64_t npts;
+    int64_t disp_bstride;
+    const char* pts;              // (npts, naxis), float32 / float64
+    int pts_dtype;
+    int64_t pts_stride[2], pts_bstride;
+    char* res;                    // (npts, naxis), float32 / float64
+    int res_dtype;
+    int64_t res_stride[2], res_bstride;
+    char* jac;                    // forward: float64 (npts, naxis, naxis); nullptr: not wanted
+    int64_t jac_stride[3], jac_bstride;
+    unsigned char* status;        // inverse: uint8 (npts), 1 = solved; nullptr: not wanted
+    int64_t status_stride, status_bstride;
+    const double* forward_linear; // inverse: host, M = (K[:, :naxis])^-1 row-major; nullptr: the identity
+    int max_iter;
+    double tol;
+};
+constexpr int kPointsLdsValues = 7680;   // control grids up to this many values are staged in LDS (60 KiB of doubles)
+hipError_t launch_deform_points(const PointsCall& c, hipStream_t stream);
+
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;
 

@@ -1275,4 +1275,109 @@ int edhip_deform_displacement_gradient_batch_strided(
                                     err, errlen);
 }
 
+// ---- the coordinate map at real positions and its inverse (deform_points.hip) ---------------------------------
+int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int64_t points_batch_stride,
+                        const edhip_array* displacement0, int64_t displacement_batch_stride, const int64_t* in_len,
+                        const int64_t* output_offset, int naxis, const double* affine, const double* forward_linear,
+                        const edhip_array* result0, int64_t result_batch_stride, const edhip_array* jacobian0,
+                        int64_t jacobian_batch_stride, const edhip_array* status0, int64_t status_batch_stride,
+                        int max_iter, double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || !points0 || !displacement0 || !result0 || !in_len)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > kMaxAxes)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
+                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_points takes the prefiltered control grid");
+    if (points0->ndim != 2 || points0->shape[1] != naxis || points0->shape[0] < 0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "points must have shape (N, naxis)");
+    if (result0->ndim != 2 || result0->shape[0] != points0->shape[0] || result0->shape[1] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "result must have the shape of points");
+    if ((points0->dtype != EDHIP_F32 && points0->dtype != EDHIP_F64) ||
+        (result0->dtype != EDHIP_F32 && result0->dtype != EDHIP_F64))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    const int64_t npts = points0->shape[0];
+    if (jacobian0) {
+        if (inverse)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the jacobian belongs to the forward direction");
+        if (jacobian0->ndim != 3 || jacobian0->shape[0] != npts || jacobian0->shape[1] != naxis ||
+            jacobian0->shape[2] != naxis)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "jacobian must have shape (N, naxis, naxis)");
+        if (jacobian0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "jacobian must be float64");
+    }
+    if (status0) {
+        if (!inverse)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the status belongs to the inverse direction");
+        if (status0->ndim != 1 || status0->shape[0] != npts)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "status must have shape (N)");
+        if (status0->dtype != EDHIP_U8)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "status must be uint8");
+    }
+    if (inverse) {
+        if (max_iter < 1)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "max_iter must be at least 1");
+        if (!(tol > 0.0))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "tol must be positive");
+        if (affine && !forward_linear)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
+    }
+    if (displacement0->ndim != naxis + 1 || displacement0->shape[0] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (!dtype_ok(displacement0->dtype))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    for (int k = 0; k <= naxis; ++k)
+        if (displacement0->shape[k] <= 0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (nbatch > 65535)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_points: too many samples");
+    PointsCall c;
+    memset(&c, 0, sizeof(c));
+    // (no EDHIP_FLAG_RAW_DISPLACEMENT: nothing is launched or reserved; refuses extents below 2)
+    int st = make_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, 0, stream, c.g, err, errlen);
+    if (st != EDHIP_OK)
+        return st;
+    if (nbatch == 0 || npts == 0)
+        return EDHIP_OK;
+    c.inverse = inverse != 0;
+    c.nbatch = nbatch;
+    c.npts = npts;
+    c.disp_bstride = displacement_batch_stride;
+    c.pts = (const char*)points0->data;
+    c.pts_dtype = points0->dtype;
+    c.pts_bstride = points_batch_stride;
+    c.res = (char*)result0->data;
+    c.res_dtype = result0->dtype;
+    c.res_bstride = result_batch_stride;
+    for (int k = 0; k < 2; ++k) {
+        c.pts_stride[k] = points0->stride_bytes[k];
+        c.res_stride[k] = result0->stride_bytes[k];
+    }
+    if (jacobian0) {
+        c.jac = (char*)jacobian0->data;
+        for (int k = 0; k < 3; ++k)
+            c.jac_stride[k] = jacobian0->stride_bytes[k];
+        c.jac_bstride = jacobian_batch_stride;
+    }
+    if (status0) {
+        c.status = (unsigned char*)status0->data;
+        c.status_stride = status0->stride_bytes[0];
+        c.status_bstride = status_batch_stride;
+    }
+    c.forward_linear = affine ? forward_linear : nullptr;
+    c.max_iter = max_iter;
+    c.tol = tol;
+    const hipError_t e = launch_deform_points(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform points launch");
+    return EDHIP_OK;
+}
+
 }  // extern "C"

@@ -1167,3 +1167,173 @@ def deform_grid_affine_gradient_batch(X, dY, displacements, order=3, mode='const
     plan, _, dk = _transform_gradient_batch(X, dY, displacements, order, mode, cval, crop, prefilter, axis, affine,
                                             rotate, zoom, False, True)
     return _affine_result_batch(dk, plan, affine, rotate, zoom, isinstance(dY, numpy.ndarray))
+
+
+# ---- the coordinate map at real positions and its inverse (no counterpart in the reference) ---------------------
+
+_POINT_DTYPES = ('float32', 'float64')
+
+
+def _as_points(points):
+    """positions as a float32 / float64 array of the caller's family; integer arrays are taken as float64"""
+    if not _host.is_array(points):
+        points = numpy.asarray(points)
+    if isinstance(points, numpy.ndarray):
+        if points.dtype.kind in 'iub':
+            return points.astype(numpy.float64)
+        if points.dtype.name not in _POINT_DTYPES:
+            raise RuntimeError('data type not supported')
+        return points
+    torch = _torch()
+    if points.dtype in (torch.float32, torch.float64):
+        return points.detach()
+    if points.is_floating_point() or points.is_complex():
+        raise RuntimeError('data type not supported')
+    return points.detach().to(torch.float64)
+
+
+def _points_fill(like, shape, value, dtype_name):
+    """an array of `shape` in the family and on the device of `like`"""
+    if isinstance(like, numpy.ndarray):
+        return numpy.full(shape, value, dtype=dtype_name)
+    torch = _torch()
+    return torch.full(shape, value, dtype=getattr(torch, dtype_name), device=like.device)
+
+
+def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, jacobian, max_iter, tol,
+                batch):
+    """Both directions of the coordinate map, single call and batch.  Returns (coordinates, jacobian or None,
+    converged or None) with the leading dimensions of `points`.  Every argument check runs before the device is
+    touched: offsets, the inverse map K and the rotate / zoom centre are the image call's own (the same Plan)."""
+    if X_shape is None:
+        raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
+    if inverse:
+        if int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError("max_iter should be a positive integer.")
+        if not float(tol) > 0.0:
+            raise ValueError("tol should be positive.")
+    X_shape = tuple(int(v) for v in X_shape)
+    pts = _as_points(points)
+    if batch:
+        if pts.ndim != 3:
+            raise ValueError("points should have shape (batch, N, naxis).")
+        plan = _batch_plan(_host.ShapeOnly((int(pts.shape[0]),) + X_shape), displacement, 3, 'constant', 0.0, crop,
+                           axis, affine, rotate, zoom)
+    else:
+        plan = _host.cached_plan([_host.ShapeOnly(X_shape)], displacement, 3, 'constant', 0.0, crop, axis, affine,
+                                 rotate, zoom)
+    n = plan.naxis
+    if pts.ndim < 1 or int(pts.shape[-1]) != n:
+        raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
+                         "but their shape is %s." % (n, str(tuple(pts.shape))))
+    lead = tuple(int(v) for v in pts.shape[:-1])
+    name = _volume_dtype_name(pts)
+
+    if any(int(d) == 1 for d in plan.deform_shape):
+        # a deformed axis of length 1: the control coordinate divides by I - 1 = 0 (the image call maps every voxel
+        # to cval there) -- no coordinate is defined and nothing converges
+        return (_points_fill(pts, lead + (n,), float('nan'), name),
+                _points_fill(pts, lead + (n, n), float('nan'), 'float64') if jacobian else None,
+                _points_fill(pts, lead, False, 'bool') if inverse else None)
+
+    K = plan.inverse_affine
+    M = numpy.linalg.inv(numpy.asarray(K, dtype=numpy.float64)[:, :n]) if (inverse and K is not None) else None
+    torch = _torch()
+    device = _device_for([pts, displacement])
+    with torch.cuda.device(device):
+        pd = _to_device(pts, device)
+        if not batch:
+            pd = pd.reshape(-1, n)
+        dd = _to_device(displacement, device)
+        # the control grid is prefiltered like the image call's (order 3, mirror, rounded to its own dtype per axis)
+        df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device)
+        res = torch.empty(tuple(pd.shape), dtype=pd.dtype, device=device)
+        jac = torch.empty(tuple(pd.shape) + (n,), dtype=torch.float64, device=device) if jacobian else None
+        ok = torch.empty(tuple(pd.shape[:-1]), dtype=torch.uint8, device=device) if inverse else None
+        if batch:
+            nb = int(pd.shape[0])
+            (p0, ps), (d0, ds), (r0, rs) = _desc_sample0(pd), _desc_sample0(df), _desc_sample0(res)
+            j0, js = _desc_sample0(jac) if jac is not None else (None, 0)
+            s0, ss = _desc_sample0(ok) if ok is not None else (None, 0)
+        else:
+            nb = 1
+            p0, d0, r0 = _desc(pd), _desc(df), _desc(res)
+            j0 = _desc(jac) if jac is not None else None
+            s0 = _desc(ok) if ok is not None else None
+            ps = ds = rs = js = ss = 0
+        _lib.deform_points(inverse, nb, p0, ps, d0, ds, plan.deform_shape, plan.output_offset, K, M, r0, rs, j0, js,
+                           s0, ss, int(max_iter), float(tol), 0, _stream(device))
+        res = _from_device(res.reshape(lead + (n,)), pts)
+        if jac is not None:
+            jac = _from_device(jac.reshape(lead + (n, n)), pts)
+        if ok is not None:
+            ok = _from_device(ok.reshape(lead).to(torch.bool), pts)
+    return res, jac, ok
+
+
+def deform_grid_coordinates(positions, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                            zoom=None, jacobian=False):
+    """
+    The coordinate map of :func:`deform_grid` at arbitrary real positions: for every crop-local output position
+    ``q`` (``positions``, shape ``(..., naxis)``) the source coordinate ``r(q)`` at which
+    ``deform_grid(X, displacement, crop=crop, axis=axis, affine=affine, rotate=rotate, zoom=zoom)`` samples ``X``
+    for that output position -- ``Y[o] = X(r(o))`` at integer ``o``, before the boundary mode.  ``X_shape`` is the
+    shape of ``X``; the other arguments are deform_grid's own, checked the same way.
+
+    No boundary mode is applied: ``r`` is the unfolded map, defined for every real ``q`` (the control spline is
+    extended by its mirror tap map) and twice continuously differentiable.  With ``jacobian=True`` the result is
+    ``(r, J)`` with ``J[..., h, l] = d r_h / d q_l`` (float64, analytic); ``det J <= 0`` somewhere means the field
+    folds there.
+
+    float32 / float64 positions keep their dtype (the arithmetic is fp64, a float32 result is rounded once); integer
+    positions are taken as float64.  numpy in gives numpy out, otherwise the result is a tensor on the positions'
+    device.  A deformed axis of length 1 gives NaN.  No autograd flows through this call.
+    """
+    r, J, _ = _points_map(positions, displacement, X_shape, crop, axis, affine, rotate, zoom, False, jacobian, 1,
+                          1.0, False)
+    return (r, J) if jacobian else r
+
+
+def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None,
+                  max_iter=32, tol=1e-9, return_converged=False):
+    """
+    Where source points land in the output of
+    ``deform_grid(X, displacement, crop=crop, axis=axis, affine=affine, rotate=rotate, zoom=zoom)``: for every point
+    ``p`` in the coordinates of ``X`` (``points``, shape ``(..., naxis)``; ``X_shape`` is the shape of ``X``) the
+    crop-local output position ``q`` with ``r(q) = p``, ``r`` being :func:`deform_grid_coordinates`.  This is what
+    landmarks, keypoints, box corners and mesh vertices need: ``deform_grid`` is a pull warp, ``Y[o] = X(r(o))``, so
+    a landmark at ``p`` in ``X`` shows up in ``Y`` at the ``o`` with ``r(o) = p``.
+
+    Solved per point by a damped Newton iteration in fp64 from the affine part's own inverse, stopped at
+    ``|r(q) - p|_inf <= tol`` (voxels).  A point that is not solved within ``max_iter`` steps -- or whose Jacobian is
+    singular, or that is not finite -- is NaN in every component; ``return_converged=True`` also returns the bool
+    mask of the solved points.  On a folding field a point can have several pre-images: the result is the one this
+    iteration reaches from its start, the same on every call.  The result may lie outside the output array: the
+    point is then not visible in ``Y``.
+
+    dtypes, array families and the length-1 axis as for :func:`deform_grid_coordinates` (nothing converges there).
+    No autograd flows through this call.
+    """
+    q, _, ok = _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, True, False, max_iter,
+                           tol, False)
+    return (q, ok) if return_converged else q
+
+
+def deform_grid_coordinates_batch(positions, displacements, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                                  zoom=None, jacobian=False):
+    """:func:`deform_grid_coordinates` over a batch with one control grid per sample (:func:`deform_grid_batch`):
+    ``positions`` ``(B, N, naxis)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE
+    sample; everything else is shared.  One launch for the batch; sample b equals the single call, bit for bit."""
+    r, J, _ = _points_map(positions, displacements, X_shape, crop, axis, affine, rotate, zoom, False, jacobian, 1,
+                          1.0, True)
+    return (r, J) if jacobian else r
+
+
+def deform_points_batch(points, displacements, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None,
+                        max_iter=32, tol=1e-9, return_converged=False):
+    """:func:`deform_points` over a batch with one control grid per sample: ``points`` ``(B, N, naxis)``,
+    ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample; everything else is shared.
+    One launch for the batch; sample b equals the single call, bit for bit."""
+    q, _, ok = _points_map(points, displacements, X_shape, crop, axis, affine, rotate, zoom, True, False, max_iter,
+                           tol, True)
+    return (q, ok) if return_converged else q

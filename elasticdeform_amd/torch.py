@@ -20,6 +20,9 @@ from . import deform_grid_gradient as _deform_grid_gradient_fn
 from . import deform_grid_batch as _deform_grid_batch_fn
 from . import deform_grid_gradient_batch as _deform_grid_gradient_batch_fn
 from . import _host
+# mapping positions through the deformation (tensors stay on their device; no autograd flows through these four)
+from . import (deform_grid_coordinates, deform_points, deform_grid_coordinates_batch,  # noqa: F401
+               deform_points_batch)
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)

@@ -381,6 +381,56 @@ int edhip_deform_transform_gradient_batch_strided(int nbatch,
                                                   char* err, size_t errlen);
 
 /*
+ * The coordinate map of a deformation at arbitrary real positions, and its inverse (no counterpart in the reference).
+ * For a real, crop-local output position q of an edhip_deform call with this control grid, crop offset and inverse
+ * map K (`affine`; the identity when NULL),
+ *   cp_k   = (ncp_k - 1) (q_k + offset_k) / (in_len_k - 1)
+ *   r_h(q) = sum_l K[h, l] q_l + K[h, naxis] + offset_h + sum_taps P[h, m(floor(cp) - 1 + t)] prod_k w_k[t_k]
+ * (w: the cubic weights, m: the mirror tap map of deform.c:650-758): at integer q the source coordinate of
+ * deform.c:771-781 BEFORE the boundary map.  No boundary mode is applied; the mirror tap map extends the spline to
+ * every real q.
+ *   inverse == 0         result[i] = r(points[i]); with `jacobian` also J[i, h, l] = d r_h / d q_l (analytic).
+ *   inverse != 0         result[i] = q with r(q) = points[i] -- where a source position lands in the output -- by a
+ *                        damped Newton iteration in fp64 from q0 = M (p - offset - K[:, naxis]): the step from the
+ *                        analytic J, halved (at most 10 times) while the residual's max-norm does not decrease, until
+ *                        |r(q) - p|_inf <= tol.  After max_iter steps, an exhausted backtrack, a singular J or a
+ *                        non-finite point the result is NaN in every component and status[i] = 0; status[i] = 1 for a
+ *                        solved point.  On a folded field a point may have several pre-images: the result is the one
+ *                        this iteration reaches from q0 (deterministic).
+ * The batch is described once, as for edhip_deform_batch_strided: sample b's points, control grid, result, jacobian
+ * and status are sample 0's moved by b * stride bytes (nbatch = 1: a single call); everything else is shared.
+ *   points0 / result0    (N, naxis), float32 or float64 each, any strides; the arithmetic is fp64, a float32 result is
+ *                        rounded once at the store.  N = 0 launches nothing.
+ *   displacement0        the PREFILTERED control grid (naxis, ncp_0, ...), any dtype / strides.
+ *                        EDHIP_FLAG_RAW_DISPLACEMENT is refused (EDHIP_ERR_INVALID): the caller prefilters.
+ *   in_len               host int64[naxis]: the deformed extents of the input (>= 2 each).
+ *   output_offset        naxis crop offsets (host int64) or NULL;  affine: K, host double[naxis * (naxis+1)] or NULL.
+ *   forward_linear       inverse only: M = (K[:, :naxis])^-1, host double[naxis * naxis] row-major; NULL with a NULL
+ *                        affine (the identity).
+ *   jacobian0            NULL, or (forward only) float64 (N, naxis, naxis), any strides.
+ *   status0              NULL, or (inverse only) uint8 (N).
+ *   max_iter, tol        inverse only: >= 1 and > 0.
+ * Every shape and dtype check answers before any launch.  One launch, one thread per point, no atomics: a point's
+ * result depends on that point and the call's arguments alone (a sample of a batch, a slice of the points and a
+ * repeated call give the same bits).  The call enqueues on hip_stream, never synchronises and uses no workspace, so
+ * it can be captured into a HIP graph.
+ */
+int edhip_deform_points(int inverse, int nbatch,
+                        const edhip_array* points0, int64_t points_batch_stride,
+                        const edhip_array* displacement0, int64_t displacement_batch_stride,
+                        const int64_t* in_len,
+                        const int64_t* output_offset,
+                        int naxis,
+                        const double* affine,
+                        const double* forward_linear,
+                        const edhip_array* result0, int64_t result_batch_stride,
+                        const edhip_array* jacobian0, int64_t jacobian_batch_stride,
+                        const edhip_array* status0, int64_t status_batch_stride,
+                        int max_iter, double tol,
+                        uint32_t flags, void* hip_stream,
+                        char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
