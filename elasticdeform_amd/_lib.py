@@ -54,7 +54,7 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_release_scratch', 'edhip_profile_dominant',
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
-           'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points')
+           'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels')
 
 
 class EdhipArray(ctypes.Structure):
@@ -176,6 +176,12 @@ def load():
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
             ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_labels.restype = ctypes.c_int
+        L.edhip_deform_labels.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_double,
+            ctypes.POINTER(ctypes.c_double), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -376,6 +382,24 @@ def deform_points(inverse, nbatch, pts_desc, pts_bstride, disp_desc, disp_bstrid
         int(disp_bstride), in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, lin,
         ctypes.byref(res_desc), int(res_bstride), _ref(jac_desc), int(jac_bstride), _ref(status_desc),
         int(status_bstride), int(max_iter), float(tol), int(flags), ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
+
+
+def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, out_desc, out_bstride,
+                  weight_desc, weight_bstride, axis, mode, cval, inverse_affine, flags, stream):
+    """edhip_deform_labels: label-aware linear resampling of an integer / bool label map into `out_desc` (the label
+    with the largest sum of order-1 weights among the 2^naxis source voxels, ties to the smallest label) and, with
+    `weight_desc` (float32, the output's shape; None = not wanted), the winning sum.  Sample 0's descriptors plus
+    byte strides; `disp_desc` is the PREFILTERED control grid."""
+    L = load()
+    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    buf = _buf()
+    status = L.edhip_deform_labels(
+        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
+        ctypes.byref(out_desc), int(out_bstride), _ref(weight_desc), int(weight_bstride), len(axis),
+        axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(mode), float(cval), aff, int(flags),
+        ctypes.c_void_p(stream), buf, 256)
     raise_for_status(status, buf)
 
 

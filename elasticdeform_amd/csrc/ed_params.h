@@ -207,6 +207,23 @@ struct PointsCall {
 constexpr int kPointsLdsValues = 7680;   // control grids up to this many values are staged in LDS (60 KiB of doubles)
 hipError_t launch_deform_points(const PointsCall& c, hipStream_t stream);
 
+// Label-aware linear resampling of label maps (deform_vote.hip): per output voxel the order-1 weights are summed per
+// distinct label among the 2^naxis source voxels, the label with the largest sum is stored (ties: the smallest label).
+// One thread per (voxel, step), blockIdx.y = sample; no scratch, no synchronisation.  1 to 3 deformed axes, integer
+// and bool maps (v.in_dtype == v.out_dtype); hipErrorNotSupported (nothing launched) otherwise.
+struct LabelsCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0
+    IOView v;                     // the label maps of sample 0: v.in read, v.out written; v.mode; order and cval unused
+    int nbatch;
+    int64_t in_bstride, out_bstride, disp_bstride;   // bytes between samples
+    uint64_t cval_bits;           // cval as an element of the map's dtype (two's complement, in the low bytes)
+    char* weight;                 // float32, the output's shape: the winning sum; nullptr: not wanted
+    int64_t weight_stride[kMaxAxes];                 // byte strides of the deformed axes
+    int64_t weight_step_stride[kMaxSteps];           // ... of the non-deformed axes, in the order of v.step_len
+    int64_t weight_bstride;
+};
+hipError_t launch_deform_labels(const LabelsCall& c, hipStream_t stream);
+
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;
 

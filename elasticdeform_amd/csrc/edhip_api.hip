@@ -1380,4 +1380,118 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
     return EDHIP_OK;
 }
 
+// ---- label-aware linear resampling of label maps (deform_vote.hip) --------------------------------------------
+int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                        const edhip_array* displacement0, int64_t displacement_batch_stride,
+                        const int64_t* output_offset, const edhip_array* output0, int64_t output_batch_stride,
+                        const edhip_array* weight0, int64_t weight_batch_stride, int naxis, const int32_t* axis,
+                        int32_t mode, double cval, const double* affine, uint32_t flags, void* hip_stream, char* err,
+                        size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || !input0 || !displacement0 || !output0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (!axis || naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > 3)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_labels takes 1 to 3 deformed axes");
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_labels takes the prefiltered control grid");
+    const edhip_array& in = *input0;
+    const edhip_array& out = *output0;
+    if (in.ndim != out.ndim)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "input and output dimensions should match");
+    if (in.ndim < 1 || in.ndim > EDHIP_MAX_DIMS)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions", EDHIP_MAX_DIMS);
+    if (in.dtype != out.dtype || in.dtype < EDHIP_BOOL || in.dtype > EDHIP_I64)
+        return fail(err, errlen, EDHIP_ERR_INVALID,
+                    "label maps must be integer or bool arrays, input and output of one dtype");
+    for (int j = 0; j < naxis; ++j)
+        if (axis[j] < 0 || axis[j] >= in.ndim || (j > 0 && axis[j] <= axis[j - 1]))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
+    if (mode < 0 || mode > 4)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
+    if (displacement0->ndim != naxis + 1 || displacement0->shape[0] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (!dtype_ok(displacement0->dtype))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    for (int k = 0; k <= naxis; ++k)
+        if (displacement0->shape[k] <= 0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (weight0) {
+        bool same = weight0->ndim == out.ndim;
+        for (int d = 0; same && d < out.ndim; ++d)
+            same = weight0->shape[d] == out.shape[d];
+        if (!same)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "weight must have the shape of the output");
+        if (weight0->dtype != EDHIP_F32)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "weight must be float32");
+    }
+    // cval as an element of the map's dtype: an integer value inside its range
+    uint64_t cval_bits = 0;
+    {
+        double lo = 0.0, hi = 1.0;           // bool; hi is the largest value for the narrow types, 2^63 / 2^64 (excluded) for the wide ones
+        bool hi_excluded = false;
+        switch (in.dtype) {
+        case EDHIP_U8: hi = 255.0; break;
+        case EDHIP_I8: lo = -128.0; hi = 127.0; break;
+        case EDHIP_U16: hi = 65535.0; break;
+        case EDHIP_I16: lo = -32768.0; hi = 32767.0; break;
+        case EDHIP_U32: hi = 4294967295.0; break;
+        case EDHIP_I32: lo = -2147483648.0; hi = 2147483647.0; break;
+        case EDHIP_U64: hi = 18446744073709551616.0; hi_excluded = true; break;
+        case EDHIP_I64: lo = -9223372036854775808.0; hi = 9223372036854775808.0; hi_excluded = true; break;
+        default: break;
+        }
+        if (!(cval >= lo) || !(hi_excluded ? cval < hi : cval <= hi) || cval != std::floor(cval))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "cval must be an integer value of the label map's dtype");
+        cval_bits = lo < 0.0 ? (uint64_t)(int64_t)cval : (uint64_t)cval;
+    }
+    if (nbatch > 65535)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_labels: too many samples");
+    LabelsCall c;
+    memset(&c, 0, sizeof(c));
+    {
+        int64_t in_len[kMaxAxes], out_len[kMaxAxes];
+        for (int k = 0; k < naxis; ++k) {
+            in_len[k] = in.shape[axis[k]];
+            out_len[k] = out.shape[axis[k]];
+        }
+        // (no EDHIP_FLAG_RAW_DISPLACEMENT: nothing is launched or reserved; refuses deformed extents below 2)
+        const int st = make_geometry(displacement0, in_len, out_len, output_offset, naxis, affine, 0, stream, c.g, err,
+                                     errlen);
+        if (st != EDHIP_OK)
+            return st;
+    }
+    int st = make_view(in, out, naxis, axis, 1, mode, cval, c.v, err, errlen);
+    if (st != EDHIP_OK)
+        return st;
+    if (weight0) {
+        IOView wv;                            // the weight's strides, sorted like the output's
+        st = make_view(in, *weight0, naxis, axis, 1, mode, cval, wv, err, errlen);
+        if (st != EDHIP_OK)
+            return st;
+        c.weight = (char*)weight0->data;
+        for (int k = 0; k < naxis; ++k)
+            c.weight_stride[k] = wv.out_stride[k];
+        for (int l = 0; l < wv.nstep; ++l)
+            c.weight_step_stride[l] = wv.out_step_stride[l];
+        c.weight_bstride = weight_batch_stride;
+    }
+    if (nbatch == 0 || c.g.nvox <= 0 || c.v.nsteps <= 0)
+        return EDHIP_OK;
+    c.nbatch = nbatch;
+    c.in_bstride = input_batch_stride;
+    c.out_bstride = output_batch_stride;
+    c.disp_bstride = displacement_batch_stride;
+    c.cval_bits = cval_bits;
+    const hipError_t e = launch_deform_labels(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform labels launch");
+    return EDHIP_OK;
+}
+
 }  // extern "C"

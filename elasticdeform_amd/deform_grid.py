@@ -1337,3 +1337,127 @@ def deform_points_batch(points, displacements, X_shape, crop=None, axis=None, af
     q, _, ok = _points_map(points, displacements, X_shape, crop, axis, affine, rotate, zoom, True, False, max_iter,
                            tol, True)
     return (q, ok) if return_converged else q
+
+
+# ---- label-aware linear resampling of label maps (no counterpart in the reference) -------------------------------
+
+_LABEL_RANGE = {'bool': (0, 1), 'uint8': (0, 2 ** 8 - 1), 'int8': (-2 ** 7, 2 ** 7 - 1), 'uint16': (0, 2 ** 16 - 1),
+                'int16': (-2 ** 15, 2 ** 15 - 1), 'uint32': (0, 2 ** 32 - 1), 'int32': (-2 ** 31, 2 ** 31 - 1),
+                'uint64': (0, 2 ** 64 - 1), 'int64': (-2 ** 63, 2 ** 63 - 1)}
+
+
+def _label_cval(cval, name):
+    """cval as a Python int: an integer value the label dtype can represent (and a float64 can carry to the library)"""
+    try:
+        value = int(cval)
+        ok = value == cval and float(value) == value
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if ok:
+        lo, hi = _LABEL_RANGE[name]
+        ok = lo <= value <= hi
+    if not ok:
+        raise ValueError("cval should be an integer value that the label map's dtype (%s) can represent, "
+                         "but %r given." % (name, cval))
+    return value
+
+
+def _label_fill(like, shape, value, dtype=None):
+    """an array of `shape` filled with `value`, in the family and on the device of `like`; `like`'s dtype unless given"""
+    shape = tuple(int(v) for v in shape)
+    if isinstance(like, numpy.ndarray):
+        return numpy.full(shape, value, dtype=like.dtype if dtype is None else dtype)
+    torch = _torch()
+    return torch.full(shape, value, dtype=like.dtype if dtype is None else getattr(torch, dtype), device=like.device)
+
+
+def _labels_run(L, displacement, mode, cval, crop, axis, affine, rotate, zoom, return_weight, batch):
+    """Both forms of deform_grid_labels.  Every argument check runs before the device is touched; offsets, the inverse
+    map and the rotate / zoom centre are deform_grid's own for order 1 (the same Plan)."""
+    if batch:
+        plan = _batch_plan(L, displacement, 1, mode, cval, crop, axis, affine, rotate, zoom)
+        Ls = [L]
+        shapes = [tuple(int(v) for v in L.shape[1:])]
+    else:
+        Ls = _host.normalize_inputs(L)
+        plan = _host.cached_plan(Ls, displacement, 1, mode, cval, crop, axis, affine, rotate, zoom)
+        shapes = [tuple(int(v) for v in x.shape) for x in Ls]
+    n = len(Ls)
+    names = [_volume_dtype_name(x) for x in Ls]
+    if any(name not in _LABEL_RANGE for name in names):
+        raise RuntimeError('data type not supported')     # float, complex, 16-bit float: label maps are integer or bool
+    cvals = [_label_cval(c, name) for c, name in zip(_host._per_input(cval, n, 'cval'), names)]
+    if plan.naxis > 3:
+        raise RuntimeError('deform_grid_labels takes 1 to 3 deformed axes')   # (the library's own limit)
+    lead = (int(L.shape[0]),) if batch else ()
+    out_shapes = [lead + tuple(int(v) for v in s) for s in plan.output_shapes]
+
+    if _host.degenerate_axis(shapes, plan.axis):
+        # a deformed axis of length 1: every voxel maps to the constant, as in deform_grid (_host.degenerate_axis)
+        labels = [_label_fill(x, s, c) for x, s, c in zip(Ls, out_shapes, cvals)]
+        weights = [_label_fill(x, s, 1.0, 'float32') for x, s in zip(Ls, out_shapes)]
+    else:
+        torch = _torch()
+        device = _device_for(list(Ls) + [displacement])
+        labels, weights = [], []
+        with torch.cuda.device(device):
+            stream = _stream(device)
+            dd = _to_device(displacement, device)
+            # the control grid is prefiltered like deform_grid's (order 3, mirror, rounded to its own dtype per axis)
+            df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device, stream=stream)
+            for i, x in enumerate(Ls):
+                xd = _to_device(x, device)
+                out = torch.empty(out_shapes[i], dtype=xd.dtype, device=device)
+                wt = torch.empty(out_shapes[i], dtype=torch.float32, device=device) if return_weight else None
+                if batch:
+                    (x0, xs), (d0, ds), (o0, os_) = _desc_sample0(xd), _desc_sample0(df), _desc_sample0(out)
+                    w0, ws = _desc_sample0(wt) if wt is not None else (None, 0)
+                else:
+                    x0, d0, o0 = _desc(xd), _desc(df), _desc(out)
+                    w0 = _desc(wt) if wt is not None else None
+                    xs = ds = os_ = ws = 0
+                # one library call (one launch) per input
+                _lib.deform_labels(lead[0] if batch else 1, x0, xs, d0, ds, plan.output_offset, o0, os_, w0, ws,
+                                   plan.axis[i], int(plan.mode[i]), float(cvals[i]), plan.inverse_affine, 0, stream)
+                labels.append(_from_device(out, x))
+                weights.append(_from_device(wt, x) if wt is not None else None)
+    if return_weight:
+        res = list(zip(labels, weights))
+        return res if isinstance(L, list) else res[0]
+    return labels if isinstance(L, list) else labels[0]
+
+
+def deform_grid_labels(L, displacement, mode='constant', cval=0, crop=None, axis=None, affine=None, rotate=None,
+                       zoom=None, return_weight=False):
+    """
+    Label-aware linear resampling of a label map (a segmentation mask) under the deformation of :func:`deform_grid`:
+    per output voxel, the ``2^naxis`` linear-interpolation weights are summed per distinct label among the
+    ``2^naxis`` source voxels and the label with the largest sum is stored -- what deforming one float channel per
+    class with ``order=1`` and taking the argmax computes, in one pass over the integer map and without the one-hot
+    volumes.  No label number is ever interpolated: the result only holds values of ``L`` (and ``cval``), where
+    ``deform_grid(L, order=1)`` puts label 5 halfway between labels 2 and 8, and its boundaries are smoother than
+    those of ``order=0``.
+
+    With the classes being the distinct values of ``L`` together with ``cval``, the score of class ``c`` is
+    ``s_c = deform_grid((L == c).astype(float64), displacement, order=1, mode=mode, cval=1.0 if c == cval else 0.0,
+    ...)`` and the result is the class with the largest score; **on a tie the numerically smallest label wins**.
+    The result equals that definition bit for bit, ties included.  ``return_weight=True`` returns ``(labels, weight)``
+    with the winning score rounded once to float32: in ``[2^-naxis, 1]``, a boundary-confidence map.
+
+    ``L``: an integer or bool array, or a list of them (a list gives a list, of pairs with ``return_weight``; ``mode``,
+    ``cval`` and ``axis`` may then be per-input lists as in deform_grid); 1 to 3 deformed axes.  ``cval`` must be an
+    integer value the dtype can represent (ValueError otherwise); float, complex and 16-bit float inputs raise
+    ``RuntimeError('data type not supported')``.  ``displacement``, ``mode``, ``crop``, ``axis``, ``affine``,
+    ``rotate`` and ``zoom`` have deform_grid's meaning and checks.  A deformed axis of length 1 gives ``cval``
+    everywhere with weight 1.0, as in deform_grid.  numpy in gives numpy out, tensors stay on their device.  No
+    autograd flows through this call.
+    """
+    return _labels_run(L, displacement, mode, cval, crop, axis, affine, rotate, zoom, return_weight, False)
+
+
+def deform_grid_labels_batch(L, displacements, mode='constant', cval=0, crop=None, axis=None, affine=None, rotate=None,
+                             zoom=None, return_weight=False):
+    """:func:`deform_grid_labels` over a batch with one control grid per sample (:func:`deform_grid_batch`): ``L``
+    ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``axis`` counts the axes of ONE sample; everything else
+    is shared.  One launch for the batch; sample b equals the single call on sample b, bit for bit."""
+    return _labels_run(L, displacements, mode, cval, crop, axis, affine, rotate, zoom, return_weight, True)

@@ -23,6 +23,8 @@ from . import _host
 # mapping positions through the deformation (tensors stay on their device; no autograd flows through these four)
 from . import (deform_grid_coordinates, deform_points, deform_grid_coordinates_batch,  # noqa: F401
                deform_points_batch)
+# label-aware linear resampling of label maps (integer tensors stay on their device; no autograd)
+from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)

@@ -431,6 +431,47 @@ int edhip_deform_points(int inverse, int nbatch,
                         char* err, size_t errlen);
 
 /*
+ * Label-aware linear resampling of label maps (no counterpart in the reference, whose order-1 interpolation of an
+ * integer map interpolates the label NUMBERS).  For a label map L, with the classes being the distinct values of L
+ * together with cval, the score of class c is the reference's own float64 order-1 result on the one-hot channel,
+ *   s_c = DeformGrid((L == c) as float64, order = 1, mode, cval = 1.0 if c == cval else 0.0, same geometry),
+ * and the result at output voxel o is the class with the largest s_c(o); ON A TIE THE NUMERICALLY SMALLEST LABEL
+ * WINS.  `weight0`, when given, receives the winning score rounded once to float32: it lies in [2^-naxis, 1] and is
+ * 1.0 where a 'constant' voxel outside the array takes cval.  The result equals that definition BIT FOR BIT, ties
+ * included: per output voxel the 2^naxis order-1 weight products (1.0 * w_0 * ... * w_{naxis-1}, formed in axis order)
+ * are added per distinct label among the 2^naxis source voxels in the reference's tap order (lexicographic, last axis
+ * fastest; deform.c:843-901), the coordinate comes from the reference-order fp64 evaluation (deform.c:650-824, no
+ * FMA), so every compared score has the bits of the one-hot channel's reference value.  One gather pass over the
+ * integer map: no one-hot volumes, no prefilter of the map.
+ * The batch is described once, as for edhip_deform_batch_strided: sample b's map, control grid, result and weight
+ * are sample 0's moved by b * stride bytes (nbatch = 1: a single call); everything else is shared.
+ *   input0 / output0     the label map and the result: one dtype, integer or bool (EDHIP_ERR_INVALID otherwise), any
+ *                        strides; labels are compared as raw integers of their own width (int64 / uint64 values
+ *                        beyond 2^53 stay distinct), signed or unsigned by dtype.
+ *   displacement0        the PREFILTERED control grid (naxis, ncp_0, ...), any dtype / strides.
+ *                        EDHIP_FLAG_RAW_DISPLACEMENT is refused (EDHIP_ERR_INVALID): the caller prefilters.
+ *   weight0              NULL, or float32 with the output's shape (EDHIP_ERR_INVALID / EDHIP_ERR_DTYPE), any strides.
+ *   naxis, axis          1 to 3 deformed axes (more: EDHIP_ERR_UNSUPPORTED), ascending; the other axes are carried
+ *                        along as in edhip_deform.  A deformed axis of length < 2 is refused as edhip_deform refuses it.
+ *   mode, cval           enum edhip_mode; cval must be an integer value the dtype can represent (EDHIP_ERR_INVALID).
+ *   output_offset, affine  as for edhip_deform.
+ * Every check answers before any launch.  One launch, one thread per (output voxel, step), no atomics: a voxel's
+ * result depends on the call's arguments alone (a sample of a batch and a repeated call give the same bits).  The call
+ * enqueues on hip_stream, never synchronises and uses no workspace, so it can be captured into a HIP graph.
+ */
+int edhip_deform_labels(int nbatch,
+                        const edhip_array* input0, int64_t input_batch_stride,
+                        const edhip_array* displacement0, int64_t displacement_batch_stride,
+                        const int64_t* output_offset,
+                        const edhip_array* output0, int64_t output_batch_stride,
+                        const edhip_array* weight0, int64_t weight_batch_stride,
+                        int naxis, const int32_t* axis,
+                        int32_t mode, double cval,
+                        const double* affine,
+                        uint32_t flags, void* hip_stream,
+                        char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
