@@ -585,12 +585,13 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
 // ================================================================================================
 // the forward kernels
 // ================================================================================================
-// Three launches per call behind the geometry kernel:
-//   k1z_fast_kernel   class-A tiles (full tile, coordinates inside the array, box inside the array, fits): ~89 % of the
-//                     benchmark's tiles.  No boundary tests, one staging path, a small argument block: nothing but the
-//                     per-voxel work is left in the loop.
-//   k1z_gen_kernel    general tiles (array faces, partial tiles, boxes that touch the array's ends), on a second stream
-//                     next to the fast kernel, persistent over the list of strips that have such tiles.
+// Two launches per call behind the geometry kernel, both on the caller's stream:
+//   k1z_tile_kernel   rows of workgroups in one of two roles:
+//                     fast rows -- class-A tiles (full tile, coordinates inside the array, box inside the array, fits):
+//                     ~89 % of the benchmark's tiles.  No boundary tests, one staging path, a small argument block:
+//                     nothing but the per-voxel work is left in the loop;
+//                     general rows -- general tiles (array faces, partial tiles, boxes that touch the array's ends),
+//                     interleaved with the fast rows, persistent over the list of strips that have such tiles.
 //   k1z_fix_kernel    behind both: tiles whose box does not fit LDS, and the voxels of staged tiles whose window was not
 //                     inside the sampled box (the tile kernels raise a flag per strip), straight from global memory.
 // All walk the same strips; a voxel gets the same bits whichever serves it (same R, same z table, same sums).
@@ -892,7 +893,7 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
 // ---- everything else ---------------------------------------------------------------------------------------------
 // General tiles (array faces, partial tiles, boxes that touch the array's ends): general coordinates (deform.c:771-824)
 // with the boundary map, constant and valid flags, every staging path.  Persistent over list G (the strips with such
-// tiles); launched on a second stream next to the fast kernel, so that its long strips -- the columns on the x faces,
+// tiles); its rows run in the fast rows' launch (k1z_tile_kernel), so that its long strips -- the columns on the x faces,
 // whose boxes are staged element by element -- overlap with the class-A work instead of trailing it.  Same walk, same R
 // and z table, same sums as the fast kernel: the same bits.
 template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
@@ -1125,9 +1126,9 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
 
 // ONE launch for both: rows of 8 consecutive workgroups (one per XCD) take the role of the fast kernel or -- every
 // `every`-th row, until there are `ngen` of them -- of the general kernel, so that the persistent general workgroups start
-// with the first class-A strips and run beside them.  (As two launches on two streams the fork and the join cost the
-// caller's stream ~6 us of idle each, and at the stream priorities on offer the general kernel either took the class-A
-// kernel's slots or was starved until it had finished.)
+// with the first class-A strips and run beside them.  (Measured as two launches on two streams in round 6: the fork and
+// the join cost the caller's stream ~6 us of idle each, and at the stream priorities on offer the general kernel either
+// took the class-A kernel's slots or was starved until it had finished.  The library has had one stream per call since.)
 template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
 __global__ __launch_bounds__(kBlock, 4) void k1z_tile_kernel(const ZFast a, czgen_p zn, const int ngen, const int every)
 {
@@ -1290,7 +1291,7 @@ __global__ __launch_bounds__(kBlock) void k1z_fix_kernel(const ZFast a, czgen_p 
 }
 
 template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
-hipError_t launch_k1z_kernels(const ZFast& zf, const void* znp, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream, SideLane*)
+hipError_t launch_k1z_kernels(const ZFast& zf, const void* znp, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream)
 {
     const unsigned nfast = k1z_grid(zf.total_strips, zf.deal);
     // general rows interleaved with the fast rows in proportion, all of them within the first fast rows' reach
@@ -1307,22 +1308,21 @@ hipError_t launch_k1z_kernels(const ZFast& zf, const void* znp, unsigned ngen, u
     return hipGetLastError();
 }
 template <int ORDER, bool AFFINE, bool OUT16>
-hipError_t launch_k1z_variant(const ZFast& zf, const void* zn, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream, SideLane* side,
+hipError_t launch_k1z_variant(const ZFast& zf, const void* zn, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream,
                               bool steps)
 {
-    return steps ? launch_k1z_kernels<ORDER, AFFINE, OUT16, true>(zf, zn, ngen, nfix, lds, stream, side)
-                 : launch_k1z_kernels<ORDER, AFFINE, OUT16, false>(zf, zn, ngen, nfix, lds, stream, side);
+    return steps ? launch_k1z_kernels<ORDER, AFFINE, OUT16, true>(zf, zn, ngen, nfix, lds, stream)
+                 : launch_k1z_kernels<ORDER, AFFINE, OUT16, false>(zf, zn, ngen, nfix, lds, stream);
 }
 template <int ORDER>
-hipError_t launch_k1z_order(const HotGeom& hg, const ZFast& zf, const void* zn, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream,
-                            SideLane* side)
+hipError_t launch_k1z_order(const HotGeom& hg, const ZFast& zf, const void* zn, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream)
 {
     const bool steps = hg.nstep != 0;
     if (hg.io16)
-        return hg.has_affine ? launch_k1z_variant<ORDER, true, true>(zf, zn, ngen, nfix, lds, stream, side, steps)
-                             : launch_k1z_variant<ORDER, false, true>(zf, zn, ngen, nfix, lds, stream, side, steps);
-    return hg.has_affine ? launch_k1z_variant<ORDER, true, false>(zf, zn, ngen, nfix, lds, stream, side, steps)
-                         : launch_k1z_variant<ORDER, false, false>(zf, zn, ngen, nfix, lds, stream, side, steps);
+        return hg.has_affine ? launch_k1z_variant<ORDER, true, true>(zf, zn, ngen, nfix, lds, stream, steps)
+                             : launch_k1z_variant<ORDER, false, true>(zf, zn, ngen, nfix, lds, stream, steps);
+    return hg.has_affine ? launch_k1z_variant<ORDER, true, false>(zf, zn, ngen, nfix, lds, stream, steps)
+                         : launch_k1z_variant<ORDER, false, false>(zf, zn, ngen, nfix, lds, stream, steps);
 }
 
 }  // namespace
@@ -1375,7 +1375,7 @@ hipError_t launch_k1z_geo(const GridGeom& g, const HotGeom& hg, const ZGeom& zg,
     return hipGetLastError();
 }
 
-hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds, hipStream_t stream, SideLane* side)
+hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds, hipStream_t stream)
 {
     ZFast zf;
     memset(&zf, 0, sizeof(zf));
@@ -1437,9 +1437,9 @@ hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds,
         ngen = (unsigned)((atoi(ng) + 7) / 8 * 8);
     const unsigned nfix = (unsigned)(zg.total_strips < 512 ? ((zg.total_strips + 7) / 8) * 8 : 512);
     switch (order) {
-    case 1: return launch_k1z_order<1>(hg, zf, zn, ngen, nfix, lds, stream, side);
-    case 2: return launch_k1z_order<2>(hg, zf, zn, ngen, nfix, lds, stream, side);
-    case 3: return launch_k1z_order<3>(hg, zf, zn, ngen, nfix, lds, stream, side);
+    case 1: return launch_k1z_order<1>(hg, zf, zn, ngen, nfix, lds, stream);
+    case 2: return launch_k1z_order<2>(hg, zf, zn, ngen, nfix, lds, stream);
+    case 3: return launch_k1z_order<3>(hg, zf, zn, ngen, nfix, lds, stream);
     default: return hipErrorNotSupported;
     }
 }

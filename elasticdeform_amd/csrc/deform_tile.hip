@@ -1151,7 +1151,7 @@ inline size_t q_global_bytes(const GridGeom& g, bool wide_opt = false)
     }
     return 8 * (size_t)g.out_len[0] * (size_t)g.out_len[1] * 4 * cols;
 }
-// The geometry buffer of the forward route of deform_k1z.hip (SideLane::geo_ptr, its own allocation):
+// The geometry buffer of the forward route of deform_k1z.hip (ed::GeoBuffer, its own allocation):
 //   counters (4 KiB, cleared at allocation) | ZGen (512) | z table | tile records (32 bytes per tile), flags and summaries
 //   (4 + 4 per strip, at most one strip per tile), two work lists dealt per XCD (entry k of XCD x at slot 8 k + x: 32 + 32
 //   per strip, in case one XCD gets them all), records of the tiles' z halves (64) | step offsets | R
@@ -1723,7 +1723,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
 #endif
                 ZGeom zg;
                 memset(&zg, 0, sizeof(zg));
-                SideLane* zside = nullptr;
+                GeoBuffer* zgeo = nullptr;
                 if (k1z) {
                     (void)k1z_lds_bytes(&hg.small_cap, false);
                     hlds = k1z_lds_bytes(&hg.box_cap, large_boxes);
@@ -1735,8 +1735,8 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                         r2 += r * r;
                     }
                     zg.slack_scale = 0.15 * 1.125 * 4.0 * r2;
-                    zside = side_lane(stream);
-                    char* gb = zside ? (char*)geo_reserve(stream, zside, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
+                    zgeo = geo_buffer(stream);
+                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
                     if (!gb)
                         return e != hipSuccess ? e : hipErrorOutOfMemory;
                     zg.ctl = (int*)gb;                       // the lists' counters: 32 ints in the cleared head
@@ -1752,7 +1752,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                     zg.steps = (long long*)(zx + k1z_zt_bytes(g) + (((size_t)ntiles * nb * 168 + 63) & ~(size_t)63));
                     zg.r = (const double*)((char*)zg.steps + kK1zMaxSteps * 16);
                     zg.r_bstride = (long long)(((k1z_r_bytes(g) + 63) & ~(size_t)63) / 8);
-                    zg.parity = (int)(zside->parity & 1);
+                    zg.parity = (int)(zgeo->parity & 1);
                     zg.disp_bstride = tg.disp_bstride;
                     zg.ncpz = (int)g.ncp[0];
                     zg.order = ORDER;
@@ -1918,7 +1918,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                     if (!tables_done && e == hipSuccess) {
                         e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
                         if (e == hipSuccess)
-                            ++zside->parity;       // (the launch is in the stream: the next call uses the other counters)
+                            ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
                         if (own && e == hipSuccess)
                             batch->gridpf_done = true;
                         tables_done = true;
@@ -1938,8 +1938,8 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
 #endif
                 size_t k2lds = 0;
                 if (k2z) {
-                    zside = side_lane(stream);
-                    char* gb = zside ? (char*)geo_reserve(stream, zside, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
+                    zgeo = geo_buffer(stream);
+                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
                     if (!gb)
                         return e != hipSuccess ? e : hipErrorOutOfMemory;
                     zg.ctl = (int*)gb;
@@ -2100,7 +2100,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                 if (wide_wave && !wave_done && e == hipSuccess)
                     e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
                 if (hlds && !wave_done && !hot_done && e == hipSuccess) {
-                    const hipError_t he = k1z ? launch_k1z(hg, zg, ORDER, hlds, stream, zside)
+                    const hipError_t he = k1z ? launch_k1z(hg, zg, ORDER, hlds, stream)
                                           : (k1_new ? launch_k1_level1(hg, ORDER, nblk, hlds, stream)
                                                     : launch_hot_level1(hg, ORDER, GRAD, nblk, hlds, stream));
                     if (he == hipSuccess) {

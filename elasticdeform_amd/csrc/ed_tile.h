@@ -477,7 +477,8 @@ struct ZGeom {
     int* sinfo;               // [sample * nstrips + strip]: 3 bits per tile of the strip (class, beyond the standard box)
     // work lists of strips: G = general tiles (geometry kernel), F = tiles that do not fit (geometry kernel) or a window
     // outside its sampled box (tile kernels).  ctl[parity] / ctl[2 + parity] = their counts for this call; the geometry
-    // kernel clears the other parity's for the next call on the stream (the workspace head is cleared when allocated)
+    // kernel clears the other parity's for the next call on the stream (the head of the geometry buffer, ed::GeoBuffer,
+    // is cleared when allocated)
     int* list_g;
     int* list_f;
     int* ctl;
@@ -503,7 +504,7 @@ bool k1z_supported(const GridGeom& g);
 size_t k1z_r_bytes(const GridGeom& g);
 hipError_t launch_k1z_geo(const GridGeom& g, const HotGeom& hg, const ZGeom& zg, const GridPrefilter& gp, int nbatch,
                           hipStream_t stream);
-hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds, hipStream_t stream, ed::SideLane* side);
+hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds, hipStream_t stream);
 // K2 of round 6 (deform_k2z.hip): the gradient on the z-walk tables (geometry kernel in its tables-only form)
 size_t k2z_lds_bytes(int* box_cap);
 hipError_t launch_k2z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds, hipStream_t stream);

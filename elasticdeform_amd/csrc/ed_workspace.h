@@ -65,23 +65,19 @@ GridStamp* grid_stamp(hipStream_t stream);
 // counts the times the stream's workspace buffer was freed or replaced (a stamp from an earlier generation is void)
 unsigned long long workspace_generation(hipStream_t stream);
 
-// A second stream per (device, stream) with the two events that fork it from / join it to the caller's stream, for the
-// forward route of deform_k1z.hip: the general-tile kernel runs next to the class-A kernel.  `parity` alternates
-// between the calls of that route (which pair of work-list counters in the workspace head the call uses).  nullptr:
-// no second stream could be made (the caller launches everything on its own stream).  Callers hold the StreamGuard.
-struct SideLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+// The geometry buffer of the forward route of deform_k1z.hip, per (device, stream): an allocation of its own (tables,
+// tile records, work lists + their counters) that nothing but that route's geometry kernel writes.  `parity` alternates
+// between the calls of that route (which pair of work-list counters in the buffer's head the call uses).  Callers hold
+// the StreamGuard.
+struct GeoBuffer {
     unsigned parity = 0;
-    bool usable = false;
-    // the geometry stage's own buffer (tables, tile records, work lists + their counters): nothing else writes it
-    void* geo_ptr = nullptr;
-    size_t geo_cap = 0;
+    void* ptr = nullptr;
+    size_t cap = 0;
 };
-SideLane* side_lane(hipStream_t stream);
-// at least `bytes` of the lane's geometry buffer (grown on demand: both streams are drained first);
-// the first 4 KiB -- the work lists' counters -- are cleared when the buffer is allocated
-void* geo_reserve(hipStream_t stream, SideLane* lane, size_t bytes, hipError_t* err);
+GeoBuffer* geo_buffer(hipStream_t stream);          // nullptr when the current device cannot be read
+// at least `bytes` of the geometry buffer (grown on demand: the stream is drained first); the first 4 KiB -- the work
+// lists' counters -- are cleared when the buffer is allocated
+void* geo_reserve(hipStream_t stream, GeoBuffer* geo, size_t bytes, hipError_t* err);
 
 // Drains the devices that own scratch and frees every cached buffer.
 void workspace_release_all();

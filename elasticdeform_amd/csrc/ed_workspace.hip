@@ -34,11 +34,7 @@ struct HintSlot {
     bool tried = false;
 };
 std::map<std::pair<int, hipStream_t>, HintSlot> g_hints;      // (std::map: addresses are stable)
-struct SideSlot {
-    SideLane lane;
-    bool tried = false;
-};
-std::map<std::pair<int, hipStream_t>, SideSlot> g_sides;      // (std::map: addresses are stable; never erased)
+std::map<std::pair<int, hipStream_t>, GeoBuffer> g_geo;       // (std::map: addresses are stable; never erased)
 // one host-side lock per (device, stream); entries are never erased, so the pointers stay valid
 std::map<std::pair<int, hipStream_t>, std::unique_ptr<std::recursive_mutex>> g_stream_locks;
 }  // namespace
@@ -134,53 +130,28 @@ void* workspace_reserve(hipStream_t stream, size_t bytes, hipError_t* err)
     return b.ptr;
 }
 
-SideLane* side_lane(hipStream_t stream)
+GeoBuffer* geo_buffer(hipStream_t stream)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess)
         return nullptr;
     std::lock_guard<std::mutex> lock(g_mutex);
-    SideSlot& sl = g_sides[std::make_pair(dev, stream)];
-    if (!sl.tried) {
-        sl.tried = true;
-        hipStream_t s2 = nullptr;
-        hipEvent_t e1 = nullptr, e2 = nullptr;
-        // (default priority: at the lowest one the general-tile kernel was starved until the class-A kernel had finished,
-        // 110 -> 167 us)
-        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess) {
-            sl.lane.stream = s2;
-            sl.lane.fork = e1;
-            sl.lane.join = e2;
-            sl.lane.usable = true;
-        } else {
-            (void)hipGetLastError();
-            if (e1)
-                (void)hipEventDestroy(e1);
-            if (s2)
-                (void)hipStreamDestroy(s2);
-        }
-    }
-    return &sl.lane;
+    return &g_geo[std::make_pair(dev, stream)];
 }
 
-void* geo_reserve(hipStream_t stream, SideLane* lane, size_t bytes, hipError_t* err)
+void* geo_reserve(hipStream_t stream, GeoBuffer* geo, size_t bytes, hipError_t* err)
 {
     *err = hipSuccess;
     std::lock_guard<std::mutex> lock(g_mutex);
-    if (lane->geo_ptr && lane->geo_cap >= bytes)
-        return lane->geo_ptr;
+    if (geo->ptr && geo->cap >= bytes)
+        return geo->ptr;
     hipError_t e = hipSuccess;
-    if (lane->geo_ptr) {
-        // kernels of earlier calls (either stream) may still be using the old buffer
-        e = hipStreamSynchronize(stream);
-        if (e == hipSuccess && lane->stream)
-            e = hipStreamSynchronize(lane->stream);
+    if (geo->ptr) {
+        e = hipStreamSynchronize(stream);        // kernels of earlier calls may still be using the old buffer
         if (e == hipSuccess)
-            e = hipFree(lane->geo_ptr);
-        lane->geo_ptr = nullptr;
-        lane->geo_cap = 0;
+            e = hipFree(geo->ptr);
+        geo->ptr = nullptr;
+        geo->cap = 0;
         if (e != hipSuccess) {
             *err = e;
             return nullptr;
@@ -188,20 +159,20 @@ void* geo_reserve(hipStream_t stream, SideLane* lane, size_t bytes, hipError_t* 
     }
     size_t want = bytes + bytes / 4;
     want = (want + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    e = hipMalloc(&lane->geo_ptr, want);
+    e = hipMalloc(&geo->ptr, want);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        lane->geo_ptr = nullptr;
+        geo->ptr = nullptr;
         *err = e;
         return nullptr;
     }
-    lane->geo_cap = want;
-    e = hipMemsetAsync(lane->geo_ptr, 0, 4096, stream);
+    geo->cap = want;
+    e = hipMemsetAsync(geo->ptr, 0, 4096, stream);
     if (e != hipSuccess) {
         *err = e;
         return nullptr;
     }
-    return lane->geo_ptr;
+    return geo->ptr;
 }
 
 void* keep_reserve(hipStream_t stream, size_t bytes, KeepKey** key, hipError_t* err)
@@ -393,14 +364,13 @@ void workspace_release_all()
         kv.second.cap = 0;
         kv.second.key = KeepKey();       // (entries stay: callers may hold the key's address)
     }
-    for (auto& kv : g_sides) {
-        if (kv.second.lane.geo_ptr && hipSetDevice(kv.first.first) == hipSuccess) {
+    for (auto& kv : g_geo) {
+        if (kv.second.ptr && hipSetDevice(kv.first.first) == hipSuccess) {
             (void)hipDeviceSynchronize();
-            (void)hipFree(kv.second.lane.geo_ptr);
+            (void)hipFree(kv.second.ptr);
         }
-        kv.second.lane.geo_ptr = nullptr;
-        kv.second.lane.geo_cap = 0;
-        // (the second stream and its events stay)
+        kv.second.ptr = nullptr;
+        kv.second.cap = 0;             // (entries and their parity stay: callers may hold the address)
     }
     for (auto& kv : g_hints) {
         if (kv.second.h.host && hipSetDevice(kv.first.first) == hipSuccess) {

@@ -49,20 +49,100 @@ int dtype_size(int dt)
 
 int64_t iabs64(int64_t v) { return v < 0 ? -v : v; }
 
-// Geometry shared by every input of a call (deform.c:381-391,439-451,771-776); with
-// EDHIP_FLAG_RAW_DISPLACEMENT the control grid is prefiltered into the head of the workspace.
-// zero_ptr / zero_bytes / zero_done: a gradient block the grid-prefilter launch may clear on its spare workgroups
-// (*zero_done says whether it did: only a RAW_DISPLACEMENT call that really launches the prefilter)
-// defer: the caller enqueues the grid prefilter itself (edhip_deform: the tables kernel of the tile path does it in its
-// own launch) -- *defer gets the parameters, *defer_stamp what the stream's stamp becomes once the filter is enqueued;
-// defer->total stays 0 when there is nothing to filter (no RAW_DISPLACEMENT, or the filtered copy is still there)
-int make_geometry(const edhip_array* displacement, const int64_t* in_len, const int64_t* out_len,
-                  const int64_t* output_offset, int naxis, const double* affine, uint32_t flags,
-                  hipStream_t stream, ed::GridGeom& g, char* err, size_t errlen, char* zero_ptr = nullptr,
-                  long long zero_bytes = 0, bool* zero_done = nullptr, ed::GridPrefilter* defer = nullptr,
-                  ed::GridStamp* defer_stamp = nullptr, bool f64_volumes = false)
+// ---- the checks the entry points share: each returns EDHIP_OK or the refusal, with its message in err --------------
+int check_naxis(int naxis, char* err, size_t errlen)
 {
-    using namespace ed;
+    if (naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > ed::kMaxAxes)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
+                    "more than %d deformed axes are not supported on the GPU", ed::kMaxAxes);
+    return EDHIP_OK;
+}
+
+// the control grid: (naxis, ncp_0, ...), a known dtype, no empty axis; *points (if wanted): its number of values
+int check_displacement(const edhip_array* d, int naxis, int64_t* points, char* err, size_t errlen)
+{
+    if (!d || d->ndim != naxis + 1 || d->shape[0] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (!dtype_ok(d->dtype))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    int64_t total = 1;
+    for (int k = 0; k <= naxis; ++k) {
+        if (d->shape[k] <= 0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+        total *= d->shape[k];
+    }
+    if (points)
+        *points = total;
+    return EDHIP_OK;
+}
+
+// the checks of _deform_grid.c:121-255 on the input/output pairs of edhip_deform and of its gradients (float_only:
+// floating-point volumes only -- the derivative of an integer volume's rounded result is not defined)
+int check_pairs(const edhip_array* inputs, const edhip_array* outputs, int ninputs, int naxis, const int32_t* axis,
+                const int32_t* orders, const int32_t* modes, const double* cvals, bool float_only, char* err,
+                size_t errlen)
+{
+    if (!inputs || !outputs || ninputs <= 0 || ninputs > EDHIP_MAX_INPUTS)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid number of inputs/outputs");
+    if (!axis || !orders || !modes || !cvals)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (const int st = check_naxis(naxis, err, errlen))
+        return st;
+    for (int i = 0; i < ninputs; ++i) {
+        const edhip_array& in = inputs[i];
+        const edhip_array& out = outputs[i];
+        if (in.ndim != out.ndim)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "input and output dimensions should match");
+        if (in.ndim < 1 || in.ndim > EDHIP_MAX_DIMS)
+            return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions",
+                        EDHIP_MAX_DIMS);
+        const bool floats = (in.dtype == EDHIP_F32 || in.dtype == EDHIP_F64) &&
+                            (out.dtype == EDHIP_F32 || out.dtype == EDHIP_F64);
+        if (!dtype_ok(in.dtype) || !dtype_ok(out.dtype) || (float_only && !floats))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+        for (int j = 0; j < naxis; ++j) {
+            const int a = axis[i * naxis + j];
+            if (a < 0 || a >= in.ndim)
+                return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
+            if (in.shape[a] != inputs[0].shape[axis[j]])
+                return fail(err, errlen, EDHIP_ERR_INVALID, "all inputs should have the same size");
+            if (out.shape[a] != outputs[0].shape[axis[j]])
+                return fail(err, errlen, EDHIP_ERR_INVALID, "all outputs should have the same size");
+        }
+        if (orders[i] < 0 || orders[i] > 5)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "spline order not supported");
+        if (modes[i] < 0 || modes[i] > 4)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
+    }
+    return EDHIP_OK;
+}
+
+// deformed extents of an input and an output
+void deformed_lengths(const edhip_array& in0, const edhip_array& out0, int naxis, const int32_t* axis,
+                      int64_t* in_len, int64_t* out_len)
+{
+    for (int k = 0; k < naxis; ++k) {
+        in_len[k] = in0.shape[axis[k]];
+        out_len[k] = out0.shape[axis[k]];
+    }
+}
+
+// sample b of a strided batch
+edhip_array sample(const edhip_array& a, int b, int64_t bstride)
+{
+    edhip_array s = a;
+    s.data = (char*)a.data + (int64_t)b * bstride;
+    return s;
+}
+
+// Geometry shared by every input of a call (deform.c:381-391,439-451,771-776).  Host arithmetic only: nothing is
+// launched or reserved; g.disp is the caller's grid (a raw one is staged by stage_raw_grid).
+int fill_geometry(const edhip_array* displacement, const int64_t* in_len, const int64_t* out_len,
+                  const int64_t* output_offset, int naxis, const double* affine, ed::GridGeom& g, char* err,
+                  size_t errlen)
+{
     memset(&g, 0, sizeof(g));
     g.naxis = naxis;
     g.has_affine = affine != nullptr;
@@ -82,77 +162,106 @@ int make_geometry(const edhip_array* displacement, const int64_t* in_len, const 
     }
     for (int k = 0; k <= naxis; ++k)
         g.disp_stride[k] = displacement->stride_bytes[k];
-    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT) {
-        // prefilter the raw control grid into the head of the stream's workspace (one launch)
-        int64_t total = 1;
-        for (int k = 0; k <= naxis; ++k)
-            total *= displacement->shape[k];
-        if (total > 4096)
-            return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
-                        "raw displacement grids are limited to 4096 points");
-        // reserve everything this call can need now: a later, larger request would move the buffer
-        // and lose the grid
-        hipError_t e = hipSuccess;
-        void* ws = workspace_reserve(stream, deform_tile_workspace_bytes(g, 1, f64_volumes), &e);
-        if (!ws)
-            return hip_fail(err, errlen, e, "scratch allocation");
-        GridPrefilter gp;
-        memset(&gp, 0, sizeof(gp));
-        gp.in = (const char*)displacement->data;
-        gp.out = (char*)ws;
-        gp.dtype = displacement->dtype;
-        gp.elem_size = dtype_size(displacement->dtype);
-        gp.ndim = naxis + 1;
-        gp.total = (int)total;
-        gp.pole = -0.267949192431122706472553658494127633;      // order 3, SciPy's literal
-        gp.gain = (1.0 - gp.pole) * (1.0 - 1.0 / gp.pole);
-        int64_t stride = gp.elem_size;
-        for (int k = naxis; k >= 0; --k) {
-            gp.shape[k] = (int)displacement->shape[k];
-            gp.stride_bytes[k] = displacement->stride_bytes[k];
-            gp.pole_pow[k] = std::pow(gp.pole, (double)(gp.shape[k] - 1));
-            g.disp_stride[k] = stride;
-            stride *= gp.shape[k];
-        }
-        // (EDHIP_FLAG_GRID_STAYS: the previous call's filtered copy of this very grid is still there)
-        GridStamp* stamp = grid_stamp(stream);
-        GridStamp now;
-        now.raw = displacement->data;
-        now.ws = ws;
-        now.generation = workspace_generation(stream);
-        now.dtype = displacement->dtype;
-        now.ndim = naxis + 1;
-        for (int k = 0; k <= naxis; ++k) {
-            now.shape[k] = displacement->shape[k];
-            now.stride[k] = displacement->stride_bytes[k];
-        }
-        const bool stays = (flags & EDHIP_FLAG_GRID_STAYS) && stamp->raw == now.raw && stamp->ws == now.ws &&
-                           stamp->generation == now.generation &&
-                           stamp->dtype == now.dtype && stamp->ndim == now.ndim &&
-                           memcmp(stamp->shape, now.shape, sizeof(now.shape)) == 0 &&
-                           memcmp(stamp->stride, now.stride, sizeof(now.stride)) == 0;
-        if (!stays && defer && defer_stamp) {
-            *stamp = GridStamp();
-            *defer = gp;
-            *defer_stamp = now;
-        } else if (!stays) {
-            *stamp = GridStamp();
-            if (zero_ptr && zero_done && ((uintptr_t)zero_ptr & 15) == 0) {
-                gp.zero_ptr = zero_ptr;
-                gp.zero_bytes = zero_bytes;
-                *zero_done = true;
-            }
-            e = launch_grid_prefilter(gp, stream);
-            if (e != hipSuccess)
-                return hip_fail(err, errlen, e, "grid prefilter launch");
-            *stamp = now;
-        }
-        g.disp = (const char*)ws;
-    }
     if (affine)
         for (int k = 0; k < naxis * (naxis + 1); ++k)
             g.affine[k] = affine[k];
     return EDHIP_OK;
+}
+
+// A raw grid's order-3 prefilter that has not been enqueued yet (gp.total == 0: nothing to filter) and what the
+// stream's stamp becomes once it is.
+struct PendingGrid {
+    ed::GridPrefilter gp;
+    ed::GridStamp stamp;
+};
+
+// EDHIP_FLAG_RAW_DISPLACEMENT: the control grid is prefiltered into the head of the stream's workspace, where g.disp
+// then points.  The filtered copy of this very grid may still be there (EDHIP_FLAG_GRID_STAYS and a matching stamp);
+// otherwise the one-workgroup prefilter is launched here -- or, with `defer`, left to the caller (edhip_deform: the
+// tables kernel of the tile path filters the grid inside its own launch).  f64_volumes: see deform_tile_workspace_bytes.
+int stage_raw_grid(const edhip_array* displacement, uint32_t flags, hipStream_t stream, bool f64_volumes,
+                   ed::GridGeom& g, PendingGrid* defer, char* err, size_t errlen)
+{
+    using namespace ed;
+    const int naxis = g.naxis;
+    int64_t total = 1;
+    for (int k = 0; k <= naxis; ++k)
+        total *= displacement->shape[k];
+    if (total > 4096)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
+                    "raw displacement grids are limited to 4096 points");
+    // reserve everything this call can need now: a later, larger request would move the buffer
+    // and lose the grid
+    hipError_t e = hipSuccess;
+    void* ws = workspace_reserve(stream, deform_tile_workspace_bytes(g, 1, f64_volumes), &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    PendingGrid now;
+    GridPrefilter& gp = now.gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.in = (const char*)displacement->data;
+    gp.out = (char*)ws;
+    gp.dtype = displacement->dtype;
+    gp.elem_size = dtype_size(displacement->dtype);
+    gp.ndim = naxis + 1;
+    gp.total = (int)total;
+    gp.pole = -0.267949192431122706472553658494127633;      // order 3, SciPy's literal
+    gp.gain = (1.0 - gp.pole) * (1.0 - 1.0 / gp.pole);
+    int64_t stride = gp.elem_size;
+    for (int k = naxis; k >= 0; --k) {
+        gp.shape[k] = (int)displacement->shape[k];
+        gp.stride_bytes[k] = displacement->stride_bytes[k];
+        gp.pole_pow[k] = std::pow(gp.pole, (double)(gp.shape[k] - 1));
+        g.disp_stride[k] = stride;
+        stride *= gp.shape[k];
+    }
+    g.disp = (const char*)ws;
+    now.stamp.raw = displacement->data;
+    now.stamp.ws = ws;
+    now.stamp.generation = workspace_generation(stream);
+    now.stamp.dtype = displacement->dtype;
+    now.stamp.ndim = naxis + 1;
+    for (int k = 0; k <= naxis; ++k) {
+        now.stamp.shape[k] = displacement->shape[k];
+        now.stamp.stride[k] = displacement->stride_bytes[k];
+    }
+    GridStamp* stamp = grid_stamp(stream);
+    if ((flags & EDHIP_FLAG_GRID_STAYS) && stamp->raw == now.stamp.raw && stamp->ws == now.stamp.ws &&
+        stamp->generation == now.stamp.generation && stamp->dtype == now.stamp.dtype &&
+        stamp->ndim == now.stamp.ndim && memcmp(stamp->shape, now.stamp.shape, sizeof(stamp->shape)) == 0 &&
+        memcmp(stamp->stride, now.stamp.stride, sizeof(stamp->stride)) == 0)
+        return EDHIP_OK;
+    *stamp = GridStamp();
+    if (defer) {
+        *defer = now;
+        return EDHIP_OK;
+    }
+    e = launch_grid_prefilter(gp, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "grid prefilter launch");
+    *stamp = now.stamp;
+    return EDHIP_OK;
+}
+
+// which kernels take one input/output pair of edhip_deform
+enum Route { kRouteExact, kRouteFast, kRouteTile, kRouteLabel, kRouteInt };
+
+Route pick_route(const ed::GridGeom& g, const ed::IOView& v, int in_dtype, int out_dtype, uint32_t flags,
+                 int gradient)
+{
+    using namespace ed;
+    if (flags & EDHIP_FLAG_EXACT)
+        return kRouteExact;
+    const bool floats = in_dtype == EDHIP_F32 || in_dtype == EDHIP_F64;
+    if (((flags & EDHIP_FLAG_FAST) || (floats && out_dtype == in_dtype)) && deform_fast_supported(g, v, gradient))
+        return deform_tile_supported(g, v, gradient != 0) ? kRouteTile : kRouteFast;
+    // order-0 label maps of any dtype: bit-equal to the exact kernels, so AUTO takes it too
+    if (!floats && deform_label_supported(g, v, gradient))
+        return kRouteLabel;
+    // 8- / 16-bit integer volumes, orders 1-5: bit-equal as well (near-tie voxels redone exactly)
+    if (deform_int_supported(g, v, gradient))
+        return kRouteInt;
+    return kRouteExact;
 }
 
 // One input/output pair as the kernels see it: strides of the deformed axes, the non-deformed
@@ -297,45 +406,10 @@ int edhip_deform(int gradient, int ninputs, const edhip_array* inputs,
     StreamGuard guard(stream);      // the stream's scratch is ours until every launch is enqueued
     if (err && errlen)
         err[0] = 0;
-    // ---- the checks of _deform_grid.c:121-255 -------------------------------------------------
-    if (!inputs || !outputs || ninputs <= 0 || ninputs > EDHIP_MAX_INPUTS)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid number of inputs/outputs");
-    if (!axis || !orders || !modes || !cvals || naxis < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > kMaxAxes)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
-                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
-    for (int i = 0; i < ninputs; ++i) {
-        const edhip_array& in = inputs[i];
-        const edhip_array& out = outputs[i];
-        if (in.ndim != out.ndim)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "input and output dimensions should match");
-        if (in.ndim < 1 || in.ndim > EDHIP_MAX_DIMS)
-            return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions",
-                        EDHIP_MAX_DIMS);
-        if (!dtype_ok(in.dtype) || !dtype_ok(out.dtype))
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-        for (int j = 0; j < naxis; ++j) {
-            const int a = axis[i * naxis + j];
-            if (a < 0 || a >= in.ndim)
-                return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
-            if (in.shape[a] != inputs[0].shape[axis[j]])
-                return fail(err, errlen, EDHIP_ERR_INVALID, "all inputs should have the same size");
-            if (out.shape[a] != outputs[0].shape[axis[j]])
-                return fail(err, errlen, EDHIP_ERR_INVALID, "all outputs should have the same size");
-        }
-        if (orders[i] < 0 || orders[i] > 5)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "spline order not supported");
-        if (modes[i] < 0 || modes[i] > 4)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
-    }
-    if (!displacement || displacement->ndim != naxis + 1 || displacement->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    for (int k = 0; k <= naxis; ++k)
-        if (displacement->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (int st = check_pairs(inputs, outputs, ninputs, naxis, axis, orders, modes, cvals, false, err, errlen))
+        return st;
+    if (int st = check_displacement(displacement, naxis, nullptr, err, errlen))
+        return st;
 
     // EDHIP_FLAG_ZERO_GRADIENT: the dense blocks to clear (checked for every input before anything is enqueued)
     const bool zero = gradient && (flags & EDHIP_FLAG_ZERO_GRADIENT);
@@ -347,42 +421,42 @@ int edhip_deform(int gradient, int ninputs, const edhip_array* inputs,
                 return fail(err, errlen, EDHIP_ERR_INVALID, "EDHIP_FLAG_ZERO_GRADIENT needs dense gradient arrays");
     }
     // ---- shared geometry ------------------------------------------------------------------------
-    // (a RAW_DISPLACEMENT call filters the control grid here, in one workgroup: the spare workgroups of that launch
-    // clear the first gradient block -- cleared[0] -- instead of the tables launch further down)
     GridGeom g;
-    bool cleared[EDHIP_MAX_INPUTS] = {};
-    // The grid prefilter of a RAW_DISPLACEMENT call is not launched here: the tile path's tables kernel filters the
-    // grid inside its own launch (DeformBatch::gridpf); every other route gets the one-workgroup launch in front of
-    // it (grid_now: its spare workgroups clear the first gradient block).
-    GridPrefilter gpf;
-    GridStamp gpf_stamp;
-    memset(&gpf, 0, sizeof(gpf));
     {
         int64_t in_len[kMaxAxes], out_len[kMaxAxes];
-        for (int k = 0; k < naxis; ++k) {
-            in_len[k] = inputs[0].shape[axis[k]];
-            out_len[k] = outputs[0].shape[axis[k]];
-        }
+        deformed_lengths(inputs[0], outputs[0], naxis, axis, in_len, out_len);
+        if (int st = fill_geometry(displacement, in_len, out_len, output_offset, naxis, affine, g, err, errlen))
+            return st;
+    }
+    // Two facts about the call's progress, kept here and nowhere else:
+    //   grid.gp.total > 0   the prefilter of a RAW_DISPLACEMENT grid is still to be enqueued.  The tables launch of the
+    //                       tile / label / integer routes filters the grid itself where its LDS holds it; every other
+    //                       launch gets the one-workgroup prefilter in front of it (grid_now).
+    //   cleared[i]          the gradient block of input i has been cleared (ZERO_GRADIENT).  The spare workgroups of
+    //                       grid_now clear block 0, those of the tile route's tables launch an aligned block i;
+    //                       everything else is cleared by a memset in front of the scatter (clear_now).
+    PendingGrid grid;
+    memset(&grid.gp, 0, sizeof(grid.gp));
+    bool cleared[EDHIP_MAX_INPUTS] = {};
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT) {
         bool f64_volumes = false;
         for (int i = 0; i < ninputs; ++i)
             f64_volumes = f64_volumes || inputs[i].dtype == EDHIP_F64;
-        const int st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine, flags,
-                                     stream, g, err, errlen, nullptr, 0, nullptr, &gpf, &gpf_stamp, f64_volumes);
-        if (st != EDHIP_OK)
+        if (int st = stage_raw_grid(displacement, flags, stream, f64_volumes, g, &grid, err, errlen))
             return st;
     }
     auto grid_now = [&]() -> hipError_t {
-        if (gpf.total <= 0)
+        if (grid.gp.total <= 0)
             return hipSuccess;
         if (zero && zero_bytes[0] > 0 && !cleared[0] && ((uintptr_t)zero_ptr[0] & 15) == 0) {
-            gpf.zero_ptr = zero_ptr[0];
-            gpf.zero_bytes = zero_bytes[0];
+            grid.gp.zero_ptr = zero_ptr[0];
+            grid.gp.zero_bytes = zero_bytes[0];
             cleared[0] = true;
         }
-        const hipError_t e = launch_grid_prefilter(gpf, stream);
-        gpf.total = 0;
+        const hipError_t e = launch_grid_prefilter(grid.gp, stream);
+        grid.gp.total = 0;
         if (e == hipSuccess)
-            *grid_stamp(stream) = gpf_stamp;
+            *grid_stamp(stream) = grid.stamp;
         return e;
     };
     auto clear_now = [&](int i) -> hipError_t {
@@ -431,106 +505,81 @@ int edhip_deform(int gradient, int ninputs, const edhip_array* inputs,
             continue;
         }
 
-        bool use_fast;
-        if (flags & EDHIP_FLAG_EXACT)
-            use_fast = false;
-        else if (flags & EDHIP_FLAG_FAST)
-            use_fast = deform_fast_supported(g, v, gradient);
-        else
-            use_fast = (in.dtype == EDHIP_F32 || in.dtype == EDHIP_F64) && out.dtype == in.dtype &&
-                       deform_fast_supported(g, v, gradient);
-        // order-0 label maps of any dtype: bit-equal to the exact kernels, so AUTO takes it too
-        const bool use_label = !(flags & EDHIP_FLAG_EXACT) && !use_fast && in.dtype != EDHIP_F32 &&
-                               in.dtype != EDHIP_F64 && deform_label_supported(g, v, gradient);
-        // 8- / 16-bit integer volumes, orders 1-5: bit-equal as well (near-tie voxels redone exactly)
-        const bool use_int = !(flags & EDHIP_FLAG_EXACT) && !use_fast && !use_label && deform_int_supported(g, v, gradient);
-        hipError_t e = hipSuccess;
-        const bool tile = !use_label && !use_int && use_fast && deform_tile_supported(g, v, gradient != 0);
-        // (label maps and the integer fast path run the tables kernel of the tile path as well: it filters a raw grid)
-        DeformBatch lone;
-        lone.nbatch = 1;
-        lone.in_bstride = lone.out_bstride = lone.disp_bstride = 0;
-        // (the tables launch filters a raw grid in LDS next to its plane slab: only where both fit -- a flat grid of
-        // 1342-1365 points would pass 64 KiB with the kernel's static LDS; such a grid gets the one-workgroup launch first)
-        const bool gpf_in_tables = gpf.total > 0 && !ed_env("EDHIP_GRIDPF_SEPARATE") &&
-                                   8 * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)gpf.total) <= 60 * 1024;
-        lone.gridpf = (gpf_in_tables && (use_label || use_int)) ? &gpf : nullptr;
-        if (!tile && !lone.gridpf)
-            e = grid_now();
-        if (e == hipSuccess && zero && !tile)
-            e = clear_now(i);
-        if (e != hipSuccess)
-            ;
-        else if (use_label || use_int) {
-            e = use_label ? launch_deform_label(g, v, stream, &lone) : launch_deform_int(g, v, stream, &lone);
-            if (lone.gridpf_done) {
-                gpf.total = 0;
-                *grid_stamp(stream) = gpf_stamp;
-            } else if (lone.gridpf && e == hipSuccess) {
-                e = hipErrorUnknown;       // (cannot happen: every route of the label / integer paths starts with the tables launch)
-            }
-        }
-        else if (!use_fast)
-            e = launch_deform_exact(g, v, gradient != 0, stream);
-        else if (tile) {
-            DeformBatch one;
-            one.nbatch = 1;
-            one.in_bstride = one.out_bstride = one.disp_bstride = 0;
-            one.box_mode = (!gradient && (flags & EDHIP_FLAG_KEEP_BOXES)) ? 1
-                           : ((gradient && (flags & EDHIP_FLAG_USE_BOXES)) ? 2 : 0);
-            one.disp_id = displacement->data;
-            one.raw = (flags & EDHIP_FLAG_RAW_DISPLACEMENT) ? 1 : 0;
-            one.strong = (flags & EDHIP_FLAG_STRONG_FIELD) ? 1 : 0;
-            one.gridpf = gpf_in_tables ? &gpf : nullptr;
-            if (!one.gridpf && grid_now() != hipSuccess)
-                return fail(err, errlen, EDHIP_ERR_DEVICE, "grid prefilter launch");
+        const Route route = pick_route(g, v, in.dtype, out.dtype, flags, gradient);
+        const bool tile = route == kRouteTile;
+        DeformBatch db;
+        db.nbatch = 1;
+        db.in_bstride = db.out_bstride = db.disp_bstride = 0;
+        if (tile) {
             // (several inputs share the geometry: the boxes are those of the last forward launch,
             // which is what a gradient call with the same inputs reads them for)
-            // The tile path clears the block inside its tables launch -- when its start is 16-byte aligned.  A
-            // block it cannot take is cleared HERE, in front of the scatter (it used to be cleared behind a
-            // launch that returned success with zero_done unset: the computed gradient was wiped).
-            hipError_t ce = hipSuccess;
-            if (zero && !cleared[i]) {
-                if (((uintptr_t)zero_ptr[i] & 15) == 0) {
-                    one.zero_ptr = zero_ptr[i];
-                    one.zero_bytes = zero_bytes[i];
-                } else {
-                    ce = clear_now(i);
-                }
-            }
-            e = ce == hipSuccess ? launch_deform_tile(g, v, gradient != 0, stream, &one) : ce;
-            if (one.gridpf_done) {
-                gpf.total = 0;
-                *grid_stamp(stream) = gpf_stamp;
-            }
-            if (out16 && e == hipErrorNotSupported) {
-                (void)hipGetLastError();
-                return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "16-bit output next to a float32 volume: outside the level-1 tile kernels");
-            }
-            if (e == hipErrorNotSupported) {
-                // (a wide control grid the level-1 kernels declined -- batches, layouts: nothing was launched, the
-                // row kernel takes the call; the gradient block is cleared below if the tile path has not done it)
-                (void)hipGetLastError();
-                if (grid_now() != hipSuccess)
-                    return fail(err, errlen, EDHIP_ERR_DEVICE, "grid prefilter launch");
-                if (zero && !cleared[i] && clear_now(i) != hipSuccess)
-                    return fail(err, errlen, EDHIP_ERR_DEVICE, "clearing the gradient arrays failed");
-                e = launch_deform_fast(g, v, gradient != 0, stream);
-            }
-            // (a tile path that declined the call -- or served it on a route without the tables' fill -- has
-            // not touched the block: cleared now, and whoever takes the call next finds it cleared)
-            // (zero_done unset behind an aligned block: the tables launch -- which precedes every scatter of the
-            // tile path -- was not made, so nothing has been added to the block yet)
-            if (zero && one.zero_ptr && one.zero_done)
-                cleared[i] = true;
-            if (zero && one.zero_ptr && !one.zero_done && (e == hipSuccess || e == hipErrorNotSupported)) {
-                const hipError_t c2 = clear_now(i);
-                if (e == hipSuccess)
-                    e = c2;
+            db.box_mode = (!gradient && (flags & EDHIP_FLAG_KEEP_BOXES)) ? 1
+                          : ((gradient && (flags & EDHIP_FLAG_USE_BOXES)) ? 2 : 0);
+            db.disp_id = displacement->data;
+            db.raw = (flags & EDHIP_FLAG_RAW_DISPLACEMENT) ? 1 : 0;
+            db.strong = (flags & EDHIP_FLAG_STRONG_FIELD) ? 1 : 0;
+        }
+        // ---- in front of the launch: the grid filtered or handed to the tables launch, the block cleared or handed
+        //      to it.  (The tables launch -- the label and integer routes run the tile path's -- filters a raw grid in
+        //      LDS next to its plane slab: only where both fit.  A flat grid of 1342-1365 points would pass 64 KiB with
+        //      the kernel's static LDS; such a grid gets the one-workgroup launch first.)
+        if (route != kRouteExact && route != kRouteFast && grid.gp.total > 0 && !ed_env("EDHIP_GRIDPF_SEPARATE") &&
+            8 * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)grid.gp.total) <= 60 * 1024)
+            db.gridpf = &grid.gp;
+        hipError_t e = db.gridpf ? hipSuccess : grid_now();
+        if (e != hipSuccess && tile)
+            return fail(err, errlen, EDHIP_ERR_DEVICE, "grid prefilter launch");
+        if (e == hipSuccess && zero && !cleared[i]) {
+            // (the tile path clears a block inside its tables launch when its start is 16-byte aligned; a block it
+            // cannot take is cleared HERE, in front of the scatter -- never behind a launch)
+            if (tile && ((uintptr_t)zero_ptr[i] & 15) == 0) {
+                db.zero_ptr = zero_ptr[i];
+                db.zero_bytes = zero_bytes[i];
+            } else {
+                e = clear_now(i);
             }
         }
+        // ---- the launch ---------------------------------------------------------------------------------------
+        if (e != hipSuccess)
+            ;
+        else if (route == kRouteLabel || route == kRouteInt) {
+            e = route == kRouteLabel ? launch_deform_label(g, v, stream, &db) : launch_deform_int(g, v, stream, &db);
+            if (e == hipSuccess && db.gridpf && !db.gridpf_done)
+                e = hipErrorUnknown;       // (cannot happen: every route of the label / integer paths starts with the tables launch)
+        }
+        else if (route == kRouteExact)
+            e = launch_deform_exact(g, v, gradient != 0, stream);
+        else if (tile)
+            e = launch_deform_tile(g, v, gradient != 0, stream, &db);
         else
             e = launch_deform_fast(g, v, gradient != 0, stream);
+        // ---- behind it: what the tables launch did on the way --------------------------------------------------
+        if (db.gridpf_done) {
+            grid.gp.total = 0;
+            *grid_stamp(stream) = grid.stamp;
+        }
+        if (tile && e == hipErrorNotSupported) {
+            (void)hipGetLastError();
+            if (out16)
+                return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "16-bit output next to a float32 volume: outside the level-1 tile kernels");
+            // (a wide control grid the level-1 kernels declined -- batches, layouts: the row kernel takes the call, behind
+            // a filtered grid and a cleared block.  A decline behind the tables launch has filtered the grid already;
+            // the block is cleared here whether or not that launch did -- nothing has been added to it yet.)
+            if (grid_now() != hipSuccess)
+                return fail(err, errlen, EDHIP_ERR_DEVICE, "grid prefilter launch");
+            if (zero && !cleared[i] && clear_now(i) != hipSuccess)
+                return fail(err, errlen, EDHIP_ERR_DEVICE, "clearing the gradient arrays failed");
+            e = launch_deform_fast(g, v, gradient != 0, stream);
+        }
+        if (db.zero_done)
+            cleared[i] = true;
+        else if (db.zero_ptr && (e == hipSuccess || e == hipErrorNotSupported)) {
+            // (the tables launch -- which precedes every scatter of the tile path -- was not made, so nothing has
+            // been added to the block yet)
+            const hipError_t c2 = clear_now(i);
+            if (e == hipSuccess)
+                e = c2;
+        }
         if (e != hipSuccess)
             return hip_fail(err, errlen, e, "deform kernel launch");
     }
@@ -588,15 +637,12 @@ int edhip_deform_batch(int gradient, int nbatch, const edhip_array* inputs,
             GridGeom g;
             int64_t in_len[kMaxAxes], out_len[kMaxAxes];
             bool shapes_ok = dtype_ok(displacements[0].dtype);
-            for (int k = 0; k < naxis; ++k) {
-                in_len[k] = inputs[0].shape[axis[k]];
-                out_len[k] = outputs[0].shape[axis[k]];
+            deformed_lengths(inputs[0], outputs[0], naxis, axis, in_len, out_len);
+            for (int k = 0; k < naxis; ++k)
                 shapes_ok = shapes_ok && displacements[0].shape[k + 1] > 0 && in_len[k] >= 2;
-            }
             IOView v;
             if (shapes_ok &&
-                make_geometry(&displacements[0], in_len, out_len, output_offset, naxis, affine, flags, stream, g,
-                              nullptr, 0) == EDHIP_OK &&
+                fill_geometry(&displacements[0], in_len, out_len, output_offset, naxis, affine, g, nullptr, 0) == EDHIP_OK &&
                 make_view(inputs[0], outputs[0], naxis, axis, order, mode, cval, v, nullptr, 0) == EDHIP_OK &&
                 g.nvox > 0 && v.nsteps > 0 && deform_tile_supported(g, v, gradient != 0)) {
                 const hipError_t e = launch_deform_tile(g, v, gradient != 0, stream, &db);
@@ -645,12 +691,9 @@ int edhip_deform_batch_strided(int gradient, int nbatch, const edhip_array* inpu
     edhip_array* disp = in + nbatch;
     edhip_array* out = disp + nbatch;
     for (int b = 0; b < nbatch; ++b) {
-        in[b] = *input0;
-        in[b].data = (char*)input0->data + (int64_t)b * input_batch_stride;
-        disp[b] = *displacement0;
-        disp[b].data = (char*)displacement0->data + (int64_t)b * displacement_batch_stride;
-        out[b] = *output0;
-        out[b].data = (char*)output0->data + (int64_t)b * output_batch_stride;
+        in[b] = sample(*input0, b, input_batch_stride);
+        disp[b] = sample(*displacement0, b, displacement_batch_stride);
+        out[b] = sample(*output0, b, output_batch_stride);
     }
     return edhip_deform_batch(gradient, nbatch, in, disp, output_offset, out, naxis, axis, order, mode, cval,
                               affine, flags, hip_stream, err, errlen);
@@ -679,23 +722,18 @@ int edhip_source_box(const edhip_array* displacement, const int64_t* in_len, con
     StreamGuard guard(stream);
     if (err && errlen)
         err[0] = 0;
-    if (!in_len || !out_len || !box || naxis < 1)
+    if (!in_len || !out_len || !box)
         return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > kMaxAxes)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
-                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
-    if (!displacement || displacement->ndim != naxis + 1 || displacement->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    for (int k = 0; k <= naxis; ++k)
-        if (displacement->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    GridGeom g;
-    const int st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine, flags,
-                                 stream, g, err, errlen);
-    if (st != EDHIP_OK)
+    if (int st = check_naxis(naxis, err, errlen))
         return st;
+    if (int st = check_displacement(displacement, naxis, nullptr, err, errlen))
+        return st;
+    GridGeom g;
+    if (int st = fill_geometry(displacement, in_len, out_len, output_offset, naxis, affine, g, err, errlen))
+        return st;
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        if (int st = stage_raw_grid(displacement, flags, stream, false, g, nullptr, err, errlen))
+            return st;
     hipError_t e = hipSuccess;
     // the box lives in the last bytes of the workspace head (the control grid uses at most 32 KiB)
     char* ws = (char*)workspace_reserve(stream, deform_tile_workspace_bytes(g), &e);
@@ -908,17 +946,9 @@ int edhip_source_window(const edhip_array* displacement, const int64_t* in_len, 
         return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
     if (naxis > 4)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_source_window: up to 4 deformed axes");
-    if (!displacement || displacement->ndim != naxis + 1 || displacement->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    int64_t points = naxis;
-    for (int k = 0; k <= naxis; ++k) {
-        if (displacement->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-        if (k > 0)
-            points *= displacement->shape[k];
-    }
+    int64_t points = 0;
+    if (int st = check_displacement(displacement, naxis, &points, err, errlen))
+        return st;
     if (points > 7680)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_source_window: control grids are limited to 7680 values");
     SourceWindow sw{};
@@ -940,10 +970,11 @@ int edhip_source_window(const edhip_array* displacement, const int64_t* in_len, 
     sw.align = align < 1 ? 1 : align;
     sw.minlen = minlen < 1 ? 1 : minlen;
     GridGeom g;
-    const int st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine, flags,
-                                 stream, g, err, errlen);
-    if (st != EDHIP_OK)
+    if (int st = fill_geometry(displacement, in_len, out_len, output_offset, naxis, affine, g, err, errlen))
         return st;
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        if (int st = stage_raw_grid(displacement, flags, stream, false, g, nullptr, err, errlen))
+            return st;
     hipError_t e = hipSuccess;
     char* ws = (char*)workspace_reserve(stream, deform_tile_workspace_bytes(g), &e);
     if (!ws)
@@ -998,49 +1029,12 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
                       int64_t ddisp_bstride, int64_t dinv_bstride, bool dry, char* err, size_t errlen)
 {
     using namespace ed;
-    // ---- the checks of edhip_deform (_deform_grid.c:121-255), then the dtypes this gradient takes ----------------
-    if (!inputs || !doutputs || ninputs <= 0 || ninputs > EDHIP_MAX_INPUTS)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid number of inputs/outputs");
-    if (!axis || !orders || !modes || !cvals || naxis < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > kMaxAxes)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
-                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
-    for (int i = 0; i < ninputs; ++i) {
-        const edhip_array& in = inputs[i];
-        const edhip_array& out = doutputs[i];
-        if (in.ndim != out.ndim)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "input and output dimensions should match");
-        if (in.ndim < 1 || in.ndim > EDHIP_MAX_DIMS)
-            return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions", EDHIP_MAX_DIMS);
-        // floating-point volumes only: the derivative of an integer volume's rounded result is not defined
-        if (!dtype_ok(in.dtype) || !dtype_ok(out.dtype) || (in.dtype != EDHIP_F32 && in.dtype != EDHIP_F64) ||
-            (out.dtype != EDHIP_F32 && out.dtype != EDHIP_F64))
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-        for (int j = 0; j < naxis; ++j) {
-            const int a = axis[i * naxis + j];
-            if (a < 0 || a >= in.ndim)
-                return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
-            if (in.shape[a] != inputs[0].shape[axis[j]])
-                return fail(err, errlen, EDHIP_ERR_INVALID, "all inputs should have the same size");
-            if (out.shape[a] != doutputs[0].shape[axis[j]])
-                return fail(err, errlen, EDHIP_ERR_INVALID, "all outputs should have the same size");
-        }
-        if (orders[i] < 0 || orders[i] > 5)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "spline order not supported");
-        if (modes[i] < 0 || modes[i] > 4)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
-    }
-    if (!displacement || displacement->ndim != naxis + 1 || displacement->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    int64_t points = 1;
-    for (int k = 0; k <= naxis; ++k) {
-        if (displacement->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-        points *= displacement->shape[k];
-    }
+    // ---- the checks of edhip_deform, on floating-point volumes only ----------------------------------------------
+    if (int st = check_pairs(inputs, doutputs, ninputs, naxis, axis, orders, modes, cvals, true, err, errlen))
+        return st;
+    int64_t points = 0;
+    if (int st = check_displacement(displacement, naxis, &points, err, errlen))
+        return st;
     if (!ddisplacement && !dinverse_affine)
         return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
     if (ddisplacement) {
@@ -1069,14 +1063,9 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
             return st;
     }
     int64_t in_len[kMaxAxes], out_len[kMaxAxes];
-    for (int k = 0; k < naxis; ++k) {
-        in_len[k] = inputs[0].shape[axis[k]];
-        out_len[k] = doutputs[0].shape[axis[k]];
-    }
-    const uint32_t gflags = flags & ~(uint32_t)(EDHIP_FLAG_RAW_DISPLACEMENT | EDHIP_FLAG_GRID_STAYS);
+    deformed_lengths(inputs[0], doutputs[0], naxis, axis, in_len, out_len);
     GridGeom g;
-    int st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine, gflags, stream, g, err,
-                           errlen);
+    int st = fill_geometry(displacement, in_len, out_len, output_offset, naxis, affine, g, err, errlen);
     if (st != EDHIP_OK)
         return st;
     if (!dgrad_supported(g))
@@ -1106,8 +1095,8 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
         return hip_fail(err, errlen, e, "scratch allocation");
     if (raw) {
         // the library's order-3 mirror prefilter of the raw grid, into the workspace head (as edhip_deform does)
-        st = make_geometry(displacement, in_len, out_len, output_offset, naxis, affine,
-                           flags & ~(uint32_t)EDHIP_FLAG_GRID_STAYS, stream, g, err, errlen);
+        st = stage_raw_grid(displacement, flags & ~(uint32_t)EDHIP_FLAG_GRID_STAYS, stream, false, g, nullptr, err,
+                            errlen);
         if (st != EDHIP_OK)
             return st;
     }
@@ -1193,18 +1182,14 @@ static int transform_gradient_batch(int nbatch, const edhip_array* input0, int64
     int st = dgrad_impl(1, input0, displacement0, output_offset, doutput0, naxis, axis, &order, &mode, &cval, affine,
                         ddisplacement0, dinverse_affine0, flags, stream, 1, 0, 0, 0, 0, 0, true, err, errlen);
     for (int b = 0; b < nbatch && st == EDHIP_OK; ++b) {
-        edhip_array in = *input0, disp = *displacement0, dout = *doutput0, ddisp, dinv;
-        in.data = (char*)input0->data + (int64_t)b * input_batch_stride;
-        disp.data = (char*)displacement0->data + (int64_t)b * displacement_batch_stride;
-        dout.data = (char*)doutput0->data + (int64_t)b * doutput_batch_stride;
-        if (ddisplacement0) {
-            ddisp = *ddisplacement0;
-            ddisp.data = (char*)ddisplacement0->data + (int64_t)b * ddisplacement_batch_stride;
-        }
-        if (dinverse_affine0) {
-            dinv = *dinverse_affine0;
-            dinv.data = (char*)dinverse_affine0->data + (int64_t)b * dinverse_affine_batch_stride;
-        }
+        const edhip_array in = sample(*input0, b, input_batch_stride);
+        const edhip_array disp = sample(*displacement0, b, displacement_batch_stride);
+        const edhip_array dout = sample(*doutput0, b, doutput_batch_stride);
+        edhip_array ddisp, dinv;
+        if (ddisplacement0)
+            ddisp = sample(*ddisplacement0, b, ddisplacement_batch_stride);
+        if (dinverse_affine0)
+            dinv = sample(*dinverse_affine0, b, dinverse_affine_batch_stride);
         st = dgrad_impl(1, &in, &disp, output_offset, &dout, naxis, axis, &order, &mode, &cval, affine,
                         ddisplacement0 ? &ddisp : nullptr, dinverse_affine0 ? &dinv : nullptr, flags, stream, 1, 0, 0,
                         0, 0, 0, false, err, errlen);
@@ -1289,11 +1274,8 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
         err[0] = 0;
     if (nbatch < 0 || !points0 || !displacement0 || !result0 || !in_len)
         return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
-    if (naxis < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > kMaxAxes)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
-                    "more than %d deformed axes are not supported on the GPU", kMaxAxes);
+    if (int st = check_naxis(naxis, err, errlen))
+        return st;
     if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
         return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_points takes the prefiltered control grid");
     if (points0->ndim != 2 || points0->shape[1] != naxis || points0->shape[0] < 0)
@@ -1329,20 +1311,13 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
         if (affine && !forward_linear)
             return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
     }
-    if (displacement0->ndim != naxis + 1 || displacement0->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement0->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    for (int k = 0; k <= naxis; ++k)
-        if (displacement0->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
     if (nbatch > 65535)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_points: too many samples");
     PointsCall c;
     memset(&c, 0, sizeof(c));
-    // (no EDHIP_FLAG_RAW_DISPLACEMENT: nothing is launched or reserved; refuses extents below 2)
-    int st = make_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, 0, stream, c.g, err, errlen);
-    if (st != EDHIP_OK)
+    if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
         return st;
     if (nbatch == 0 || npts == 0)
         return EDHIP_OK;
@@ -1414,13 +1389,8 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
             return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
     if (mode < 0 || mode > 4)
         return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
-    if (displacement0->ndim != naxis + 1 || displacement0->shape[0] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
-    if (!dtype_ok(displacement0->dtype))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    for (int k = 0; k <= naxis; ++k)
-        if (displacement0->shape[k] <= 0)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid displacement shape");
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
     if (weight0) {
         bool same = weight0->ndim == out.ndim;
         for (int d = 0; same && d < out.ndim; ++d)
@@ -1456,14 +1426,8 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
     memset(&c, 0, sizeof(c));
     {
         int64_t in_len[kMaxAxes], out_len[kMaxAxes];
-        for (int k = 0; k < naxis; ++k) {
-            in_len[k] = in.shape[axis[k]];
-            out_len[k] = out.shape[axis[k]];
-        }
-        // (no EDHIP_FLAG_RAW_DISPLACEMENT: nothing is launched or reserved; refuses deformed extents below 2)
-        const int st = make_geometry(displacement0, in_len, out_len, output_offset, naxis, affine, 0, stream, c.g, err,
-                                     errlen);
-        if (st != EDHIP_OK)
+        deformed_lengths(in, out, naxis, axis, in_len, out_len);
+        if (int st = fill_geometry(displacement0, in_len, out_len, output_offset, naxis, affine, c.g, err, errlen))
             return st;
     }
     int st = make_view(in, out, naxis, axis, 1, mode, cval, c.v, err, errlen);

@@ -1815,6 +1815,53 @@ def test_zero_gradient_flag_clears_dense_accumulators_on_every_route():
                     None, _lib.FLAG_AUTO | _lib.FLAG_RAW_DISPLACEMENT | _lib.FLAG_ZERO_GRADIENT, stream)
 
 
+def test_zero_gradient_flag_clears_an_aligned_and_a_misaligned_block_in_one_call():
+    """One gradient call (EDHIP_FLAG_ZERO_GRADIENT | EDHIP_FLAG_RAW_DISPLACEMENT), two inputs on one geometry, both
+    accumulators pre-filled with garbage: the first is dense and 16-byte aligned -- the spare workgroups of the tables
+    launch clear it, and that launch filters the raw grid -- the second is a dense block 4 bytes into an allocation,
+    which the tables launch cannot take: it is cleared in front of the scatter.  Each must be cleared exactly once,
+    before anything is added: the results are those of the same call on pre-zeroed arrays without the flag (bit for
+    bit if that call repeats its own bits; the scatter adds with float atomics) and within the file's float32
+    gradient bound of the oracle."""
+    from elasticdeform_amd import _lib
+    import importlib
+    dgm = importlib.import_module("elasticdeform_amd.deform_grid")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rng = np.random.default_rng(31)
+    shape = (24, 28, 40)
+    n = int(np.prod(shape))
+    disp = rng.standard_normal((3, 3, 3, 3)) * 1.5
+    dYs = [rng.random(shape).astype(np.float32) for _ in range(2)]
+    d = torch.from_numpy(disp).to(dev)
+    dYd = [torch.from_numpy(a).to(dev) for a in dYs]
+
+    def call(fill, flags):
+        first = torch.full(shape, fill, dtype=torch.float32, device=dev)
+        pool = torch.full((n + 8,), fill, dtype=torch.float32, device=dev)
+        second = pool[1:1 + n].view(shape)
+        assert first.data_ptr() % 16 == 0 and second.data_ptr() % 16 == 4 and second.is_contiguous()
+        _lib.deform(True, [dgm._desc(first), dgm._desc(second)], dgm._desc(d), None, [dgm._desc(a) for a in dYd],
+                    [(0, 1, 2)] * 2, [3, 3], [3, 3], [0.0, 0.0], None, _lib.FLAG_AUTO | _lib.FLAG_RAW_DISPLACEMENT | flags,
+                    stream)
+        return first, second, pool
+
+    plain = call(0.0, 0)
+    again = call(0.0, 0)
+    repeats = all(torch.equal(a, b) for a, b in zip(plain[:2], again[:2]))
+    for garbage in (7.0, float("nan")):
+        got = call(garbage, _lib.FLAG_ZERO_GRADIENT)
+        pool = got[2]
+        assert bool((pool[:1] == garbage).all() if garbage == garbage else torch.isnan(pool[:1]).all())
+        assert bool((pool[1 + n:] == garbage).all() if garbage == garbage else torch.isnan(pool[1 + n:]).all())
+        for i in range(2):
+            if repeats:
+                assert torch.equal(got[i], plain[i]), (garbage, i)
+            w = orc.deform_grid_gradient(dYs[i], disp, order=3, mode="mirror", prefilter=False)
+            truth = orc.deform_grid_gradient(dYs[i].astype(np.float64), disp, order=3, mode="mirror", prefilter=False)
+            _f32_grad_check(got[i].cpu().numpy(), w, truth)
+
+
 # ---- round 5: K1 with sampled tile boxes (csrc/deform_k1.hip) ------------------------------------------------------
 @pytest.mark.parametrize("mode", ["nearest", "wrap", "reflect", "mirror", "constant"])
 def test_k1_general_tiles_every_mode(mode):

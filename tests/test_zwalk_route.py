@@ -90,6 +90,41 @@ def test_strong_fields_halves_and_unfit_tiles(sigma):
     assert err <= 4 * ref_err + 4 * np.finfo(np.float32).eps * scale, (err, ref_err, scale)
 
 
+def _geo_bytes(shape, ncp_z):
+    """what the z-walk route asks of its geometry buffer for one float32 volume (k1z_geo_bytes, csrc/deform_tile.hip):
+    counters | uniforms | z table (48 bytes per output plane) | 168 bytes per 8^3 tile | step offsets | R"""
+    def up64(v):
+        return (v + 63) // 64 * 64
+    tiles = int(np.prod([(s + 7) // 8 for s in shape]))
+    return 4096 + 512 + up64(48 * shape[0]) + up64(tiles * 168) + 4096 * 16 + up64(8 * shape[1] * shape[2] * 4 * ncp_z)
+
+
+def test_geometry_buffer_grows_and_is_reused():
+    """The route's geometry buffer is an allocation of its own per stream, 1 MiB granularity plus 25 % slack, grown
+    behind a drained stream.  From an empty cache: 40 x 48 x 56 with a 5^3 grid asks for 537 472 bytes (a 1 MiB
+    buffer), 96 x 104 x 120 for 2 464 704 (the buffer is freed and a 3 MiB one allocated, its counters cleared), then
+    the small call again inside the large buffer.  All three against the oracle; the third repeats the first's bits."""
+    from elasticdeform_amd import _lib
+    small, large = (40, 48, 56), (96, 104, 120)
+    assert _geo_bytes(small, 5) == 537472 and _geo_bytes(large, 5) == 2464704
+    assert _geo_bytes(small, 5) * 5 // 4 <= 1 << 20 < _geo_bytes(large, 5)
+    rng = np.random.default_rng(21)
+    kw = dict(order=3, mode="mirror")
+    Xs, Xl = rng.random(small).astype(np.float32), rng.random(large).astype(np.float32)
+    ds, dl = rng.standard_normal((3, 5, 5, 5)) * 3.0, rng.standard_normal((3, 5, 5, 5)) * 3.0
+    Xsd, Xld, dsd, dld = (torch.from_numpy(a).cuda() for a in (Xs, Xl, ds, dl))
+    torch.cuda.synchronize()
+    _lib.release_scratch()
+    first = ed.deform_grid(Xsd, dsd, **kw)
+    grown = ed.deform_grid(Xld, dld, **kw)
+    third = ed.deform_grid(Xsd, dsd, **kw)
+    want = orc.deform_grid(Xs, ds, **kw)
+    np.testing.assert_allclose(first.cpu().numpy(), want, **TOL)
+    np.testing.assert_allclose(grown.cpu().numpy(), orc.deform_grid(Xl, dl, **kw), **TOL)
+    np.testing.assert_allclose(third.cpu().numpy(), want, **TOL)
+    assert torch.equal(third, first)
+
+
 def test_batch_and_single_calls_agree():
     """One control grid per sample through the batch entry point (one geometry launch for all samples): the bits of
     the per-sample calls, and the oracle's values."""
