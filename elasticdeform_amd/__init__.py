@@ -18,6 +18,8 @@ reference either) differentiate with respect to the control-point displacement,
 ``deform_grid_affine_gradient`` / ``deform_grid_affine_gradient_batch`` with respect to affine, rotate and zoom.
 ``deform_grid_coordinates`` / ``deform_points`` (and their ``_batch`` forms) map positions through the deformation:
 the coordinate map of ``deform_grid`` at real positions with its Jacobian, and where source points land in the output.
+``deform_grid_coordinates_gradient`` / ``deform_points_gradient`` (and their ``_batch`` forms) are their adjoints: the
+gradient of a loss on mapped points with respect to the points, the displacement and affine / rotate / zoom.
 ``deform_grid_labels`` / ``deform_grid_labels_batch`` resample label maps with linear weights and a per-label vote:
 the argmax of the order-1 deformed one-hot channels without the one-hot volumes.
 """
@@ -28,7 +30,9 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_displacement_gradient_batch, deform_grid_affine_gradient,
                           deform_grid_affine_gradient_batch, AffineGradient, deform_grid_coordinates,
                           deform_points, deform_grid_coordinates_batch, deform_points_batch,
-                          deform_grid_labels, deform_grid_labels_batch)
+                          deform_grid_labels, deform_grid_labels_batch, PointsGradient,
+                          deform_grid_coordinates_gradient, deform_points_gradient,
+                          deform_grid_coordinates_gradient_batch, deform_points_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

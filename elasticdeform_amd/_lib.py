@@ -54,7 +54,8 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_release_scratch', 'edhip_profile_dominant',
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
-           'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels')
+           'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
+           'edhip_deform_points_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -176,6 +177,14 @@ def load():
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
             ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_points_gradient.restype = ctypes.c_int
+        L.edhip_deform_points_gradient.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p,
+            ctypes.c_char_p, ctypes.c_size_t]
         L.edhip_deform_labels.restype = ctypes.c_int
         L.edhip_deform_labels.argtypes = [
             ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
@@ -382,6 +391,27 @@ def deform_points(inverse, nbatch, pts_desc, pts_bstride, disp_desc, disp_bstrid
         int(disp_bstride), in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, lin,
         ctypes.byref(res_desc), int(res_bstride), _ref(jac_desc), int(jac_bstride), _ref(status_desc),
         int(status_bstride), int(max_iter), float(tol), int(flags), ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
+
+
+def deform_points_gradient(inverse, nbatch, pos_desc, pos_bstride, cot_desc, cot_bstride, status_desc, status_bstride,
+                           disp_desc, disp_bstride, in_len, output_offset, inverse_affine, dpts_desc, dpts_bstride,
+                           ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride, flags, stream):
+    """edhip_deform_points_gradient: the adjoint of deform_points().  `pos_desc`: the positions q (inverse true: the
+    solved q), `cot_desc`: dL/dr (inverse true: dL/dq), `status_desc`: inverse only, 0 = not solved.  Results (None =
+    not wanted): the per-point rows into `dpts_desc`, the gradient with respect to the PREFILTERED grid `disp_desc`
+    into `ddisp_desc`, with respect to the inverse map into `dinv_desc` (float64, naxis x naxis+1).  Sample 0's
+    descriptors plus byte strides."""
+    L = load()
+    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    buf = _buf()
+    status = L.edhip_deform_points_gradient(
+        int(bool(inverse)), int(nbatch), ctypes.byref(pos_desc), int(pos_bstride), ctypes.byref(cot_desc),
+        int(cot_bstride), _ref(status_desc), int(status_bstride), ctypes.byref(disp_desc), int(disp_bstride),
+        in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, _ref(dpts_desc),
+        int(dpts_bstride), _ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc), int(dinv_bstride), int(flags),
+        ctypes.c_void_p(stream), buf, 256)
     raise_for_status(status, buf)
 
 

@@ -207,6 +207,38 @@ struct PointsCall {
 constexpr int kPointsLdsValues = 7680;   // control grids up to this many values are staged in LDS (60 KiB of doubles)
 hipError_t launch_deform_points(const PointsCall& c, hipStream_t stream);
 
+// The adjoint of the coordinate map and of its inverse (deform_points_grad.hip): for the cotangents of r(q) (forward) or of
+// q = r^-1(p) (inverse, at the solved q) the per-point rows, the gradient with respect to the prefiltered grid and
+// with respect to the inverse map K.  Sums are 64-bit integer fixed point (order-independent bits).  The call
+// clears its scratch itself (a kernel of its own): [per sample 4 words | per sample naxis (naxis + 1) + values cells | per sample
+// npts x naxis doubles], points_grad_scratch_bytes() bytes from the caller.
+struct PointsGradCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len >= 2 on every axis
+    int inverse;                  // 0: cot = dL/dr(q); 1: cot = dL/dq at the solved q
+    int nbatch;
+    int64_t npts;
+    int64_t disp_bstride;
+    const char* pos;              // (npts, naxis) float32 / float64: q
+    int pos_dtype;
+    int64_t pos_stride[2], pos_bstride;
+    const char* cot;              // (npts, naxis) float32 / float64
+    int cot_dtype;
+    int64_t cot_stride[2], cot_bstride;
+    const unsigned char* status;  // inverse: uint8 (npts), 0 = not solved (contributes nothing); nullptr: all solved
+    int64_t status_stride, status_bstride;
+    char* dpts;                   // (npts, naxis) float32 / float64; nullptr: not wanted
+    int dpts_dtype;
+    int64_t dpts_stride[2], dpts_bstride;
+    char* ddisp;                  // the grid's shape, a floating dtype; nullptr: not wanted
+    int ddisp_dtype;
+    int64_t ddisp_stride[kMaxAxes + 1], ddisp_bstride;
+    char* dK;                     // float64 (naxis, naxis + 1); nullptr: not wanted
+    int64_t dK_stride[2], dK_bstride;
+    char* scratch;
+};
+size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts);
+hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream);
+
 // Label-aware linear resampling of label maps (deform_vote.hip): per output voxel the order-1 weights are summed per
 // distinct label among the 2^naxis source voxels, the label with the largest sum is stored (ties: the smallest label).
 // One thread per (voxel, step), blockIdx.y = sample; no scratch, no synchronisation.  1 to 3 deformed axes, integer

@@ -1355,6 +1355,132 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
     return EDHIP_OK;
 }
 
+// ---- the adjoint of the coordinate map and of its inverse (deform_points_grad.hip) ---------------------------------
+int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* positions0,
+                                 int64_t positions_batch_stride, const edhip_array* cotangent0,
+                                 int64_t cotangent_batch_stride, const edhip_array* status0,
+                                 int64_t status_batch_stride, const edhip_array* displacement0,
+                                 int64_t displacement_batch_stride, const int64_t* in_len,
+                                 const int64_t* output_offset, int naxis, const double* affine,
+                                 const edhip_array* dpoints0, int64_t dpoints_batch_stride,
+                                 const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                 const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                 uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || !positions0 || !cotangent0 || !displacement0 || !in_len)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (int st = check_naxis(naxis, err, errlen))
+        return st;
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        return fail(err, errlen, EDHIP_ERR_INVALID,
+                    "edhip_deform_points_gradient takes the prefiltered control grid");
+    if (!dpoints0 && !ddisplacement0 && !dinverse_affine0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested");
+    if (positions0->ndim != 2 || positions0->shape[1] != naxis || positions0->shape[0] < 0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "positions must have shape (N, naxis)");
+    const int64_t npts = positions0->shape[0];
+    if (cotangent0->ndim != 2 || cotangent0->shape[0] != npts || cotangent0->shape[1] != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "cotangent must have the shape of positions");
+    const auto f32_or_f64 = [](const edhip_array* a) { return a->dtype == EDHIP_F32 || a->dtype == EDHIP_F64; };
+    if (!f32_or_f64(positions0) || !f32_or_f64(cotangent0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    if (status0) {
+        if (!inverse)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the status belongs to the inverse direction");
+        if (status0->ndim != 1 || status0->shape[0] != npts)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "status must have shape (N)");
+        if (status0->dtype != EDHIP_U8)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "status must be uint8");
+    }
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (dpoints0) {
+        if (dpoints0->ndim != 2 || dpoints0->shape[0] != npts || dpoints0->shape[1] != naxis)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dpoints must have the shape of positions");
+        if (!f32_or_f64(dpoints0))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    }
+    if (ddisplacement0) {
+        bool same = ddisplacement0->ndim == displacement0->ndim;
+        for (int k = 0; same && k <= naxis; ++k)
+            same = ddisplacement0->shape[k] == displacement0->shape[k];
+        if (!same)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        const int dt = ddisplacement0->dtype;
+        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
+    }
+    if (dinverse_affine0) {
+        if (dinverse_affine0->ndim != 2 || dinverse_affine0->shape[0] != naxis ||
+            dinverse_affine0->shape[1] != naxis + 1)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
+    if (nbatch > 65535)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_points_gradient: too many samples");
+    PointsGradCall c;
+    memset(&c, 0, sizeof(c));
+    if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    if (nbatch == 0 || (npts == 0 && !ddisplacement0 && !dinverse_affine0))
+        return EDHIP_OK;
+    c.inverse = inverse != 0;
+    c.nbatch = nbatch;
+    c.npts = npts;
+    c.disp_bstride = displacement_batch_stride;
+    c.pos = (const char*)positions0->data;
+    c.pos_dtype = positions0->dtype;
+    c.pos_bstride = positions_batch_stride;
+    c.cot = (const char*)cotangent0->data;
+    c.cot_dtype = cotangent0->dtype;
+    c.cot_bstride = cotangent_batch_stride;
+    for (int k = 0; k < 2; ++k) {
+        c.pos_stride[k] = positions0->stride_bytes[k];
+        c.cot_stride[k] = cotangent0->stride_bytes[k];
+    }
+    if (status0) {
+        c.status = (const unsigned char*)status0->data;
+        c.status_stride = status0->stride_bytes[0];
+        c.status_bstride = status_batch_stride;
+    }
+    if (dpoints0) {
+        c.dpts = (char*)dpoints0->data;
+        c.dpts_dtype = dpoints0->dtype;
+        c.dpts_stride[0] = dpoints0->stride_bytes[0];
+        c.dpts_stride[1] = dpoints0->stride_bytes[1];
+        c.dpts_bstride = dpoints_batch_stride;
+    }
+    if (ddisplacement0) {
+        c.ddisp = (char*)ddisplacement0->data;
+        c.ddisp_dtype = ddisplacement0->dtype;
+        for (int k = 0; k <= naxis; ++k)
+            c.ddisp_stride[k] = ddisplacement0->stride_bytes[k];
+        c.ddisp_bstride = ddisplacement_batch_stride;
+    }
+    if (dinverse_affine0) {
+        c.dK = (char*)dinverse_affine0->data;
+        c.dK_stride[0] = dinverse_affine0->stride_bytes[0];
+        c.dK_stride[1] = dinverse_affine0->stride_bytes[1];
+        c.dK_bstride = dinverse_affine_batch_stride;
+    }
+    // cells, maxima, flags and the per-point u rows: the stream's workspace, behind its grid head
+    StreamGuard guard(stream);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + points_grad_scratch_bytes(c.g, nbatch, npts), &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    c.scratch = ws + kWorkspaceGridBytes;
+    e = launch_deform_points_gradient(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform points gradient launch");
+    return EDHIP_OK;
+}
+
 // ---- label-aware linear resampling of label maps (deform_vote.hip) --------------------------------------------
 int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
                         const edhip_array* displacement0, int64_t displacement_batch_stride,

@@ -1287,7 +1287,9 @@ def deform_grid_coordinates(positions, displacement, X_shape, crop=None, axis=No
 
     float32 / float64 positions keep their dtype (the arithmetic is fp64, a float32 result is rounded once); integer
     positions are taken as float64.  numpy in gives numpy out, otherwise the result is a tensor on the positions'
-    device.  A deformed axis of length 1 gives NaN.  No autograd flows through this call.
+    device.  A deformed axis of length 1 gives NaN.  No autograd flows through this call itself:
+    :func:`deform_grid_coordinates_gradient` is its adjoint and ``elasticdeform_amd.torch.deform_grid_coordinates``
+    the differentiable wrapper.
     """
     r, J, _ = _points_map(positions, displacement, X_shape, crop, axis, affine, rotate, zoom, False, jacobian, 1,
                           1.0, False)
@@ -1312,7 +1314,8 @@ def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=No
     point is then not visible in ``Y``.
 
     dtypes, array families and the length-1 axis as for :func:`deform_grid_coordinates` (nothing converges there).
-    No autograd flows through this call.
+    No autograd flows through this call itself: :func:`deform_points_gradient` is its adjoint and
+    ``elasticdeform_amd.torch.deform_points`` the differentiable wrapper.
     """
     q, _, ok = _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, True, False, max_iter,
                            tol, False)
@@ -1337,6 +1340,191 @@ def deform_points_batch(points, displacements, X_shape, crop=None, axis=None, af
     q, _, ok = _points_map(points, displacements, X_shape, crop, axis, affine, rotate, zoom, True, False, max_iter,
                            tol, True)
     return (q, ok) if return_converged else q
+
+
+# ---- gradients through the coordinate map and its inverse -------------------------------------------------------
+
+PointsGradient = collections.namedtuple('PointsGradient',
+                                        ['points', 'displacement', 'affine', 'rotate', 'zoom', 'inverse_map'])
+
+
+def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, batch,
+                     want_points=True, want_disp=True, want_map=True, max_iter=32, tol=1e-9, positions=None,
+                     converged=None):
+    """The adjoint of _points_map, single call and batch: ONE library call for whatever is wanted.  `cotangent` is
+    dL/dr(q) for the positions q = `points` (forward direction) or dL/dq for q = r^-1(points) (inverse; solved here
+    in float64 through _points_map unless `positions`, the solved q, and optionally its mask `converged` are given).
+    Returns (plan, d points or None, d displacement or None, dK or None): the first two in the family of `points`, dK
+    a float64 tensor (naxis, naxis+1) -- (B, naxis, naxis+1) for a batch -- on the device.  Every argument check
+    runs before the device or the library is touched."""
+    if X_shape is None:
+        raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
+    if inverse and positions is None:
+        if int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError("max_iter should be a positive integer.")
+        if not float(tol) > 0.0:
+            raise ValueError("tol should be positive.")
+    X_shape = tuple(int(v) for v in X_shape)
+    pts = _as_points(points)
+    cot = _as_points(cotangent)
+    if batch:
+        if pts.ndim != 3:
+            raise ValueError("points should have shape (batch, N, naxis).")
+        plan = _batch_plan(_host.ShapeOnly((int(pts.shape[0]),) + X_shape), displacement, 3, 'constant', 0.0, crop,
+                           axis, affine, rotate, zoom)
+    else:
+        plan = _host.cached_plan([_host.ShapeOnly(X_shape)], displacement, 3, 'constant', 0.0, crop, axis, affine,
+                                 rotate, zoom)
+    n = plan.naxis
+    if pts.ndim < 1 or int(pts.shape[-1]) != n:
+        raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
+                         "but their shape is %s." % (n, str(tuple(pts.shape))))
+    if tuple(int(v) for v in cot.shape) != tuple(int(v) for v in pts.shape):
+        raise ValueError("The cotangent should have the shape of the points, %s, but its shape is %s."
+                         % (str(tuple(pts.shape)), str(tuple(cot.shape))))
+    if positions is not None:
+        positions = _as_points(positions)
+        if tuple(int(v) for v in positions.shape) != tuple(int(v) for v in pts.shape):
+            raise ValueError("positions should have the shape of the points, %s, but their shape is %s."
+                             % (str(tuple(pts.shape)), str(tuple(positions.shape))))
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
+    lead = tuple(int(v) for v in pts.shape[:-1])
+    name = _volume_dtype_name(pts)
+    dk_shape = ((lead[0],) if batch else ()) + (n, n + 1)
+    torch = _torch()
+
+    if any(int(d) == 1 for d in plan.deform_shape):
+        # a deformed axis of length 1: no coordinate is defined there, nothing depends on anything
+        dk = None
+        if want_map:
+            dk = torch.zeros(dk_shape, dtype=torch.float64, device=pts.device if torch.is_tensor(pts) else 'cpu')
+        return (plan, _points_fill(pts, lead + (n,), 0.0, name) if want_points else None,
+                _dgrad_zeros(displacement, pts) if want_disp else None, dk)
+
+    device = _device_for([pts, cot, displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        pd = _to_device(pts, device)
+        cd = _to_device(cot, device)
+        dd = _to_device(displacement, device)
+        ok = None
+        if inverse:
+            if positions is None:
+                # solved in float64, so that float32 points give the float64 call's rows, rounded once
+                qd, _, okb = _points_map(pd.to(torch.float64), dd, X_shape, crop, axis, affine, rotate, zoom, True,
+                                         False, max_iter, tol, batch)
+                ok = okb.to(torch.uint8)
+            else:
+                qd = _to_device(positions, device)
+                if converged is not None:
+                    ok = _to_device(converged, device).to(torch.uint8)
+        else:
+            qd = pd
+        if not batch:
+            qd, cd = qd.reshape(-1, n), cd.reshape(-1, n)
+            ok = ok.reshape(-1) if ok is not None else None
+        grid_axes = range(2 if batch else 1, dd.ndim)
+        # the control grid is prefiltered as the forward call prefilters it
+        df = _filter_axes(dd, grid_axes, 3, False, device, stream=stream)
+        rows = torch.empty(tuple(qd.shape), dtype=pd.dtype, device=device) if want_points else None
+        dp = torch.empty(tuple(int(v) for v in dd.shape), dtype=torch.float64, device=device) if want_disp else None
+        dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
+        none = (None, 0)
+        if batch:
+            nb = int(qd.shape[0])
+            (q0, qs), (c0, cs), (d0, ds) = _desc_sample0(qd), _desc_sample0(cd), _desc_sample0(df)
+            (s0, ss) = _desc_sample0(ok) if ok is not None else none
+            (r0, rs) = _desc_sample0(rows) if rows is not None else none
+            (p0, ps) = _desc_sample0(dp) if dp is not None else none
+            (k0, ks) = _desc_sample0(dk) if dk is not None else none
+        else:
+            nb = 1
+            q0, c0, d0 = _desc(qd), _desc(cd), _desc(df)
+            s0, r0, p0, k0 = [_desc(t) if t is not None else None for t in (ok, rows, dp, dk)]
+            qs = cs = ds = ss = rs = ps = ks = 0
+        _lib.deform_points_gradient(inverse, nb, q0, qs, c0, cs, s0, ss, d0, ds, plan.deform_shape,
+                                    plan.output_offset, plan.inverse_affine, r0, rs, p0, ps, k0, ks, 0, stream)
+        out = None
+        if dp is not None:
+            # dD = (order-3 mirror prefilter)^T dP in fp64, rounded once to the result's dtype
+            dp = _filter_axes(dp, grid_axes, 3, True, device, overwrite=True, stream=stream)
+            out = _from_device(dp.to(_result_tensor_dtype(displacement)), pts)
+        if rows is not None:
+            rows = _from_device(rows.reshape(lead + (n,)), pts)
+    return plan, rows, out, dk
+
+
+def _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, numpy_out, batch):
+    result = _affine_result_batch if batch else _affine_result
+    return PointsGradient(rows, ddisp, *result(dk, plan, affine, rotate, zoom, numpy_out))
+
+
+def deform_grid_coordinates_gradient(positions, d_coordinates, displacement, X_shape, crop=None, axis=None,
+                                     affine=None, rotate=None, zoom=None):
+    """
+    Gradient through :func:`deform_grid_coordinates`: for ``L`` with ``d_coordinates = dL / d r`` (the shape of
+    ``positions``, float32 / float64) and ``r = deform_grid_coordinates(positions, displacement, X_shape, ...)``,
+    returns ``PointsGradient(points, displacement, affine, rotate, zoom, inverse_map)``:
+
+    * ``points``: dL / d positions, ``J^T d_coordinates`` per point, in the shape and dtype of the positions (fp64
+      arithmetic, a float32 row is rounded once);
+    * ``displacement``: dL / d displacement (the order-3 prefilter of the grid included), as
+      :func:`deform_grid_displacement_gradient` returns it;
+    * ``affine`` / ``rotate`` / ``zoom`` / ``inverse_map``: as in :class:`AffineGradient` (``zoom=0`` raises).
+
+    A position that is not finite (or absurdly far out) contributes nothing: its row is zero and its cotangent is
+    ignored.  One non-finite cotangent elsewhere makes ``displacement`` and the map's fields NaN.  The sums over the
+    points are accumulated in 64-bit integer fixed point (one contribution resolved to 2^-61 of N max|d_coordinates|):
+    they are the same bits on every call and after any permutation of the points.  numpy in gives numpy out,
+    otherwise tensors on the positions' device.  A deformed axis of length 1 gives zeros.
+    """
+    plan, rows, ddisp, dk = _points_gradient(positions, d_coordinates, displacement, X_shape, crop, axis, affine,
+                                             rotate, zoom, False, False)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   False)
+
+
+def deform_points_gradient(points, d_positions, displacement, X_shape, crop=None, axis=None, affine=None,
+                           rotate=None, zoom=None, max_iter=32, tol=1e-9, positions=None):
+    """
+    Gradient through :func:`deform_points`: for ``L`` with ``d_positions = dL / d q`` (the shape of ``points``) and
+    ``q = deform_points(points, displacement, X_shape, ...)``, by the implicit function theorem at the solved ``q``:
+    ``points`` is ``J(q)^-T d_positions`` per point, ``displacement`` / ``affine`` / ``rotate`` / ``zoom`` /
+    ``inverse_map`` the sums of :func:`deform_grid_coordinates_gradient` with ``-J(q)^-T d_positions`` in place of
+    the cotangent.  This is what a landmark loss, a keypoint-consistency term or a fit to point correspondences
+    differentiates.
+
+    The inverse is solved here (in float64, with ``max_iter`` / ``tol``) unless ``positions``, the solved ``q``, is
+    given.  Points that are not solved (NaN), or whose Jacobian is singular, contribute nothing: a zero row, their
+    cotangent ignored.  Everything else as for :func:`deform_grid_coordinates_gradient`.
+    """
+    plan, rows, ddisp, dk = _points_gradient(points, d_positions, displacement, X_shape, crop, axis, affine, rotate,
+                                             zoom, True, False, max_iter=max_iter, tol=tol, positions=positions)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   False)
+
+
+def deform_grid_coordinates_gradient_batch(positions, d_coordinates, displacements, X_shape, crop=None, axis=None,
+                                           affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_coordinates_gradient` over a batch with one control grid per sample: ``positions`` and
+    ``d_coordinates`` ``(B, N, naxis)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE
+    sample.  ``points`` and ``displacement`` are per sample, the same bits as the single call on that sample; the
+    map's fields are the sum over the samples in sample order (:func:`deform_grid_affine_gradient_batch`)."""
+    plan, rows, ddisp, dk = _points_gradient(positions, d_coordinates, displacements, X_shape, crop, axis, affine,
+                                             rotate, zoom, False, True)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   True)
+
+
+def deform_points_gradient_batch(points, d_positions, displacements, X_shape, crop=None, axis=None, affine=None,
+                                 rotate=None, zoom=None, max_iter=32, tol=1e-9, positions=None):
+    """:func:`deform_points_gradient` over a batch with one control grid per sample; shapes and the summed fields
+    as for :func:`deform_grid_coordinates_gradient_batch`."""
+    plan, rows, ddisp, dk = _points_gradient(points, d_positions, displacements, X_shape, crop, axis, affine, rotate,
+                                             zoom, True, True, max_iter=max_iter, tol=tol, positions=positions)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   True)
 
 
 # ---- label-aware linear resampling of label maps (no counterpart in the reference) -------------------------------

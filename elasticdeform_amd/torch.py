@@ -20,9 +20,11 @@ from . import deform_grid_gradient as _deform_grid_gradient_fn
 from . import deform_grid_batch as _deform_grid_batch_fn
 from . import deform_grid_gradient_batch as _deform_grid_gradient_batch_fn
 from . import _host
-# mapping positions through the deformation (tensors stay on their device; no autograd flows through these four)
-from . import (deform_grid_coordinates, deform_points, deform_grid_coordinates_batch,  # noqa: F401
-               deform_points_batch)
+# mapping positions through the deformation: the batch forms are the package's own (tensors stay on their device, no
+# autograd); deform_grid_coordinates / deform_points below are differentiable wrappers of the single calls
+from . import deform_grid_coordinates_batch, deform_points_batch  # noqa: F401
+from . import deform_grid_coordinates as _deform_grid_coordinates_fn
+from . import deform_points as _deform_points_fn
 # label-aware linear resampling of label maps (integer tensors stay on their device; no autograd)
 from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
 import importlib  # noqa: E402
@@ -284,3 +286,127 @@ def deform_random_grid_batch(X, sigma=25, points=3, axis=None, generator=None, *
                                generator=generator)
     with _random_grid_hint(sigma, points, deform_shape):
         return deform_grid_batch(X, disp, axis=axis, **kwargs)
+
+
+# ---- points through the deformation, with autograd ------------------------------------------------------------------
+
+def _points_backward(ctx, inverse, cotangent, positions, converged):
+    """backward of both point Functions (inputs: points, displacement, affine, rotate, zoom, two non-tensors): ONE
+    library call (deform_grid.py _points_gradient) for whatever needs a gradient"""
+    pts, displacement = (t.detach() for t in ctx.saved_tensors[:2])
+    want_points = ctx.needs_input_grad[0]
+    want_disp = ctx.disp_grad and ctx.needs_input_grad[1]
+    want_map = any(ctx.needs_input_grad[2:5])
+    dpts = ddisp = None
+    grads = [None, None, None]
+    if want_points or want_disp or want_map:
+        host = ctx.host
+        plan, dpts, ddisp, dk = _api._points_gradient(
+            pts, cotangent.detach(), displacement, ctx.x_shape, ctx.kw.get('crop'), ctx.kw.get('axis'),
+            host.get('affine'), host.get('rotate'), host.get('zoom'), inverse, False, want_points=want_points,
+            want_disp=want_disp, want_map=want_map, positions=positions, converged=converged)
+        if ddisp is not None:
+            ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+        if dk is not None:
+            r = _api._affine_result(dk, plan, host.get('affine'), host.get('rotate'), host.get('zoom'), False)
+            grads = _param_grads(ctx.needs_input_grad[2:5], ctx.params, r[:3])
+    return (dpts, ddisp) + tuple(grads) + (None, None)
+
+
+def _points_forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad):
+    ctx.params = (affine, rotate, zoom)
+    ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, ctx.params) if v is not None}
+    ctx.kw = kw
+    ctx.x_shape = kw['X_shape']
+    ctx.disp_grad = disp_grad
+    return dict(crop=kw.get('crop'), axis=kw.get('axis'), **ctx.host)
+
+
+class DeformGridCoordinates(torch.autograd.Function):
+    """forward: deform_grid_coordinates (with its Jacobian); backward: deform_grid_coordinates_gradient"""
+
+    @staticmethod
+    def forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad):
+        call = _points_forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad)
+        ctx.save_for_backward(pts, displacement)
+        r, J = _deform_grid_coordinates_fn(pts.detach(), displacement.detach(), kw['X_shape'], jacobian=True, **call)
+        ctx.mark_non_differentiable(J)
+        return r, J
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dr, _dJ):
+        return _points_backward(ctx, False, dr, None, None)
+
+
+class DeformPoints(torch.autograd.Function):
+    """forward: deform_points, solved in float64 (q and the mask are kept); backward: deform_points_gradient at the
+    kept q -- it never solves again"""
+
+    @staticmethod
+    def forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad):
+        call = _points_forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad)
+        q, ok = _deform_points_fn(pts.detach().to(torch.float64), displacement.detach(), kw['X_shape'],
+                                  max_iter=kw['max_iter'], tol=kw['tol'], return_converged=True, **call)
+        ctx.save_for_backward(pts, displacement, q, ok)
+        ctx.mark_non_differentiable(ok)
+        return q.to(pts.dtype), ok
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dq, _dok):
+        q, ok = ctx.saved_tensors[2:]
+        return _points_backward(ctx, True, dq, q, ok)
+
+
+def _points_need_autograd(points, displacement, params, displacement_grad, affine_grad):
+    def needs(v):
+        return torch.is_tensor(v) and v.requires_grad
+    return (needs(points) or (displacement_grad and needs(displacement))
+            or (affine_grad and any(needs(v) for v in params)))
+
+
+def deform_grid_coordinates(positions, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                            zoom=None, jacobian=False, *, displacement_grad=False, affine_grad=False):
+    """
+    ``elasticdeform_amd.deform_grid_coordinates`` with autograd: the gradient flows to ``positions`` whenever they
+    require it, to ``displacement`` with ``displacement_grad=True`` and to tensor ``affine`` / ``rotate`` / ``zoom``
+    with ``affine_grad=True`` (keyword-only, the switches of :func:`deform_grid`); the backward is ONE call of
+    ``elasticdeform_amd.deform_grid_coordinates_gradient``'s kernels.  The Jacobian is not differentiable.  With
+    nothing requiring a gradient the call is the package's own: same bits, same types, numpy stays numpy.
+    """
+    params = (affine, rotate, zoom)
+    if not _points_need_autograd(positions, displacement, params, displacement_grad, affine_grad):
+        host = [_host_value(v) for v in params]
+        return _deform_grid_coordinates_fn(positions, displacement, X_shape, crop, axis, *host, jacobian=jacobian)
+    positions = torch.as_tensor(positions)
+    displacement = torch.as_tensor(displacement)
+    if not affine_grad:
+        params = tuple(_host_value(v) for v in params)
+    r, J = DeformGridCoordinates.apply(positions, displacement, *params, dict(X_shape=X_shape, crop=crop, axis=axis),
+                                       bool(displacement_grad))
+    return (r, J) if jacobian else r
+
+
+def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None,
+                  max_iter=32, tol=1e-9, return_converged=False, *, displacement_grad=False, affine_grad=False):
+    """
+    ``elasticdeform_amd.deform_points`` with autograd (implicit function theorem at the solved position): the
+    gradient flows to ``points`` whenever they require it, to ``displacement`` with ``displacement_grad=True`` and to
+    tensor ``affine`` / ``rotate`` / ``zoom`` with ``affine_grad=True``.  The forward keeps the solved positions and
+    the mask; the backward never solves again, and points that were not solved receive and contribute nothing.  The
+    mask is not differentiable.  With nothing requiring a gradient the call is the package's own.
+    """
+    params = (affine, rotate, zoom)
+    if not _points_need_autograd(points, displacement, params, displacement_grad, affine_grad):
+        host = [_host_value(v) for v in params]
+        return _deform_points_fn(points, displacement, X_shape, crop, axis, *host, max_iter=max_iter, tol=tol,
+                                 return_converged=return_converged)
+    points = torch.as_tensor(points)
+    displacement = torch.as_tensor(displacement)
+    if not affine_grad:
+        params = tuple(_host_value(v) for v in params)
+    q, ok = DeformPoints.apply(points, displacement, *params,
+                               dict(X_shape=X_shape, crop=crop, axis=axis, max_iter=max_iter, tol=tol),
+                               bool(displacement_grad))
+    return (q, ok) if return_converged else q

@@ -431,6 +431,61 @@ int edhip_deform_points(int inverse, int nbatch,
                         char* err, size_t errlen);
 
 /*
+ * The adjoint of edhip_deform_points: gradients through the coordinate map and through its inverse (no counterpart in
+ * the reference).  In the notation above, with beta(q, j) the sum of the cubic tap-weight products whose mirrored tap
+ * index is j (beta >= 0, sum_j beta = 1; with few control points several taps of one point fold onto one j),
+ *   r_h(q) = sum_l K[h, l] q_l + K[h, naxis] + offset_h + sum_j P[h, j] beta(q, j)
+ * is linear in the prefiltered grid P and in K.
+ *   inverse == 0   positions = q_i, cotangent u[i, :] = dL / d r(q_i):
+ *                    dpoints[i, l]        = sum_h J[i, h, l] u[i, h]
+ *                    ddisplacement[h, j]  = sum_i u[i, h] beta(q_i, j)                (= dL / dP)
+ *                    dinverse_affine[h, l < naxis] = sum_i u[i, h] q_i[l],  [h, naxis] = sum_i u[i, h]
+ *   inverse != 0   positions = the SOLVED q_i = r^-1(p_i) (the result of edhip_deform_points), cotangent
+ *                  g[i, :] = dL / d q_i.  By the implicit function theorem at q_i:
+ *                    dpoints[i, :] = J(q_i)^-T g[i, :]                                 (= dL / d p_i)
+ *                    ddisplacement, dinverse_affine: the sums above with u[i, :] = -J(q_i)^-T g[i, :]
+ * ddisplacement is the gradient with respect to the PREFILTERED grid; the caller applies the transposed prefilter.
+ * Points that contribute nothing get a zero row of their own and their cotangent is ignored: (forward) a position
+ * that is not finite or whose control coordinate exceeds 4e15; (inverse) status[i] == 0, a non-finite q, a singular or
+ * non-finite J.
+ *   positions0 / cotangent0 / dpoints0   (N, naxis), float32 or float64 each, any strides; fp64 arithmetic, a float32
+ *                        row is rounded once at the store.  dpoints0 may be NULL.
+ *   status0              NULL, or (inverse only, EDHIP_ERR_INVALID otherwise) uint8 (N).
+ *   displacement0        the PREFILTERED control grid, as for edhip_deform_points; EDHIP_FLAG_RAW_DISPLACEMENT is
+ *                        refused (EDHIP_ERR_INVALID).
+ *   ddisplacement0       NULL, or the grid's shape in a floating-point dtype (EDHIP_ERR_INVALID / EDHIP_ERR_DTYPE).
+ *   dinverse_affine0     NULL, or float64 (naxis, naxis + 1).  All three results NULL: EDHIP_ERR_INVALID.
+ *   nbatch               at most 65535 (EDHIP_ERR_UNSUPPORTED); sample b's arrays are sample 0's moved by b * stride.
+ * Every shape, dtype and flag check answers before any launch.  With N == 0 the requested ddisplacement /
+ * dinverse_affine are written as zeros; with nbatch == 0 nothing is launched.
+ * Resolution and bit contracts: the sums are accumulated in 64-bit integer fixed point.  Per sample, with N the number
+ * of contributing points and max|u|, max|q| taken over them, one contribution to ddisplacement is rounded to a multiple of 2^(e-62), 2^e
+ * being the smallest power of two >= 2 N max|u| -- it is resolved to 2^-61 of N max|u| -- and one contribution to
+ * dinverse_affine likewise with N max|u| max(1, max|q|).  No cell can overflow, and integer addition is associative:
+ * ddisplacement and dinverse_affine are the same bits on a repeated call, for a sample of a batch and the single call
+ * on it, after ANY permutation of the points, and eager or replayed from a captured HIP graph.  A row of dpoints
+ * depends on that point and the call's arguments alone.  One non-finite cotangent on a contributing point makes
+ * every element of that sample's ddisplacement / dinverse_affine NaN (and no other sample's); max|u| = 0 gives exact
+ * zeros.  Four launches -- the clearing of the call's scratch (the stream's workspace) and three kernels -- on hip_stream
+ * without synchronising; nothing is carried from one call to the next, so a captured graph replays self-contained
+ * (warm up once on the capture stream: the workspace is allocated on first use).
+ */
+int edhip_deform_points_gradient(int inverse, int nbatch,
+                                 const edhip_array* positions0, int64_t positions_batch_stride,
+                                 const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                 const edhip_array* status0, int64_t status_batch_stride,
+                                 const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                 const int64_t* in_len,
+                                 const int64_t* output_offset,
+                                 int naxis,
+                                 const double* affine,
+                                 const edhip_array* dpoints0, int64_t dpoints_batch_stride,
+                                 const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                 const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                 uint32_t flags, void* hip_stream,
+                                 char* err, size_t errlen);
+
+/*
  * Label-aware linear resampling of label maps (no counterpart in the reference, whose order-1 interpolation of an
  * integer map interpolates the label NUMBERS).  For a label map L, with the classes being the distinct values of L
  * together with cval, the score of class c is the reference's own float64 order-1 result on the one-hot channel,
