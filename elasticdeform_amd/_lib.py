@@ -55,7 +55,7 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
-           'edhip_deform_points_gradient')
+           'edhip_deform_points_gradient', 'edhip_deform_inverse')
 
 
 class EdhipArray(ctypes.Structure):
@@ -191,6 +191,13 @@ def load():
             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_double,
             ctypes.POINTER(ctypes.c_double), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_inverse.restype = ctypes.c_int
+        L.edhip_deform_inverse.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+            ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+            ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -429,6 +436,32 @@ def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_o
         int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
         ctypes.byref(out_desc), int(out_bstride), _ref(weight_desc), int(weight_bstride), len(axis),
         axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(mode), float(cval), aff, int(flags),
+        ctypes.c_void_p(stream), buf, 256)
+    raise_for_status(status, buf)
+
+
+def deform_inverse(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, in_len, output_offset, out_desc, out_bstride,
+                   valid_desc, valid_bstride, axis, order, mode, cval, inverse_affine, forward_linear, max_iter, tol,
+                   flags, stream):
+    """edhip_deform_inverse: `in_desc` (the deformed image, spline coefficients for order > 1) resampled back into the
+    source frame -- per source voxel the q with r(q) = voxel, solved as deform_points() solves it, and the forward
+    gather of `in_desc` at q into `out_desc` (deformed extents `in_len`); `valid_desc` (uint8, shape `in_len`; None =
+    not wanted): 1 where q was solved and lies inside `in_desc`.  Sample 0's descriptors plus byte strides; `disp_desc`
+    is the PREFILTERED control grid."""
+    L = load()
+    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
+    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    lin = lin_arr = None
+    if forward_linear is not None:
+        lin_arr = numpy.ascontiguousarray(forward_linear, dtype=numpy.float64)
+        lin = lin_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    buf = _buf()
+    status = L.edhip_deform_inverse(
+        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride),
+        in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, ctypes.byref(out_desc), int(out_bstride),
+        _ref(valid_desc), int(valid_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        int(order), int(mode), float(cval), aff, lin, int(max_iter), float(tol), int(flags),
         ctypes.c_void_p(stream), buf, 256)
     raise_for_status(status, buf)
 

@@ -24,8 +24,8 @@
 // 3-axis instances keep everything in registers (the tap sum unrolled, but for the outermost of three tap loops);
 // 4 to 7 axes run an odometer over the 4^n taps.
 //
-// eval_map, solve and the grid readers live in ed_points.h: deform_points_grad.hip (the adjoint of both directions)
-// shares them.
+// eval_map, solve, invert_map and the grid readers live in ed_points.h: deform_points_grad.hip (the adjoint of both
+// directions) and deform_unwarp.hip (the image resampled back through the deformation) share them.
 #include <cmath>
 #include <cstring>
 
@@ -37,88 +37,6 @@
 namespace ed {
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ double max_norm_diff(const double (&r)[N], const double (&p)[N])
-{
-    double m = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        const double e = fabs(r[h] - p[h]);
-        bad = bad || !(e == e);
-        m = e > m ? e : m;
-    }
-    return bad ? INFINITY : m;
-}
-
-// q with r(q) = p; false: no solution reached (see the head of the file)
-template <int N, typename Grid>
-__device__ __forceinline__ bool invert_map(const PointsArgs& a, const Grid& grid, const int64_t (&tstride)[N],
-                                           const double (&p)[N], double (&q)[N])
-{
-    const GridGeom& g = a.g;
-    double b[N], s[N], trial[N];
-    bool finite = true;
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        finite = finite && isfinite(p[h]);
-        b[h] = p[h] - (double)g.off[h] - (g.has_affine ? g.affine[h * (N + 1) + N] : 0.0);
-    }
-    if (!finite)
-        return false;
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        if (g.has_affine) {
-            double acc = 0.0;
-#pragma unroll
-            for (int l = 0; l < N; ++l)
-                acc += a.minv[h * N + l] * b[l];
-            trial[h] = acc;
-        } else {
-            trial[h] = b[h];
-        }
-        s[h] = 0.0;
-    }
-    double res = INFINITY, lambda = 1.0;
-    int steps = 0, halvings = 0;
-    bool first = true;
-    // one evaluation per turn: of the start, of a full Newton step, or of a halved one
-    for (;;) {
-        double r[N], J[N][N];
-        eval_map<N>(a, grid, tstride, trial, r, J);
-        const double rt = max_norm_diff<N>(r, p);
-        if (rt < res) {
-            // accepted (the start, or a step that lowers the residual)
-#pragma unroll
-            for (int h = 0; h < N; ++h)
-                q[h] = trial[h];
-            res = rt;
-            if (res <= a.tol)
-                return true;
-            if (steps == a.max_iter)
-                return false;
-            double e[N];
-#pragma unroll
-            for (int h = 0; h < N; ++h)
-                e[h] = r[h] - p[h];
-            if (!solve<N>(J, e, s))
-                return false;
-            ++steps;
-            lambda = 1.0;
-            halvings = 0;
-        } else {
-            if (first || halvings == kPointsMaxHalvings)
-                return false;             // a start that is not finite, or an exhausted backtrack
-            ++halvings;
-            lambda *= 0.5;
-        }
-        first = false;
-#pragma unroll
-        for (int h = 0; h < N; ++h)
-            trial[h] = q[h] - lambda * s[h];
-    }
-}
 
 template <int N, bool LDS, bool INVERSE>
 __global__ __launch_bounds__(kPointsThreads) void points_kernel(PointsArgs a)

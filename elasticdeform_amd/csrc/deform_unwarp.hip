@@ -1,0 +1,335 @@
+// deform_unwarp.hip -- an image carried back through the deformation (edhip_deform_inverse): the image-side
+// counterpart of the inverse direction of deform_points.hip.
+//
+// deform_grid is a pull warp, Y[o] = X(r(o)).  For every integer source position p (extents I, the deformed extents
+// of X) this kernel solves r(q) = p for the crop-local real position q in Y -- invert_map of ed_points.h, the very
+// iteration of points_kernel<N, LDS, true>: same start, damped Newton step, halvings, tol and max_iter -- and stores
+//   Z[p, step] = S_Y(q)[step]
+// where S_Y is the gather deform_grid applies to its input at a source coordinate, on the array Y of deformed extents
+// O: map_coordinate per axis, window_start, the mirror edge taps, spline_weights(order), the fp64 tap sum in the
+// reference's tap order (lexicographic, last axis fastest; value, then * w_0, * w_1, * w_2, then added:
+// deform.c:841-924 as deform_exact.hip restates it, no FMA) and store_forward.  A 'constant' coordinate outside
+// [0, O_k - 1] gives cval; a voxel whose iteration does not solve gives cval in EVERY mode.  valid[p] = 1 exactly when
+// q was solved and 0 <= q_k <= O_k - 1 on every axis: Z is interpolated from inside Y there.
+//
+// One thread per source voxel (the thread lattice is I = GridGeom::in_len; the array that is sampled and
+// bounds-checked has the extents O = GridGeom::out_len), last deformed axis fastest, blockIdx.y = sample.  The thread
+// runs in two phases that share q[N] and the solved flag only: the Newton phase (fp64, the control grid staged in LDS
+// as doubles up to kPointsLdsValues values and read from global memory beyond), then the gather phase, which forms the
+// taps and weights once and loops over the steps (channels) of its voxel.  The outer tap loops stay rolled and rotate
+// their weights and offsets through scalars, the innermost row of up to six taps is unrolled and loaded together, so
+// every array is indexed with compile-time constants (nothing goes to scratch).  Whatever the coordinate, no load
+// leaves Y: tap indices are clamped to [0, O_k - 1] (no effect on a coordinate the boundary map produced).  No
+// atomics, no workspace, no synchronisation beyond the staging barrier: a voxel's result depends on the call's
+// arguments alone, so a sample of a batch and a repeated call give the same bits.
+#include <cstring>
+
+#include "ed_device.h"
+#include "ed_exact_coord.h"
+#include "ed_params.h"
+#include "ed_points.h"
+
+namespace ed {
+
+namespace {
+
+constexpr int kUnwarpThreads = 256;
+
+// what the gather phase reads (never written in the kernel: its step arrays are indexed at run time)
+struct UnwarpView {
+    IOView v;                                 // in: Y of sample 0 (deformed extents O); out: Z (deformed extents I)
+    int64_t in_bstride, out_bstride;
+    unsigned char* valid;                     // uint8, deformed extents I, or nullptr
+    int64_t valid_stride[3], valid_bstride;
+    int64_t nsrc;                             // prod I_k: the work size
+};
+
+// spline_weights for a constant order; every order writes all six slots (zeros past the order), so that no store to
+// w is ever indexed by the order at run time
+template <int ORDER>
+__device__ __forceinline__ void weights_of_order(double c, double (&w)[6])
+{
+    double tmp[ORDER + 1];
+    spline_weights(c, ORDER, tmp);
+#pragma unroll
+    for (int l = 0; l < 6; ++l)
+        w[l] = l <= ORDER ? tmp[l <= ORDER ? l : 0] : 0.0;
+}
+__device__ __forceinline__ void weights_by_order(double c, int order, double (&w)[6])
+{
+    switch (order) {
+    case 1: weights_of_order<1>(c, w); break;
+    case 2: weights_of_order<2>(c, w); break;
+    case 3: weights_of_order<3>(c, w); break;
+    case 4: weights_of_order<4>(c, w); break;
+    case 5: weights_of_order<5>(c, w); break;
+    default:                                  // order 0: one tap, no weight
+#pragma unroll
+        for (int l = 0; l < 6; ++l)
+            w[l] = 0.0;
+        break;
+    }
+}
+
+// The (order + 1)^N taps from deformed axis D on, added to t in the reference's order.  wo[k], k < D: the weight of
+// the current tap on the outer axes.  S: the element type (its conversion to double is the plain C one).
+template <typename S, int N, int D>
+__device__ __forceinline__ void tap_rows(const char* base, int order, const int64_t (&tap)[N][6],
+                                         const double (&w)[N][6], double (&wo)[N], double& t)
+{
+    // reference arithmetic (x86-64, no FMA): keep the products and sums separate
+#pragma clang fp contract(off)
+    if constexpr (D == N - 1) {
+        S val[6];
+#pragma unroll
+        for (int l = 0; l < 6; ++l)           // (taps past the order repeat tap 0: no branch around a load)
+            val[l] = *reinterpret_cast<const S*>(base + tap[D][l]);
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+            if (l <= order) {
+                double coeff = (double)val[l];
+                if (order > 0) {
+#pragma unroll
+                    for (int k = 0; k < D; ++k)
+                        coeff *= wo[k];
+                    coeff *= w[D][l];
+                }
+                t += coeff;
+            }
+        }
+    } else {
+        // rolled: the turn's weight and offset rotate through scalars (deform_points.hip: grid_taps)
+        double w0 = w[D][0], w1 = w[D][1], w2 = w[D][2], w3 = w[D][3], w4 = w[D][4], w5 = w[D][5];
+        int64_t o0 = tap[D][0], o1 = tap[D][1], o2 = tap[D][2], o3 = tap[D][3], o4 = tap[D][4], o5 = tap[D][5];
+#pragma unroll 1
+        for (int l = 0; l <= order; ++l) {
+            wo[D] = w0;
+            tap_rows<S, N, D + 1>(base + o0, order, tap, w, wo, t);
+            const double wr = w0;
+            const int64_t orot = o0;
+            w0 = w1, w1 = w2, w2 = w3, w3 = w4, w4 = w5, w5 = wr;
+            o0 = o1, o1 = o2, o2 = o3, o3 = o4, o4 = o5, o5 = orot;
+        }
+    }
+}
+
+template <typename S, int N>
+__device__ __forceinline__ double tap_sum(const char* base, int order, const int64_t (&tap)[N][6],
+                                          const double (&w)[N][6])
+{
+    double t = 0.0;
+    double wo[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        wo[k] = 1.0;
+    tap_rows<S, N, 0>(base, order, tap, w, wo, t);
+    return t;
+}
+
+// The gather phase of source voxel o: S_Y(q) for every step, and valid.
+template <int N>
+__device__ __forceinline__ void resample(const GridGeom& g, const UnwarpView& u, const int64_t b,
+                                         const int64_t (&o)[N], const double (&q)[N], const bool solved)
+{
+    // reference arithmetic (x86-64, no FMA): keep the products and sums separate
+#pragma clang fp contract(off)
+    const IOView& v = u.v;
+    const int order = v.order;
+    double w[N][6];
+    int64_t tap[N][6];                        // byte offsets of the taps on each deformed axis of Y
+    bool constant = !solved, inside = solved;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        const int64_t len = g.out_len[h];
+        const double qh = solved ? q[h] : 0.0;
+        inside = inside && qh >= 0.0 && qh <= (double)(len - 1);
+        // boundary map, window and weights as deform_exact.hip has them (deform.c:768-824)
+        const double cc = map_coordinate(qh, len, v.mode);
+        const bool in = cc > -1.0;
+        constant = constant || !in;           // 'constant' outside the array (or a NaN coordinate): cval
+        const double c = in ? cc : 0.0;       // (a voxel that takes cval forms taps inside the array and loads nothing)
+        const int64_t start = window_start(c, order);
+        // (a tap past the order repeats tap 0: the row loads below need no branch, and its value is never added)
+        if (start < 0 || start + order >= len) {
+            int64_t first = 0;
+#pragma unroll
+            for (int l = 0; l < 6; ++l) {
+                int64_t idx = mirror_index(start + l, len);
+                // no load leaves the array, whatever the coordinate (no effect on a coordinate the boundary map produced)
+                idx = idx < 0 ? 0 : (idx > len - 1 ? len - 1 : idx);
+                if (l == 0)
+                    first = idx;
+                tap[h][l] = (l <= order ? idx : first) * v.in_stride[h];
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 6; ++l)
+                tap[h][l] = (l <= order ? start + l : start) * v.in_stride[h];
+        }
+        weights_by_order(c, order, w[h]);
+    }
+
+    int64_t out_vox = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        out_vox += v.out_stride[k] * o[k];
+    if (u.valid) {
+        int64_t voff = b * u.valid_bstride;
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            voff += u.valid_stride[k] * o[k];
+        u.valid[voff] = inside ? 1 : 0;
+    }
+
+    // every step (channel) of the voxel reuses q, the taps and the weights
+    const char* in_b = v.in + b * u.in_bstride;
+    char* out_b = v.out + b * u.out_bstride + out_vox;
+    for (int64_t ss = 0; ss < v.nsteps; ++ss) {
+        // step (non-deformed axes) offsets, first step axis fastest, deform.c:828-838 (the same for every thread)
+        int64_t in_off = 0, out_off = 0;
+        {
+            int64_t r = ss;
+            for (int l = 0; l < v.nstep; ++l) {
+                const int64_t d = r / v.step_len[l];
+                const int64_t c = r - d * v.step_len[l];
+                in_off += v.in_step_stride[l] * c;
+                out_off += v.out_step_stride[l] * c;
+                r = d;
+            }
+        }
+        double t = v.cval;
+        if (!constant) {
+            const char* base = in_b + in_off;
+            switch (v.in_dtype) {
+            case EDHIP_BOOL:
+            case EDHIP_U8: t = tap_sum<uint8_t, N>(base, order, tap, w); break;
+            case EDHIP_I8: t = tap_sum<int8_t, N>(base, order, tap, w); break;
+            case EDHIP_U16: t = tap_sum<uint16_t, N>(base, order, tap, w); break;
+            case EDHIP_I16: t = tap_sum<int16_t, N>(base, order, tap, w); break;
+            case EDHIP_U32: t = tap_sum<uint32_t, N>(base, order, tap, w); break;
+            case EDHIP_I32: t = tap_sum<int32_t, N>(base, order, tap, w); break;
+            case EDHIP_U64: t = tap_sum<uint64_t, N>(base, order, tap, w); break;
+            case EDHIP_I64: t = tap_sum<int64_t, N>(base, order, tap, w); break;
+            case EDHIP_F32: t = tap_sum<float, N>(base, order, tap, w); break;
+            default: t = tap_sum<double, N>(base, order, tap, w); break;      // float64 (the launcher admits no other)
+            }
+        }
+        store_forward(out_b + out_off, v.out_dtype, t);
+    }
+}
+
+template <int N, bool LDS>
+__global__ __launch_bounds__(kUnwarpThreads) void unwarp_kernel(PointsArgs a, const UnwarpView u)
+{
+    extern __shared__ double s_grid[];        // LDS: [N][ncp_0]...[ncp_{N-1}]
+    const int64_t b = blockIdx.y;
+    a.g.disp += b * a.disp_bstride;           // this sample's control grid
+    const GridGeom& g = a.g;
+    int64_t tstride[N];
+    int per = 0;
+    if constexpr (LDS) {
+        per = stage_grid_lds<N>(g, s_grid);
+        __syncthreads();
+        int64_t cs = 1;
+#pragma unroll
+        for (int k = N - 1; k >= 0; --k) {
+            tstride[k] = cs;
+            cs *= g.ncp[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            tstride[k] = g.disp_stride[k + 1];
+    }
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= u.nsrc)
+        return;
+    // source voxel index (extents I), last deformed axis fastest
+    int64_t o[N];
+    {
+        int64_t r = tid;
+#pragma unroll
+        for (int k = N - 1; k >= 0; --k) {
+            const int64_t d = r / g.in_len[k];
+            o[k] = r - d * g.in_len[k];
+            r = d;
+        }
+    }
+    // the Newton phase: q with r(q) = p
+    double p[N], q[N];
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        p[h] = (double)o[h];
+        q[h] = 0.0;
+    }
+    bool solved;
+    if constexpr (LDS)
+        solved = invert_map<N>(a, LdsGrid{s_grid, per}, tstride, p, q);
+    else
+        solved = invert_map<N>(a, GlobalGrid{g.disp, g.disp_stride[0], g.disp_dtype}, tstride, p, q);
+    // the gather phase
+    resample<N>(g, u, b, o, q, solved);
+}
+
+template <int N>
+hipError_t launch_unwarp(const PointsArgs& a, const UnwarpView& u, int nbatch, hipStream_t stream)
+{
+    const int64_t nblk = (u.nsrc + kUnwarpThreads - 1) / kUnwarpThreads;
+    if (nblk > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    int64_t values = N;
+    for (int k = 0; k < N; ++k)
+        values *= a.g.ncp[k];
+    const dim3 grid((unsigned)nblk, (unsigned)nbatch);
+    if (values <= kPointsLdsValues)
+        hipLaunchKernelGGL((unwarp_kernel<N, true>), grid, dim3(kUnwarpThreads), (size_t)values * sizeof(double),
+                           stream, a, u);
+    else
+        hipLaunchKernelGGL((unwarp_kernel<N, false>), grid, dim3(kUnwarpThreads), 0, stream, a, u);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream)
+{
+    const GridGeom& g = c.g;
+    const int n = g.naxis;
+    if (n < 1 || n > 3 || c.nbatch > 65535 || c.v.in_dtype != c.v.out_dtype || c.v.in_dtype == EDHIP_F16 ||
+        c.v.in_dtype == EDHIP_BF16 || c.v.order < 0 || c.v.order > 5)
+        return hipErrorNotSupported;
+    UnwarpView u;
+    memset(&u, 0, sizeof(u));
+    u.v = c.v;
+    u.in_bstride = c.in_bstride;
+    u.out_bstride = c.out_bstride;
+    u.valid = c.valid;
+    u.valid_bstride = c.valid_bstride;
+    u.nsrc = 1;
+    for (int k = 0; k < n; ++k) {
+        u.valid_stride[k] = c.valid_stride[k];
+        u.nsrc *= g.in_len[k];
+        if (g.in_len[k] < 2 || g.out_len[k] < 1)
+            return hipErrorInvalidValue;
+    }
+    if (c.nbatch <= 0 || u.nsrc <= 0 || c.v.nsteps <= 0)
+        return hipSuccess;                    // nothing to launch
+    PointsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g = g;
+    a.disp_bstride = c.disp_bstride;
+    a.max_iter = c.max_iter;
+    a.tol = c.tol;
+    for (int k = 0; k < n; ++k) {
+        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
+        for (int l = 0; l < n; ++l)
+            a.minv[k * n + l] = c.forward_linear ? c.forward_linear[k * n + l] : (k == l ? 1.0 : 0.0);
+    }
+    switch (n) {
+    case 1: return launch_unwarp<1>(a, u, c.nbatch, stream);
+    case 2: return launch_unwarp<2>(a, u, c.nbatch, stream);
+    default: return launch_unwarp<3>(a, u, c.nbatch, stream);
+    }
+}
+
+}  // namespace ed

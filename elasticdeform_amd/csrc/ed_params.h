@@ -256,6 +256,25 @@ struct LabelsCall {
 };
 hipError_t launch_deform_labels(const LabelsCall& c, hipStream_t stream);
 
+// An image carried back through the deformation (deform_unwarp.hip): for every integer source position p (extents
+// g.in_len) the q with r(q) = p, solved as launch_deform_points(inverse) solves it, and the forward gather of `v.in`
+// (deformed extents g.out_len) at q, for every step of the voxel.  One thread per source voxel, blockIdx.y = sample; no
+// scratch, no synchronisation.  1 to 3 deformed axes, v.in_dtype == v.out_dtype, no 16-bit floats;
+// hipErrorNotSupported (nothing launched) otherwise.
+struct InverseCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len = I (>= 2 each), out_len = O
+    IOView v;                     // sample 0: v.in = Y (read, extents O), v.out = Z (written, extents I); order, mode, cval
+    int nbatch;
+    int64_t in_bstride, out_bstride, disp_bstride;   // bytes between samples
+    unsigned char* valid;         // uint8, deformed extents I: 1 = solved and inside Y; nullptr: not wanted
+    int64_t valid_stride[kMaxAxes];
+    int64_t valid_bstride;
+    const double* forward_linear; // host, M = (K[:, :naxis])^-1 row-major; nullptr: the identity
+    int max_iter;
+    double tol;
+};
+hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream);
+
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;
 

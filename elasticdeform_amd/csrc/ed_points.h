@@ -1,6 +1,7 @@
-// ed_points.h -- what the kernels of deform_points.hip (the coordinate map at real positions and its inverse) and of
-// deform_points_grad.hip (their adjoint) share: the argument block, the control grid's readers, the separable tap sum,
-// r(q) with its Jacobian and the n x n solve.  Notation: the head of deform_points.hip.
+// ed_points.h -- what the kernels of deform_points.hip (the coordinate map at real positions and its inverse), of
+// deform_points_grad.hip (their adjoint) and of deform_unwarp.hip (an image resampled back through the deformation)
+// share: the argument block, the control grid's readers, the separable tap sum, r(q) with its Jacobian, the n x n solve
+// and the damped Newton inversion.  Notation: the head of deform_points.hip.
 #pragma once
 
 #include <cmath>
@@ -299,6 +300,88 @@ __device__ __forceinline__ bool solve(const double (&J)[N][N], const double (&b)
             ok = ok && isfinite(s[i]);
         }
         return ok;
+    }
+}
+
+template <int N>
+__device__ __forceinline__ double max_norm_diff(const double (&r)[N], const double (&p)[N])
+{
+    double m = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        const double e = fabs(r[h] - p[h]);
+        bad = bad || !(e == e);
+        m = e > m ? e : m;
+    }
+    return bad ? INFINITY : m;
+}
+
+// q with r(q) = p; false: no solution reached (see the head of deform_points.hip)
+template <int N, typename Grid>
+__device__ __forceinline__ bool invert_map(const PointsArgs& a, const Grid& grid, const int64_t (&tstride)[N],
+                                           const double (&p)[N], double (&q)[N])
+{
+    const GridGeom& g = a.g;
+    double b[N], s[N], trial[N];
+    bool finite = true;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        finite = finite && isfinite(p[h]);
+        b[h] = p[h] - (double)g.off[h] - (g.has_affine ? g.affine[h * (N + 1) + N] : 0.0);
+    }
+    if (!finite)
+        return false;
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        if (g.has_affine) {
+            double acc = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+                acc += a.minv[h * N + l] * b[l];
+            trial[h] = acc;
+        } else {
+            trial[h] = b[h];
+        }
+        s[h] = 0.0;
+    }
+    double res = INFINITY, lambda = 1.0;
+    int steps = 0, halvings = 0;
+    bool first = true;
+    // one evaluation per turn: of the start, of a full Newton step, or of a halved one
+    for (;;) {
+        double r[N], J[N][N];
+        eval_map<N>(a, grid, tstride, trial, r, J);
+        const double rt = max_norm_diff<N>(r, p);
+        if (rt < res) {
+            // accepted (the start, or a step that lowers the residual)
+#pragma unroll
+            for (int h = 0; h < N; ++h)
+                q[h] = trial[h];
+            res = rt;
+            if (res <= a.tol)
+                return true;
+            if (steps == a.max_iter)
+                return false;
+            double e[N];
+#pragma unroll
+            for (int h = 0; h < N; ++h)
+                e[h] = r[h] - p[h];
+            if (!solve<N>(J, e, s))
+                return false;
+            ++steps;
+            lambda = 1.0;
+            halvings = 0;
+        } else {
+            if (first || halvings == kPointsMaxHalvings)
+                return false;             // a start that is not finite, or an exhausted backtrack
+            ++halvings;
+            lambda *= 0.5;
+        }
+        first = false;
+#pragma unroll
+        for (int h = 0; h < N; ++h)
+            trial[h] = q[h] - lambda * s[h];
     }
 }
 

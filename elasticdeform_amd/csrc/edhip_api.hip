@@ -1584,4 +1584,90 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
     return EDHIP_OK;
 }
 
+// ---- an image carried back through the deformation (deform_unwarp.hip) ----------------------------------------
+int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                         const edhip_array* displacement0, int64_t displacement_batch_stride, const int64_t* in_len,
+                         const int64_t* output_offset, const edhip_array* output0, int64_t output_batch_stride,
+                         const edhip_array* valid0, int64_t valid_batch_stride, int naxis, const int32_t* axis,
+                         int32_t order, int32_t mode, double cval, const double* affine, const double* forward_linear,
+                         int max_iter, double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || !input0 || !displacement0 || !output0 || !in_len)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (!axis || naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > 3)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_inverse takes 1 to 3 deformed axes");
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_inverse takes the prefiltered control grid");
+    const edhip_array& in = *input0;
+    const edhip_array& out = *output0;
+    if (int st = check_pairs(input0, output0, 1, naxis, axis, &order, &mode, &cval, false, err, errlen))
+        return st;
+    for (int j = 1; j < naxis; ++j)
+        if (axis[j] <= axis[j - 1])
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
+    if (in.dtype != out.dtype)
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "input and output must have one dtype");
+    if (in.dtype == EDHIP_F16 || in.dtype == EDHIP_BF16)
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    int64_t sampled_len[kMaxAxes];
+    for (int k = 0; k < naxis; ++k) {
+        sampled_len[k] = in.shape[axis[k]];
+        if (out.shape[axis[k]] != in_len[k])
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the output's deformed axes must have the extents in_len");
+        if (sampled_len[k] < 2)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "deformed axes must have at least 2 elements");
+    }
+    if (valid0) {
+        bool same = valid0->ndim == naxis;
+        for (int k = 0; same && k < naxis; ++k)
+            same = valid0->shape[k] == in_len[k];
+        if (!same)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "valid must have the output's deformed shape");
+        if (valid0->dtype != EDHIP_U8)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "valid must be uint8");
+    }
+    if (max_iter < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "max_iter must be at least 1");
+    if (!(tol > 0.0))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "tol must be positive");
+    if (affine && !forward_linear)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (nbatch > 65535)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_inverse: too many samples");
+    InverseCall c;
+    memset(&c, 0, sizeof(c));
+    // the solve's geometry is the forward call's (extents in_len); the sampled array has the input's own extents
+    if (int st = fill_geometry(displacement0, in_len, sampled_len, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    if (int st = make_view(in, out, naxis, axis, order, mode, cval, c.v, err, errlen))
+        return st;
+    if (nbatch == 0 || c.v.nsteps <= 0)
+        return EDHIP_OK;
+    c.nbatch = nbatch;
+    c.in_bstride = input_batch_stride;
+    c.out_bstride = output_batch_stride;
+    c.disp_bstride = displacement_batch_stride;
+    if (valid0) {
+        c.valid = (unsigned char*)valid0->data;
+        for (int k = 0; k < naxis; ++k)
+            c.valid_stride[k] = valid0->stride_bytes[k];
+        c.valid_bstride = valid_batch_stride;
+    }
+    c.forward_linear = affine ? forward_linear : nullptr;
+    c.max_iter = max_iter;
+    c.tol = tol;
+    const hipError_t e = launch_deform_inverse(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform inverse launch");
+    return EDHIP_OK;
+}
+
 }  // extern "C"

@@ -1649,3 +1649,153 @@ def deform_grid_labels_batch(L, displacements, mode='constant', cval=0, crop=Non
     ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``axis`` counts the axes of ONE sample; everything else
     is shared.  One launch for the batch; sample b equals the single call on sample b, bit for bit."""
     return _labels_run(L, displacements, mode, cval, crop, axis, affine, rotate, zoom, return_weight, True)
+
+
+# ---- an image carried back through the deformation (no counterpart in the reference) -----------------------------
+
+def _inverse_shapes(X_shape, Ys, batch):
+    """X_shape as one shape per input: a single shape serves every input, a list of shapes is per input"""
+    if X_shape is None:
+        raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
+    per_input = isinstance(X_shape, list) and len(X_shape) > 0 and isinstance(X_shape[0], (tuple, list))
+    if per_input and batch:
+        raise ValueError("X_shape should be the shape of ONE sample.")
+    shapes = [tuple(int(v) for v in s) for s in X_shape] if per_input else [tuple(int(v) for v in X_shape)] * len(Ys)
+    assert len(shapes) == len(Ys), 'Number of X_shape parameters should be equal to number of inputs.'
+    for s, y in zip(shapes, Ys):
+        ndim = int(y.ndim) - (1 if batch else 0)
+        if len(s) != ndim:
+            raise ValueError("X_shape should have one extent per dimension of Y (%d), but %s given."
+                             % (ndim, str(s)))
+    return shapes
+
+
+def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter, tol,
+                 return_valid, batch):
+    """Both forms of deform_grid_inverse.  Every argument check runs before the device is touched; offsets, the inverse
+    map K and the rotate / zoom centre are those of the forward call on an array of shape X_shape (the same Plan)."""
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError("max_iter should be a positive integer.")
+    if not float(tol) > 0.0:
+        raise ValueError("tol should be positive.")
+    if batch:
+        if not _host.is_array(Y) or Y.ndim < 2:
+            raise Exception('Y should be an array with a leading batch axis.')
+        Ys = [Y]
+        X_shapes = _inverse_shapes(X_shape, Ys, True)
+        plan = _batch_plan(_host.ShapeOnly((int(Y.shape[0]),) + X_shapes[0]), displacement, order, mode, cval, crop,
+                           axis, affine, rotate, zoom)
+        y_shapes = [tuple(int(v) for v in Y.shape[1:])]
+    else:
+        Ys = _host.normalize_inputs(Y)
+        X_shapes = _inverse_shapes(X_shape, Ys, False)
+        plan = _host.cached_plan([_host.ShapeOnly(s) for s in X_shapes], displacement, order, mode, cval, crop, axis,
+                                 affine, rotate, zoom)
+        y_shapes = [tuple(int(v) for v in y.shape) for y in Ys]
+    if [tuple(int(v) for v in s) for s in plan.output_shapes] != y_shapes:
+        raise ValueError("Y does not match X_shape and cropping. Expected shape of Y is %s, but %s given."
+                         % (str([tuple(s) for s in plan.output_shapes]), str(y_shapes)))
+    names = [_volume_dtype_name(y) for y in Ys]
+    if any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in names):
+        raise RuntimeError('data type not supported')     # complex, 16-bit floats
+    n = plan.naxis
+    if n > 3:
+        raise RuntimeError('deform_grid_inverse takes 1 to 3 deformed axes')   # (the library's own limit)
+    lead = (int(Y.shape[0]),) if batch else ()
+    deformed = tuple(int(v) for v in plan.deform_shape)
+    sampled = tuple(int(y_shapes[0][a]) for a in plan.axis[0])
+    degenerate = any(v == 1 for v in deformed)
+    if not degenerate and any(v < 2 for v in sampled):
+        raise ValueError("deform_grid_inverse needs at least 2 elements along every deformed axis of Y, "
+                         "but its deformed extents are %s." % str(sampled))
+
+    if degenerate:
+        # a deformed axis of X of length 1: the forward call maps every voxel to the constant and no position is
+        # defined (deform_points solves nothing there) -- cval everywhere, nothing valid
+        Zs = [_constant_result(y, lead + s, c) for y, s, c in zip(Ys, X_shapes, plan.cval)]
+        valids = [_label_fill(y, lead + deformed, 0, 'uint8') for y in Ys]
+    else:
+        K = plan.inverse_affine
+        M = numpy.linalg.inv(numpy.asarray(K, dtype=numpy.float64)[:, :n]) if K is not None else None
+        torch = _torch()
+        device = _device_for(list(Ys) + [displacement])
+        Zs, valids = [], []
+        with torch.cuda.device(device):
+            stream = _stream(device)
+            dd = _to_device(displacement, device)
+            # the control grid is prefiltered like deform_grid's (order 3, mirror, rounded to its own dtype per axis)
+            df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device, stream=stream)
+            for i, y in enumerate(Ys):
+                yd = _to_device(y, device)
+                o = int(plan.order[i])
+                ax = plan.axis[i]
+                # Y is prepared as deform_grid prepares its input: filtered along its deformed axes (deform_grid.py:155-164)
+                yf = yd
+                if prefilter and o > 1:
+                    yf = _filter_axes(yd, [a + 1 for a in ax] if batch else ax, o, False, device, stream=stream)
+                out = torch.empty(lead + X_shapes[i], dtype=yd.dtype, device=device)
+                ok = torch.empty(lead + deformed, dtype=torch.uint8, device=device) if return_valid else None
+                if batch:
+                    (y0, ys), (d0, ds), (o0, os_) = _desc_sample0(yf), _desc_sample0(df), _desc_sample0(out)
+                    v0, vs = _desc_sample0(ok) if ok is not None else (None, 0)
+                else:
+                    y0, d0, o0 = _desc(yf), _desc(df), _desc(out)
+                    v0 = _desc(ok) if ok is not None else None
+                    ys = ds = os_ = vs = 0
+                # one library call (one launch) per input: the solve is done again for each
+                _lib.deform_inverse(lead[0] if batch else 1, y0, ys, d0, ds, deformed, plan.output_offset, o0, os_, v0,
+                                    vs, ax, o, int(plan.mode[i]), float(plan.cval[i]), K, M, int(max_iter), float(tol),
+                                    0, stream)
+                Zs.append(_from_device(out, y))
+                valids.append(_from_device(ok, y) if ok is not None else None)
+    if return_valid:
+        res = list(zip(Zs, valids))
+        return res if isinstance(Y, list) else res[0]
+    return Zs if isinstance(Y, list) else Zs[0]
+
+
+def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                        axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9, return_valid=False):
+    """
+    Resample an image back through a deformation: the image-side counterpart of :func:`deform_points`.  With
+    ``Y = deform_grid(X, displacement, crop=crop, axis=axis, affine=affine, rotate=rotate, zoom=zoom)`` a pull warp,
+    ``Y[o] = X(r(o))``, this call carries ``Y`` -- or anything that lives in its frame: a prediction made on the
+    deformed image, the moving image of a fitted registration -- into the frame of ``X``.  ``X_shape`` is the shape of
+    ``X``; the result ``Z`` has that shape and ``Y``'s dtype.  For every voxel ``p`` of ``X`` along the deformed axes:
+
+    * ``q(p)`` solves ``r(q) = p`` exactly as :func:`deform_points` solves it (same start, damped Newton step, ``tol``
+      and ``max_iter``); it is a real position in ``Y``;
+    * ``Z[p] = Y(q(p))``, interpolated with the spline ``order``, boundary ``mode`` and ``cval`` the way ``deform_grid``
+      interpolates its input at a source coordinate (orders 0-5, the five legacy modes; in fp64, stored with
+      ``deform_grid``'s rounding rules for integer types).  With ``mode='constant'`` a position outside ``Y`` gives
+      ``cval``;
+    * where the iteration does not solve (``deform_points`` returns NaN there: a folding field, a singular Jacobian)
+      ``Z = cval`` in every mode.
+
+    ``return_valid=True`` returns ``(Z, valid)``: ``valid`` (uint8, the deformed extents of ``X``) is 1 exactly where
+    ``q`` was solved and lies inside ``Y`` (``0 <= q_k <= O_k - 1``) -- where ``Z`` is interpolated from inside ``Y``
+    and not extended by the boundary mode; average test-time-augmentation predictions over it.  The solve happens once
+    per voxel: every channel (non-deformed position) reuses it.
+
+    ``Y``: an array or a list of arrays (a list gives a list, of pairs with ``return_valid``; ``order``, ``mode``,
+    ``cval`` and ``axis`` may then be per-input lists as in deform_grid, and ``X_shape`` a list of shapes); 1 to 3
+    deformed axes; float32, float64, integer and bool arrays (16-bit floats raise
+    ``RuntimeError('data type not supported')``).  ``prefilter=True`` filters ``Y`` along its deformed axes for
+    ``order > 1``, as deform_grid prepares its input.  ``displacement``, ``crop``, ``axis``, ``affine``, ``rotate`` and
+    ``zoom`` are the forward call's own, checked the same way; ``Y`` must have the shape that call returns.  A deformed
+    axis of ``X`` of length 1 gives ``cval`` everywhere and nothing valid; every deformed axis of ``Y`` needs at least
+    2 elements.  numpy in gives numpy out, tensors stay on their device.  No autograd flows through this call.
+    """
+    return _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                        max_iter, tol, return_valid, False)
+
+
+def deform_grid_inverse_batch(Y, displacements, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                              axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9,
+                              return_valid=False):
+    """:func:`deform_grid_inverse` over a batch with one control grid per sample (:func:`deform_grid_batch`): ``Y``
+    ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample and ``axis`` counts
+    the axes of one sample; everything else is shared.  One launch for the batch; sample b equals the single call on
+    sample b, bit for bit (``Z`` and ``valid``)."""
+    return _inverse_run(Y, displacements, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                        max_iter, tol, return_valid, True)

@@ -27,6 +27,8 @@ from . import deform_grid_coordinates as _deform_grid_coordinates_fn
 from . import deform_points as _deform_points_fn
 # label-aware linear resampling of label maps (integer tensors stay on their device; no autograd)
 from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
+# an image resampled back through the deformation (tensors stay on their device; no autograd)
+from . import deform_grid_inverse, deform_grid_inverse_batch  # noqa: F401
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)

@@ -527,6 +527,60 @@ int edhip_deform_labels(int nbatch,
                         char* err, size_t errlen);
 
 /*
+ * An image carried back through the deformation: the image-side counterpart of edhip_deform_points(inverse) (no
+ * counterpart in the reference: the inverse of a B-spline field is not a B-spline field).  The forward call is a pull
+ * warp, Y[o] = X(r(o)) with X of deformed extents in_len and Y of deformed extents O (in_len, or the crop's shape).
+ * For every integer source position p in [0, in_len):
+ *   q(p)        the solution of r(q) = p exactly as edhip_deform_points(inverse = 1) defines it: the same start
+ *               q0 = M (p - offset - K[:, naxis]), damped Newton step, halvings, tol and max_iter; q is crop-local, a
+ *               real position in Y.
+ *   Z[p, step]  = S_Y(q(p))[step]: the gather edhip_deform applies to its input at a source coordinate, on the array
+ *               input0 with extents O -- the boundary map of `mode` per axis, the (order + 1)-wide window with mirrored
+ *               edge taps, the B-spline weights, the fp64 tap sum in the reference's tap order (deform.c:841-924, no
+ *               FMA) and the per-dtype store (deform.c:292-306,906-919).  A 'constant' coordinate outside [0, O_k - 1]
+ *               gives cval.  Where the iteration does not solve (edhip_deform_points: NaN, status 0), Z = cval in
+ *               EVERY mode.
+ *   valid[p]    1 exactly when q was solved and 0 <= q_k <= O_k - 1 on every axis (Z is interpolated from inside
+ *               input0 there), else 0.
+ * The solve happens once per voxel; every step (non-deformed position) of that voxel reuses q, the taps and weights.
+ * The batch is described once, as for edhip_deform_batch_strided: sample b's input, control grid, output and valid
+ * are sample 0's moved by b * stride bytes (nbatch = 1: a single call); everything else is shared.
+ *   input0               Y: any dtype but the 16-bit floats (EDHIP_ERR_DTYPE), any strides; spline coefficients when
+ *                        order > 1 (the caller prefilters, as for edhip_deform).  Deformed axes shorter than 2 are
+ *                        refused (EDHIP_ERR_INVALID).
+ *   displacement0        the PREFILTERED control grid (naxis, ncp_0, ...), any dtype / strides.
+ *                        EDHIP_FLAG_RAW_DISPLACEMENT is refused (EDHIP_ERR_INVALID): the caller prefilters.
+ *   in_len               host int64[naxis]: the deformed extents of X, hence of output0 (>= 2 each).
+ *   output0              Z: input0's dtype (EDHIP_ERR_DTYPE) and non-deformed axes, deformed extents in_len
+ *                        (EDHIP_ERR_INVALID), any strides.
+ *   valid0               NULL, or uint8 with output0's deformed shape (in_len): EDHIP_ERR_INVALID / EDHIP_ERR_DTYPE.
+ *   naxis, axis          1 to 3 deformed axes (more: EDHIP_ERR_UNSUPPORTED), ascending; the other axes are carried
+ *                        along as in edhip_deform.
+ *   order, mode, cval    0..5, enum edhip_mode, the constant: of the gather on input0.
+ *   output_offset, affine  as for edhip_deform: the forward call's own.
+ *   forward_linear       M = (K[:, :naxis])^-1, host double[naxis * naxis] row-major; NULL with a NULL affine.
+ *   max_iter, tol        >= 1 and > 0 (EDHIP_ERR_INVALID).
+ * Every shape, dtype and flag check answers before any launch.  One launch, one thread per source voxel, no atomics:
+ * a voxel's result depends on the call's arguments alone (a sample of a batch and a repeated call give the same
+ * bits).  The call enqueues on hip_stream, never synchronises and uses no workspace, so it can be captured into a
+ * HIP graph.
+ */
+int edhip_deform_inverse(int nbatch,
+                         const edhip_array* input0, int64_t input_batch_stride,
+                         const edhip_array* displacement0, int64_t displacement_batch_stride,
+                         const int64_t* in_len,
+                         const int64_t* output_offset,
+                         const edhip_array* output0, int64_t output_batch_stride,
+                         const edhip_array* valid0, int64_t valid_batch_stride,
+                         int naxis, const int32_t* axis,
+                         int32_t order, int32_t mode, double cval,
+                         const double* affine,
+                         const double* forward_linear,
+                         int max_iter, double tol,
+                         uint32_t flags, void* hip_stream,
+                         char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
