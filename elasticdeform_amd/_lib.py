@@ -279,37 +279,52 @@ def deform(gradient, in_descs, disp_desc, output_offset, out_descs, axis, orders
     return status
 
 
+_POINTER = {numpy.int32: ctypes.POINTER(ctypes.c_int32), numpy.int64: ctypes.POINTER(ctypes.c_int64),
+            numpy.float64: ctypes.POINTER(ctypes.c_double)}
+
+
+def _ptr(values, dtype):
+    """(typed pointer to `values` as a flat host array of `dtype`, that array) -- (None, None) for None.  The caller
+    holds on to the array until its library call has returned."""
+    if values is None:
+        return None, None
+    arr = numpy.ascontiguousarray(values, dtype=dtype).reshape(-1)
+    return arr.ctypes.data_as(_POINTER[dtype]), arr
+
+
 def _offset_affine(output_offset, inverse_affine):
     """(int64 pointer to the crop offsets, double pointer to the inverse affine, the arrays behind them) -- None for
     an argument that is None.  The caller holds on to the third value until its library call has returned."""
-    off = aff = off_arr = aff_arr = None
-    if output_offset is not None:
-        off_arr = numpy.ascontiguousarray(output_offset, dtype=numpy.int64)
-        off = off_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    if inverse_affine is not None:
-        aff_arr = numpy.ascontiguousarray(inverse_affine, dtype=numpy.float64)
-        aff = aff_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    off, off_arr = _ptr(output_offset, numpy.int64)
+    aff, aff_arr = _ptr(inverse_affine, numpy.float64)
     return off, aff, (off_arr, aff_arr)
+
+
+def _call(entry, args, flags, stream):
+    """entry(*args, flags, stream, the thread's error buffer, its size); raises what the status stands for"""
+    buf = _buf()
+    raise_for_status(entry(*args, int(flags), ctypes.c_void_p(stream), buf, 256), buf)
 
 
 def deform_batch_strided(gradient, nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset,
                          out_desc, out_bstride, axis, order, mode, cval, inverse_affine, flags, stream):
     """edhip_deform_batch_strided: the batch described once -- sample 0's descriptors plus the byte
     distance between consecutive samples of each stacked array."""
-    L = load()
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    ax, axis = _ptr(axis, numpy.int32)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    buf = ctypes.create_string_buffer(256)
-    status = L.edhip_deform_batch_strided(
-        int(bool(gradient)), int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc),
-        int(disp_bstride), off, ctypes.byref(out_desc), int(out_bstride), len(axis),
-        axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(order), int(mode), float(cval), aff,
-        int(flags), ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    _call(load().edhip_deform_batch_strided,
+          (int(bool(gradient)), int(nbatch), *_pairs(in_desc, in_bstride, disp_desc, disp_bstride), off,
+           *_pairs(out_desc, out_bstride), len(axis), ax, int(order), int(mode), float(cval), aff), flags, stream)
 
 
 def _ref(desc):
     return ctypes.byref(desc) if desc is not None else None
+
+
+def _pairs(*flat):
+    """descriptor, byte stride, descriptor, byte stride, ... as the C side takes them: each descriptor by reference
+    (None: not given / not wanted), each stride an int"""
+    return [_ref(v) if i % 2 == 0 else int(v) for i, v in enumerate(flat)]
 
 
 def _grid_gradient(entry, in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals, inverse_affine,
@@ -329,16 +344,12 @@ def _grid_gradient(entry, in_descs, disp_desc, output_offset, dout_descs, axis, 
 
 def _grid_gradient_batch_strided(entry, nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, dout_desc,
                                  dout_bstride, axis, order, mode, cval, inverse_affine, results, flags, stream):
-    """The batch form of the two gradient entry points: `results` are (descriptor by reference, byte stride) pairs,
-    flattened."""
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    """The batch form of the two gradient entry points: `results` are descriptor, byte stride, ... as for _pairs."""
+    ax, axis = _ptr(axis, numpy.int32)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    buf = ctypes.create_string_buffer(256)
-    status = entry(
-        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
-        ctypes.byref(dout_desc), int(dout_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        int(order), int(mode), float(cval), aff, *results, int(flags), ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    _call(entry, (int(nbatch), *_pairs(in_desc, in_bstride, disp_desc, disp_bstride), off,
+                  *_pairs(dout_desc, dout_bstride), len(axis), ax, int(order), int(mode), float(cval), aff,
+                  *_pairs(*results)), flags, stream)
 
 
 def deform_displacement_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
@@ -356,7 +367,7 @@ def deform_displacement_gradient_batch_strided(nbatch, in_desc, in_bstride, disp
     """edhip_deform_displacement_gradient_batch_strided: sample 0's descriptors plus byte strides."""
     _grid_gradient_batch_strided(load().edhip_deform_displacement_gradient_batch_strided, nbatch, in_desc, in_bstride,
                                  disp_desc, disp_bstride, output_offset, dout_desc, dout_bstride, axis, order, mode,
-                                 cval, inverse_affine, (ctypes.byref(ddisp_desc), int(ddisp_bstride)), flags, stream)
+                                 cval, inverse_affine, (ddisp_desc, ddisp_bstride), flags, stream)
 
 
 def deform_transform_gradient(in_descs, disp_desc, output_offset, dout_descs, axis, orders, modes, cvals,
@@ -374,9 +385,7 @@ def deform_transform_gradient_batch_strided(nbatch, in_desc, in_bstride, disp_de
     """edhip_deform_transform_gradient_batch_strided: sample 0's descriptors plus byte strides (None = not wanted)."""
     _grid_gradient_batch_strided(load().edhip_deform_transform_gradient_batch_strided, nbatch, in_desc, in_bstride,
                                  disp_desc, disp_bstride, output_offset, dout_desc, dout_bstride, axis, order, mode,
-                                 cval, inverse_affine,
-                                 (_ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc), int(dinv_bstride)), flags,
-                                 stream)
+                                 cval, inverse_affine, (ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride), flags, stream)
 
 
 def deform_points(inverse, nbatch, pts_desc, pts_bstride, disp_desc, disp_bstride, in_len, output_offset,
@@ -385,20 +394,13 @@ def deform_points(inverse, nbatch, pts_desc, pts_bstride, disp_desc, disp_bstrid
     """edhip_deform_points: the coordinate map r(q) at the points (inverse false; `jac_desc`: also its Jacobian) or
     the q with r(q) = point (inverse true; `status_desc`: 1 where solved).  Sample 0's descriptors plus byte strides;
     `disp_desc` is the PREFILTERED control grid; None = not wanted / not given."""
-    L = load()
-    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
+    lens, in_len = _ptr(in_len, numpy.int64)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    lin = lin_arr = None
-    if forward_linear is not None:
-        lin_arr = numpy.ascontiguousarray(forward_linear, dtype=numpy.float64)
-        lin = lin_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    buf = _buf()
-    status = L.edhip_deform_points(
-        int(bool(inverse)), int(nbatch), ctypes.byref(pts_desc), int(pts_bstride), ctypes.byref(disp_desc),
-        int(disp_bstride), in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, lin,
-        ctypes.byref(res_desc), int(res_bstride), _ref(jac_desc), int(jac_bstride), _ref(status_desc),
-        int(status_bstride), int(max_iter), float(tol), int(flags), ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    lin, _lin = _ptr(forward_linear, numpy.float64)
+    _call(load().edhip_deform_points,
+          (int(bool(inverse)), int(nbatch), *_pairs(pts_desc, pts_bstride, disp_desc, disp_bstride), lens, off,
+           len(in_len), aff, lin, *_pairs(res_desc, res_bstride, jac_desc, jac_bstride, status_desc, status_bstride),
+           int(max_iter), float(tol)), flags, stream)
 
 
 def deform_points_gradient(inverse, nbatch, pos_desc, pos_bstride, cot_desc, cot_bstride, status_desc, status_bstride,
@@ -409,17 +411,12 @@ def deform_points_gradient(inverse, nbatch, pos_desc, pos_bstride, cot_desc, cot
     not wanted): the per-point rows into `dpts_desc`, the gradient with respect to the PREFILTERED grid `disp_desc`
     into `ddisp_desc`, with respect to the inverse map into `dinv_desc` (float64, naxis x naxis+1).  Sample 0's
     descriptors plus byte strides."""
-    L = load()
-    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
+    lens, in_len = _ptr(in_len, numpy.int64)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    buf = _buf()
-    status = L.edhip_deform_points_gradient(
-        int(bool(inverse)), int(nbatch), ctypes.byref(pos_desc), int(pos_bstride), ctypes.byref(cot_desc),
-        int(cot_bstride), _ref(status_desc), int(status_bstride), ctypes.byref(disp_desc), int(disp_bstride),
-        in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, len(in_len), aff, _ref(dpts_desc),
-        int(dpts_bstride), _ref(ddisp_desc), int(ddisp_bstride), _ref(dinv_desc), int(dinv_bstride), int(flags),
-        ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    _call(load().edhip_deform_points_gradient,
+          (int(bool(inverse)), int(nbatch), *_pairs(pos_desc, pos_bstride, cot_desc, cot_bstride, status_desc,
+                                                    status_bstride, disp_desc, disp_bstride), lens, off, len(in_len),
+           aff, *_pairs(dpts_desc, dpts_bstride, ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride)), flags, stream)
 
 
 def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, out_desc, out_bstride,
@@ -428,16 +425,12 @@ def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_o
     with the largest sum of order-1 weights among the 2^naxis source voxels, ties to the smallest label) and, with
     `weight_desc` (float32, the output's shape; None = not wanted), the winning sum.  Sample 0's descriptors plus
     byte strides; `disp_desc` is the PREFILTERED control grid."""
-    L = load()
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    ax, axis = _ptr(axis, numpy.int32)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    buf = _buf()
-    status = L.edhip_deform_labels(
-        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride), off,
-        ctypes.byref(out_desc), int(out_bstride), _ref(weight_desc), int(weight_bstride), len(axis),
-        axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(mode), float(cval), aff, int(flags),
-        ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    _call(load().edhip_deform_labels,
+          (int(nbatch), *_pairs(in_desc, in_bstride, disp_desc, disp_bstride), off,
+           *_pairs(out_desc, out_bstride, weight_desc, weight_bstride), len(axis), ax, int(mode), float(cval), aff),
+          flags, stream)
 
 
 def deform_inverse(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, in_len, output_offset, out_desc, out_bstride,
@@ -448,22 +441,14 @@ def deform_inverse(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, in_len,
     gather of `in_desc` at q into `out_desc` (deformed extents `in_len`); `valid_desc` (uint8, shape `in_len`; None =
     not wanted): 1 where q was solved and lies inside `in_desc`.  Sample 0's descriptors plus byte strides; `disp_desc`
     is the PREFILTERED control grid."""
-    L = load()
-    in_len = numpy.ascontiguousarray(in_len, dtype=numpy.int64)
-    axis = numpy.ascontiguousarray(axis, dtype=numpy.int32).reshape(-1)
+    lens, _lens = _ptr(in_len, numpy.int64)
+    ax, axis = _ptr(axis, numpy.int32)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
-    lin = lin_arr = None
-    if forward_linear is not None:
-        lin_arr = numpy.ascontiguousarray(forward_linear, dtype=numpy.float64)
-        lin = lin_arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    buf = _buf()
-    status = L.edhip_deform_inverse(
-        int(nbatch), ctypes.byref(in_desc), int(in_bstride), ctypes.byref(disp_desc), int(disp_bstride),
-        in_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), off, ctypes.byref(out_desc), int(out_bstride),
-        _ref(valid_desc), int(valid_bstride), len(axis), axis.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        int(order), int(mode), float(cval), aff, lin, int(max_iter), float(tol), int(flags),
-        ctypes.c_void_p(stream), buf, 256)
-    raise_for_status(status, buf)
+    lin, _lin = _ptr(forward_linear, numpy.float64)
+    _call(load().edhip_deform_inverse,
+          (int(nbatch), *_pairs(in_desc, in_bstride, disp_desc, disp_bstride), lens, off,
+           *_pairs(out_desc, out_bstride, valid_desc, valid_bstride), len(axis), ax, int(order), int(mode),
+           float(cval), aff, lin, int(max_iter), float(tol)), flags, stream)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):
@@ -476,7 +461,7 @@ def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags,
     p64 = ctypes.POINTER(ctypes.c_int64)
     off, aff, _keep = _offset_affine(output_offset, inverse_affine)
     box = numpy.zeros((naxis, 2), dtype=numpy.int64)
-    buf = ctypes.create_string_buffer(256)
+    buf = _buf()
     status = L.edhip_source_box(ctypes.byref(disp_desc), in_len.ctypes.data_as(p64),
                                 out_len.ctypes.data_as(p64), off, naxis, aff, int(flags),
                                 ctypes.c_void_p(stream), box.ctypes.data_as(p64), buf, 256)

@@ -144,35 +144,18 @@ hipError_t launch_deform_points(const PointsCall& c, hipStream_t stream)
         return hipSuccess;                    // nothing to launch
     PointsArgs a;
     memset(&a, 0, sizeof(a));
-    a.g = g;
-    a.disp_bstride = c.disp_bstride;
-    a.pts = c.pts;
-    a.pts_f32 = c.pts_dtype == EDHIP_F32;
-    a.pts_bstride = c.pts_bstride;
-    a.res = c.res;
-    a.res_f32 = c.res_dtype == EDHIP_F32;
-    a.res_bstride = c.res_bstride;
-    for (int k = 0; k < 2; ++k) {
-        a.pts_stride[k] = c.pts_stride[k];
-        a.res_stride[k] = c.res_stride[k];
-    }
-    a.jac = c.inverse ? nullptr : c.jac;
-    for (int k = 0; k < 3; ++k)
-        a.jac_stride[k] = c.jac_stride[k];
-    a.jac_bstride = c.jac_bstride;
-    a.status = c.inverse ? c.status : nullptr;
-    a.status_stride = c.status_stride;
-    a.status_bstride = c.status_bstride;
+    const int64_t values = fill_points_args(a, g, c.disp_bstride, c.forward_linear, c.max_iter, c.tol);
+    unpack(c.pts, a.pts, a.pts_stride, a.pts_bstride);
+    unpack(c.res, a.res, a.res_stride, a.res_bstride);
+    unpack(c.jac, a.jac, a.jac_stride, a.jac_bstride);
+    unpack(c.status, a.status, a.status_stride, a.status_bstride);
+    a.pts_f32 = c.pts.dtype == EDHIP_F32;
+    a.res_f32 = c.res.dtype == EDHIP_F32;
+    if (c.inverse)
+        a.jac = nullptr;
+    else
+        a.status = nullptr;
     a.npts = c.npts;
-    a.max_iter = c.max_iter;
-    a.tol = c.tol;
-    int64_t values = n;
-    for (int k = 0; k < n; ++k) {
-        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
-        values *= g.ncp[k];
-        for (int l = 0; l < n; ++l)
-            a.minv[k * n + l] = c.forward_linear ? c.forward_linear[k * n + l] : (k == l ? 1.0 : 0.0);
-    }
     const size_t lds = values <= kPointsLdsValues ? (size_t)values * sizeof(double) : 0;
     switch (n) {
     case 1: return launch_points<1>(a, c.inverse, c.nbatch, lds, stream);

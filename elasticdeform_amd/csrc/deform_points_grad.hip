@@ -500,40 +500,21 @@ hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t st
     PointsGradArgs ga;
     memset(&ga, 0, sizeof(ga));
     PointsArgs& a = ga.p;
-    a.g = g;
-    a.disp_bstride = c.disp_bstride;
-    a.pts = c.pos;
-    a.pts_f32 = c.pos_dtype == EDHIP_F32;
-    a.pts_bstride = c.pos_bstride;
+    const int64_t values = fill_points_args(a, g, c.disp_bstride, nullptr, 0, 0.0);
+    unpack(c.pos, a.pts, a.pts_stride, a.pts_bstride);
+    unpack(c.cot, ga.cot, ga.cot_stride, ga.cot_bstride);
+    unpack(c.status, ga.status, ga.status_stride, ga.status_bstride);
+    unpack(c.dpts, ga.dpts, ga.dpts_stride, ga.dpts_bstride);
+    unpack(c.ddisp, ga.ddisp, ga.ddisp_stride, ga.ddisp_bstride);
+    unpack(c.dK, ga.dK, ga.dK_stride, ga.dK_bstride);
+    a.pts_f32 = c.pos.dtype == EDHIP_F32;
+    ga.cot_f32 = c.cot.dtype == EDHIP_F32;
+    ga.dpts_f32 = c.dpts.dtype == EDHIP_F32;
+    ga.ddisp_dtype = c.ddisp.dtype;
     a.npts = c.npts;
     ga.inverse = c.inverse;
-    ga.cot = c.cot;
-    ga.cot_f32 = c.cot_dtype == EDHIP_F32;
-    ga.cot_bstride = c.cot_bstride;
-    ga.dpts = c.dpts;
-    ga.dpts_f32 = c.dpts_dtype == EDHIP_F32;
-    ga.dpts_bstride = c.dpts_bstride;
-    for (int k = 0; k < 2; ++k) {
-        a.pts_stride[k] = c.pos_stride[k];
-        ga.cot_stride[k] = c.cot_stride[k];
-        ga.dpts_stride[k] = c.dpts_stride[k];
-        ga.dK_stride[k] = c.dK_stride[k];
-    }
-    ga.status = c.inverse ? c.status : nullptr;
-    ga.status_stride = c.status_stride;
-    ga.status_bstride = c.status_bstride;
-    ga.ddisp = c.ddisp;
-    ga.ddisp_dtype = c.ddisp_dtype;
-    ga.ddisp_bstride = c.ddisp_bstride;
-    for (int k = 0; k <= n; ++k)
-        ga.ddisp_stride[k] = c.ddisp_stride[k];
-    ga.dK = c.dK;
-    ga.dK_bstride = c.dK_bstride;
-    int64_t values = n;
-    for (int k = 0; k < n; ++k) {
-        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
-        values *= g.ncp[k];
-    }
+    if (!c.inverse)
+        ga.status = nullptr;
     ga.cells_per = values + n * (n + 1);
     const bool lds = values <= kPointsLdsValues;
     ga.values = lds ? (int)values : 0;

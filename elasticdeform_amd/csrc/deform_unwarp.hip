@@ -272,14 +272,11 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_kernel(PointsArgs a, co
 }
 
 template <int N>
-hipError_t launch_unwarp(const PointsArgs& a, const UnwarpView& u, int nbatch, hipStream_t stream)
+hipError_t launch_unwarp(const PointsArgs& a, const UnwarpView& u, int64_t values, int nbatch, hipStream_t stream)
 {
     const int64_t nblk = (u.nsrc + kUnwarpThreads - 1) / kUnwarpThreads;
     if (nblk > 0x7fffffffLL)
         return hipErrorInvalidValue;
-    int64_t values = N;
-    for (int k = 0; k < N; ++k)
-        values *= a.g.ncp[k];
     const dim3 grid((unsigned)nblk, (unsigned)nbatch);
     if (values <= kPointsLdsValues)
         hipLaunchKernelGGL((unwarp_kernel<N, true>), grid, dim3(kUnwarpThreads), (size_t)values * sizeof(double),
@@ -303,11 +300,9 @@ hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream)
     u.v = c.v;
     u.in_bstride = c.in_bstride;
     u.out_bstride = c.out_bstride;
-    u.valid = c.valid;
-    u.valid_bstride = c.valid_bstride;
+    unpack(c.valid, u.valid, u.valid_stride, u.valid_bstride);
     u.nsrc = 1;
     for (int k = 0; k < n; ++k) {
-        u.valid_stride[k] = c.valid_stride[k];
         u.nsrc *= g.in_len[k];
         if (g.in_len[k] < 2 || g.out_len[k] < 1)
             return hipErrorInvalidValue;
@@ -316,19 +311,11 @@ hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream)
         return hipSuccess;                    // nothing to launch
     PointsArgs a;
     memset(&a, 0, sizeof(a));
-    a.g = g;
-    a.disp_bstride = c.disp_bstride;
-    a.max_iter = c.max_iter;
-    a.tol = c.tol;
-    for (int k = 0; k < n; ++k) {
-        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
-        for (int l = 0; l < n; ++l)
-            a.minv[k * n + l] = c.forward_linear ? c.forward_linear[k * n + l] : (k == l ? 1.0 : 0.0);
-    }
+    const int64_t values = fill_points_args(a, g, c.disp_bstride, c.forward_linear, c.max_iter, c.tol);
     switch (n) {
-    case 1: return launch_unwarp<1>(a, u, c.nbatch, stream);
-    case 2: return launch_unwarp<2>(a, u, c.nbatch, stream);
-    default: return launch_unwarp<3>(a, u, c.nbatch, stream);
+    case 1: return launch_unwarp<1>(a, u, values, c.nbatch, stream);
+    case 2: return launch_unwarp<2>(a, u, values, c.nbatch, stream);
+    default: return launch_unwarp<3>(a, u, values, c.nbatch, stream);
     }
 }
 

@@ -182,24 +182,27 @@ bool dgrad_supported(const GridGeom& g);
 size_t dgrad_scratch_bytes(const GridGeom& g, int nbatch, bool dp = true, bool dk = false);
 hipError_t launch_deform_dgrad(const DgradCall& c, hipStream_t stream);
 
+// Sample 0 of an array of a strided batch, as the entry points hand it to the launchers below: sample b sits
+// b * bstride bytes after it.  All zero (ptr == nullptr): the array was not given / is not wanted.
+struct BatchArray {
+    char* ptr;
+    int dtype;
+    int64_t stride[EDHIP_MAX_DIMS];   // bytes, in the array's own dimension order
+    int64_t bstride;
+};
+
 // The coordinate map at arbitrary real positions and its inverse (deform_points.hip): one thread per point,
-// blockIdx.y = sample, fp64; no scratch, no synchronisation.  Sample b's arrays sit b * bstride bytes after sample 0's.
+// blockIdx.y = sample, fp64; no scratch, no synchronisation.
 struct PointsCall {
     GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len >= 2 on every axis
     int inverse;                  // 0: r(q) (and J); 1: q with r(q) = p
     int nbatch;
     int64_t npts;
     int64_t disp_bstride;
-    const char* pts;              // (npts, naxis), float32 / float64
-    int pts_dtype;
-    int64_t pts_stride[2], pts_bstride;
-    char* res;                    // (npts, naxis), float32 / float64
-    int res_dtype;
-    int64_t res_stride[2], res_bstride;
-    char* jac;                    // forward: float64 (npts, naxis, naxis); nullptr: not wanted
-    int64_t jac_stride[3], jac_bstride;
-    unsigned char* status;        // inverse: uint8 (npts), 1 = solved; nullptr: not wanted
-    int64_t status_stride, status_bstride;
+    BatchArray pts;               // (npts, naxis), float32 / float64 (read)
+    BatchArray res;               // (npts, naxis), float32 / float64
+    BatchArray jac;               // forward: float64 (npts, naxis, naxis); not wanted otherwise
+    BatchArray status;            // inverse: uint8 (npts), 1 = solved; not wanted otherwise
     const double* forward_linear; // inverse: host, M = (K[:, :naxis])^-1 row-major; nullptr: the identity
     int max_iter;
     double tol;
@@ -218,22 +221,12 @@ struct PointsGradCall {
     int nbatch;
     int64_t npts;
     int64_t disp_bstride;
-    const char* pos;              // (npts, naxis) float32 / float64: q
-    int pos_dtype;
-    int64_t pos_stride[2], pos_bstride;
-    const char* cot;              // (npts, naxis) float32 / float64
-    int cot_dtype;
-    int64_t cot_stride[2], cot_bstride;
-    const unsigned char* status;  // inverse: uint8 (npts), 0 = not solved (contributes nothing); nullptr: all solved
-    int64_t status_stride, status_bstride;
-    char* dpts;                   // (npts, naxis) float32 / float64; nullptr: not wanted
-    int dpts_dtype;
-    int64_t dpts_stride[2], dpts_bstride;
-    char* ddisp;                  // the grid's shape, a floating dtype; nullptr: not wanted
-    int ddisp_dtype;
-    int64_t ddisp_stride[kMaxAxes + 1], ddisp_bstride;
-    char* dK;                     // float64 (naxis, naxis + 1); nullptr: not wanted
-    int64_t dK_stride[2], dK_bstride;
+    BatchArray pos;               // (npts, naxis) float32 / float64: q (read)
+    BatchArray cot;               // (npts, naxis) float32 / float64 (read)
+    BatchArray status;            // inverse: uint8 (npts), 0 = not solved (contributes nothing; read); not given: all solved
+    BatchArray dpts;              // (npts, naxis) float32 / float64
+    BatchArray ddisp;             // the grid's shape, a floating dtype
+    BatchArray dK;                // float64 (naxis, naxis + 1)
     char* scratch;
 };
 size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts);
@@ -266,9 +259,7 @@ struct InverseCall {
     IOView v;                     // sample 0: v.in = Y (read, extents O), v.out = Z (written, extents I); order, mode, cval
     int nbatch;
     int64_t in_bstride, out_bstride, disp_bstride;   // bytes between samples
-    unsigned char* valid;         // uint8, deformed extents I: 1 = solved and inside Y; nullptr: not wanted
-    int64_t valid_stride[kMaxAxes];
-    int64_t valid_bstride;
+    BatchArray valid;             // uint8, deformed extents I: 1 = solved and inside Y
     const double* forward_linear; // host, M = (K[:, :naxis])^-1 row-major; nullptr: the identity
     int max_iter;
     double tol;

@@ -39,6 +39,44 @@ struct PointsArgs {
     double tol;
 };
 
+// ---- host: what the three launchers share ----------------------------------------------------------------------------
+// The part of PointsArgs that every launcher fills alike: g, disp_bstride, scale, minv, max_iter, tol.  Returns the
+// number of control-grid values, naxis prod ncp_k (up to kPointsLdsValues of them are staged in LDS).
+inline int64_t fill_points_args(PointsArgs& a, const GridGeom& g, int64_t disp_bstride, const double* forward_linear,
+                                int max_iter, double tol)
+{
+    const int n = g.naxis;
+    a.g = g;
+    a.disp_bstride = disp_bstride;
+    a.max_iter = max_iter;
+    a.tol = tol;
+    int64_t values = n;
+    for (int k = 0; k < n; ++k) {
+        a.scale[k] = (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1);
+        values *= g.ncp[k];
+        for (int l = 0; l < n; ++l)
+            a.minv[k * n + l] = forward_linear ? forward_linear[k * n + l] : (k == l ? 1.0 : 0.0);
+    }
+    return values;
+}
+
+// a BatchArray into the (pointer, strides, batch stride) fields of a kernel argument block
+template <typename P, int R>
+inline void unpack(const BatchArray& s, P*& ptr, int64_t (&stride)[R], int64_t& bstride)
+{
+    ptr = (P*)s.ptr;
+    for (int k = 0; k < R; ++k)
+        stride[k] = s.stride[k];
+    bstride = s.bstride;
+}
+template <typename P>
+inline void unpack(const BatchArray& s, P*& ptr, int64_t& stride, int64_t& bstride)
+{
+    ptr = (P*)s.ptr;
+    stride = s.stride[0];
+    bstride = s.bstride;
+}
+
 constexpr int ipow4(int e) { return e == 0 ? 1 : 4 * ipow4(e - 1); }
 
 // a[t] for a runtime t without indexing a register array dynamically

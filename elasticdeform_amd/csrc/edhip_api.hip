@@ -78,6 +78,95 @@ int check_displacement(const edhip_array* d, int naxis, int64_t* points, char* e
     return EDHIP_OK;
 }
 
+// ---- what the strided-batch calls on the prefiltered grid share (points, their gradient, labels, inverse) -----------
+// the preamble: an empty message; a negative batch or a missing required argument is refused
+int check_batch_call(int nbatch, bool required_given, char* err, size_t errlen)
+{
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch < 0 || !required_given)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    return EDHIP_OK;
+}
+
+// the image-side calls: an axis list of 1 to 3 deformed axes
+int check_axes_1_to_3(const char* entry, const int32_t* axis, int naxis, char* err, size_t errlen)
+{
+    if (!axis || naxis < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
+    if (naxis > 3)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "%s takes 1 to 3 deformed axes", entry);
+    return EDHIP_OK;
+}
+
+int check_prefiltered(const char* entry, uint32_t flags, char* err, size_t errlen)
+{
+    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "%s takes the prefiltered control grid", entry);
+    return EDHIP_OK;
+}
+
+// blockIdx.y carries the sample
+int check_batch_limit(const char* entry, int nbatch, char* err, size_t errlen)
+{
+    if (nbatch > 65535)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "%s: too many samples", entry);
+    return EDHIP_OK;
+}
+
+// exactly this rank (at most EDHIP_MAX_DIMS) and these extents
+bool has_shape(const edhip_array* a, int ndim, const int64_t* shape)
+{
+    bool same = a->ndim == ndim;
+    for (int d = 0; same && d < ndim; ++d)
+        same = a->shape[d] == shape[d];
+    return same;
+}
+
+bool f32_or_f64(const edhip_array* a) { return a->dtype == EDHIP_F32 || a->dtype == EDHIP_F64; }
+
+// the optional solved-mask of the inverse direction: uint8 (npts)
+int check_status(const edhip_array* status, bool inverse, int64_t npts, char* err, size_t errlen)
+{
+    if (!status)
+        return EDHIP_OK;
+    if (!inverse)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "the status belongs to the inverse direction");
+    if (!has_shape(status, 1, &npts))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "status must have shape (N)");
+    if (status->dtype != EDHIP_U8)
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "status must be uint8");
+    return EDHIP_OK;
+}
+
+// the controls of the Newton iteration, and the inverse of the affine map's linear part it starts from
+int check_iteration(int max_iter, double tol, const double* affine, const double* forward_linear, char* err,
+                    size_t errlen)
+{
+    if (max_iter < 1)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "max_iter must be at least 1");
+    if (!(tol > 0.0))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "tol must be positive");
+    if (affine && !forward_linear)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
+    return EDHIP_OK;
+}
+
+// sample 0's array and the byte distance between samples, as the launchers take them; nullptr: a zeroed struct
+ed::BatchArray batch_array(const edhip_array* a, int64_t bstride)
+{
+    ed::BatchArray s;
+    memset(&s, 0, sizeof(s));
+    if (a) {
+        s.ptr = (char*)a->data;
+        s.dtype = a->dtype;
+        for (int d = 0; d < a->ndim && d < EDHIP_MAX_DIMS; ++d)
+            s.stride[d] = a->stride_bytes[d];
+        s.bstride = bstride;
+    }
+    return s;
+}
+
 // the checks of _deform_grid.c:121-255 on the input/output pairs of edhip_deform and of its gradients (float_only:
 // floating-point volumes only -- the derivative of an integer volume's rounded result is not defined)
 int check_pairs(const edhip_array* inputs, const edhip_array* outputs, int ninputs, int naxis, const int32_t* axis,
@@ -1270,51 +1359,37 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
 {
     using namespace ed;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (err && errlen)
-        err[0] = 0;
-    if (nbatch < 0 || !points0 || !displacement0 || !result0 || !in_len)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (int st = check_batch_call(nbatch, points0 && displacement0 && result0 && in_len, err, errlen))
+        return st;
     if (int st = check_naxis(naxis, err, errlen))
         return st;
-    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_points takes the prefiltered control grid");
+    if (int st = check_prefiltered("edhip_deform_points", flags, err, errlen))
+        return st;
     if (points0->ndim != 2 || points0->shape[1] != naxis || points0->shape[0] < 0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "points must have shape (N, naxis)");
-    if (result0->ndim != 2 || result0->shape[0] != points0->shape[0] || result0->shape[1] != naxis)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "result must have the shape of points");
-    if ((points0->dtype != EDHIP_F32 && points0->dtype != EDHIP_F64) ||
-        (result0->dtype != EDHIP_F32 && result0->dtype != EDHIP_F64))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     const int64_t npts = points0->shape[0];
+    const int64_t rows[3] = {npts, naxis, naxis};            // (N, naxis) and (N, naxis, naxis)
+    if (!has_shape(result0, 2, rows))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "result must have the shape of points");
+    if (!f32_or_f64(points0) || !f32_or_f64(result0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     if (jacobian0) {
         if (inverse)
             return fail(err, errlen, EDHIP_ERR_INVALID, "the jacobian belongs to the forward direction");
-        if (jacobian0->ndim != 3 || jacobian0->shape[0] != npts || jacobian0->shape[1] != naxis ||
-            jacobian0->shape[2] != naxis)
+        if (!has_shape(jacobian0, 3, rows))
             return fail(err, errlen, EDHIP_ERR_INVALID, "jacobian must have shape (N, naxis, naxis)");
         if (jacobian0->dtype != EDHIP_F64)
             return fail(err, errlen, EDHIP_ERR_DTYPE, "jacobian must be float64");
     }
-    if (status0) {
-        if (!inverse)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "the status belongs to the inverse direction");
-        if (status0->ndim != 1 || status0->shape[0] != npts)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "status must have shape (N)");
-        if (status0->dtype != EDHIP_U8)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "status must be uint8");
-    }
-    if (inverse) {
-        if (max_iter < 1)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "max_iter must be at least 1");
-        if (!(tol > 0.0))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "tol must be positive");
-        if (affine && !forward_linear)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
-    }
+    if (int st = check_status(status0, inverse != 0, npts, err, errlen))
+        return st;
+    if (inverse)
+        if (int st = check_iteration(max_iter, tol, affine, forward_linear, err, errlen))
+            return st;
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
-    if (nbatch > 65535)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_points: too many samples");
+    if (int st = check_batch_limit("edhip_deform_points", nbatch, err, errlen))
+        return st;
     PointsCall c;
     memset(&c, 0, sizeof(c));
     if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
@@ -1325,27 +1400,10 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
     c.nbatch = nbatch;
     c.npts = npts;
     c.disp_bstride = displacement_batch_stride;
-    c.pts = (const char*)points0->data;
-    c.pts_dtype = points0->dtype;
-    c.pts_bstride = points_batch_stride;
-    c.res = (char*)result0->data;
-    c.res_dtype = result0->dtype;
-    c.res_bstride = result_batch_stride;
-    for (int k = 0; k < 2; ++k) {
-        c.pts_stride[k] = points0->stride_bytes[k];
-        c.res_stride[k] = result0->stride_bytes[k];
-    }
-    if (jacobian0) {
-        c.jac = (char*)jacobian0->data;
-        for (int k = 0; k < 3; ++k)
-            c.jac_stride[k] = jacobian0->stride_bytes[k];
-        c.jac_bstride = jacobian_batch_stride;
-    }
-    if (status0) {
-        c.status = (unsigned char*)status0->data;
-        c.status_stride = status0->stride_bytes[0];
-        c.status_bstride = status_batch_stride;
-    }
+    c.pts = batch_array(points0, points_batch_stride);
+    c.res = batch_array(result0, result_batch_stride);
+    c.jac = batch_array(jacobian0, jacobian_batch_stride);
+    c.status = batch_array(status0, status_batch_stride);
     c.forward_linear = affine ? forward_linear : nullptr;
     c.max_iter = max_iter;
     c.tol = tol;
@@ -1369,60 +1427,47 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
 {
     using namespace ed;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (err && errlen)
-        err[0] = 0;
-    if (nbatch < 0 || !positions0 || !cotangent0 || !displacement0 || !in_len)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
+    if (int st = check_batch_call(nbatch, positions0 && cotangent0 && displacement0 && in_len, err, errlen))
+        return st;
     if (int st = check_naxis(naxis, err, errlen))
         return st;
-    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
-        return fail(err, errlen, EDHIP_ERR_INVALID,
-                    "edhip_deform_points_gradient takes the prefiltered control grid");
+    if (int st = check_prefiltered("edhip_deform_points_gradient", flags, err, errlen))
+        return st;
     if (!dpoints0 && !ddisplacement0 && !dinverse_affine0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested");
     if (positions0->ndim != 2 || positions0->shape[1] != naxis || positions0->shape[0] < 0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "positions must have shape (N, naxis)");
     const int64_t npts = positions0->shape[0];
-    if (cotangent0->ndim != 2 || cotangent0->shape[0] != npts || cotangent0->shape[1] != naxis)
+    const int64_t rows[2] = {npts, naxis}, map[2] = {naxis, naxis + 1};
+    if (!has_shape(cotangent0, 2, rows))
         return fail(err, errlen, EDHIP_ERR_INVALID, "cotangent must have the shape of positions");
-    const auto f32_or_f64 = [](const edhip_array* a) { return a->dtype == EDHIP_F32 || a->dtype == EDHIP_F64; };
     if (!f32_or_f64(positions0) || !f32_or_f64(cotangent0))
         return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    if (status0) {
-        if (!inverse)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "the status belongs to the inverse direction");
-        if (status0->ndim != 1 || status0->shape[0] != npts)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "status must have shape (N)");
-        if (status0->dtype != EDHIP_U8)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "status must be uint8");
-    }
+    if (int st = check_status(status0, inverse != 0, npts, err, errlen))
+        return st;
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
     if (dpoints0) {
-        if (dpoints0->ndim != 2 || dpoints0->shape[0] != npts || dpoints0->shape[1] != naxis)
+        if (!has_shape(dpoints0, 2, rows))
             return fail(err, errlen, EDHIP_ERR_INVALID, "dpoints must have the shape of positions");
         if (!f32_or_f64(dpoints0))
             return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     }
     if (ddisplacement0) {
-        bool same = ddisplacement0->ndim == displacement0->ndim;
-        for (int k = 0; same && k <= naxis; ++k)
-            same = ddisplacement0->shape[k] == displacement0->shape[k];
-        if (!same)
+        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
             return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
         const int dt = ddisplacement0->dtype;
         if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
             return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
     }
     if (dinverse_affine0) {
-        if (dinverse_affine0->ndim != 2 || dinverse_affine0->shape[0] != naxis ||
-            dinverse_affine0->shape[1] != naxis + 1)
+        if (!has_shape(dinverse_affine0, 2, map))
             return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
         if (dinverse_affine0->dtype != EDHIP_F64)
             return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
     }
-    if (nbatch > 65535)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_points_gradient: too many samples");
+    if (int st = check_batch_limit("edhip_deform_points_gradient", nbatch, err, errlen))
+        return st;
     PointsGradCall c;
     memset(&c, 0, sizeof(c));
     if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
@@ -1433,41 +1478,12 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
     c.nbatch = nbatch;
     c.npts = npts;
     c.disp_bstride = displacement_batch_stride;
-    c.pos = (const char*)positions0->data;
-    c.pos_dtype = positions0->dtype;
-    c.pos_bstride = positions_batch_stride;
-    c.cot = (const char*)cotangent0->data;
-    c.cot_dtype = cotangent0->dtype;
-    c.cot_bstride = cotangent_batch_stride;
-    for (int k = 0; k < 2; ++k) {
-        c.pos_stride[k] = positions0->stride_bytes[k];
-        c.cot_stride[k] = cotangent0->stride_bytes[k];
-    }
-    if (status0) {
-        c.status = (const unsigned char*)status0->data;
-        c.status_stride = status0->stride_bytes[0];
-        c.status_bstride = status_batch_stride;
-    }
-    if (dpoints0) {
-        c.dpts = (char*)dpoints0->data;
-        c.dpts_dtype = dpoints0->dtype;
-        c.dpts_stride[0] = dpoints0->stride_bytes[0];
-        c.dpts_stride[1] = dpoints0->stride_bytes[1];
-        c.dpts_bstride = dpoints_batch_stride;
-    }
-    if (ddisplacement0) {
-        c.ddisp = (char*)ddisplacement0->data;
-        c.ddisp_dtype = ddisplacement0->dtype;
-        for (int k = 0; k <= naxis; ++k)
-            c.ddisp_stride[k] = ddisplacement0->stride_bytes[k];
-        c.ddisp_bstride = ddisplacement_batch_stride;
-    }
-    if (dinverse_affine0) {
-        c.dK = (char*)dinverse_affine0->data;
-        c.dK_stride[0] = dinverse_affine0->stride_bytes[0];
-        c.dK_stride[1] = dinverse_affine0->stride_bytes[1];
-        c.dK_bstride = dinverse_affine_batch_stride;
-    }
+    c.pos = batch_array(positions0, positions_batch_stride);
+    c.cot = batch_array(cotangent0, cotangent_batch_stride);
+    c.status = batch_array(status0, status_batch_stride);
+    c.dpts = batch_array(dpoints0, dpoints_batch_stride);
+    c.ddisp = batch_array(ddisplacement0, ddisplacement_batch_stride);
+    c.dK = batch_array(dinverse_affine0, dinverse_affine_batch_stride);
     // cells, maxima, flags and the per-point u rows: the stream's workspace, behind its grid head
     StreamGuard guard(stream);
     hipError_t e = hipSuccess;
@@ -1491,16 +1507,12 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
 {
     using namespace ed;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (err && errlen)
-        err[0] = 0;
-    if (nbatch < 0 || !input0 || !displacement0 || !output0)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
-    if (!axis || naxis < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > 3)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_labels takes 1 to 3 deformed axes");
-    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_labels takes the prefiltered control grid");
+    if (int st = check_batch_call(nbatch, input0 && displacement0 && output0, err, errlen))
+        return st;
+    if (int st = check_axes_1_to_3("edhip_deform_labels", axis, naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered("edhip_deform_labels", flags, err, errlen))
+        return st;
     const edhip_array& in = *input0;
     const edhip_array& out = *output0;
     if (in.ndim != out.ndim)
@@ -1518,10 +1530,7 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
     if (weight0) {
-        bool same = weight0->ndim == out.ndim;
-        for (int d = 0; same && d < out.ndim; ++d)
-            same = weight0->shape[d] == out.shape[d];
-        if (!same)
+        if (!has_shape(weight0, out.ndim, out.shape))
             return fail(err, errlen, EDHIP_ERR_INVALID, "weight must have the shape of the output");
         if (weight0->dtype != EDHIP_F32)
             return fail(err, errlen, EDHIP_ERR_DTYPE, "weight must be float32");
@@ -1546,8 +1555,8 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
             return fail(err, errlen, EDHIP_ERR_INVALID, "cval must be an integer value of the label map's dtype");
         cval_bits = lo < 0.0 ? (uint64_t)(int64_t)cval : (uint64_t)cval;
     }
-    if (nbatch > 65535)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_labels: too many samples");
+    if (int st = check_batch_limit("edhip_deform_labels", nbatch, err, errlen))
+        return st;
     LabelsCall c;
     memset(&c, 0, sizeof(c));
     {
@@ -1594,16 +1603,12 @@ int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_ba
 {
     using namespace ed;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (err && errlen)
-        err[0] = 0;
-    if (nbatch < 0 || !input0 || !displacement0 || !output0 || !in_len)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid batch");
-    if (!axis || naxis < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis list");
-    if (naxis > 3)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_inverse takes 1 to 3 deformed axes");
-    if (flags & EDHIP_FLAG_RAW_DISPLACEMENT)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "edhip_deform_inverse takes the prefiltered control grid");
+    if (int st = check_batch_call(nbatch, input0 && displacement0 && output0 && in_len, err, errlen))
+        return st;
+    if (int st = check_axes_1_to_3("edhip_deform_inverse", axis, naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered("edhip_deform_inverse", flags, err, errlen))
+        return st;
     const edhip_array& in = *input0;
     const edhip_array& out = *output0;
     if (int st = check_pairs(input0, output0, 1, naxis, axis, &order, &mode, &cval, false, err, errlen))
@@ -1624,24 +1629,17 @@ int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_ba
             return fail(err, errlen, EDHIP_ERR_INVALID, "deformed axes must have at least 2 elements");
     }
     if (valid0) {
-        bool same = valid0->ndim == naxis;
-        for (int k = 0; same && k < naxis; ++k)
-            same = valid0->shape[k] == in_len[k];
-        if (!same)
+        if (!has_shape(valid0, naxis, in_len))
             return fail(err, errlen, EDHIP_ERR_INVALID, "valid must have the output's deformed shape");
         if (valid0->dtype != EDHIP_U8)
             return fail(err, errlen, EDHIP_ERR_DTYPE, "valid must be uint8");
     }
-    if (max_iter < 1)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "max_iter must be at least 1");
-    if (!(tol > 0.0))
-        return fail(err, errlen, EDHIP_ERR_INVALID, "tol must be positive");
-    if (affine && !forward_linear)
-        return fail(err, errlen, EDHIP_ERR_INVALID, "forward_linear is required with an affine map");
+    if (int st = check_iteration(max_iter, tol, affine, forward_linear, err, errlen))
+        return st;
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
-    if (nbatch > 65535)
-        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "edhip_deform_inverse: too many samples");
+    if (int st = check_batch_limit("edhip_deform_inverse", nbatch, err, errlen))
+        return st;
     InverseCall c;
     memset(&c, 0, sizeof(c));
     // the solve's geometry is the forward call's (extents in_len); the sampled array has the input's own extents
@@ -1655,12 +1653,7 @@ int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_ba
     c.in_bstride = input_batch_stride;
     c.out_bstride = output_batch_stride;
     c.disp_bstride = displacement_batch_stride;
-    if (valid0) {
-        c.valid = (unsigned char*)valid0->data;
-        for (int k = 0; k < naxis; ++k)
-            c.valid_stride[k] = valid0->stride_bytes[k];
-        c.valid_bstride = valid_batch_stride;
-    }
+    c.valid = batch_array(valid0, valid_batch_stride);
     c.forward_linear = affine ? forward_linear : nullptr;
     c.max_iter = max_iter;
     c.tol = tol;

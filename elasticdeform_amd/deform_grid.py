@@ -1192,12 +1192,72 @@ def _as_points(points):
     return points.detach().to(torch.float64)
 
 
-def _points_fill(like, shape, value, dtype_name):
-    """an array of `shape` in the family and on the device of `like`"""
+def _fill(like, shape, value, dtype=None):
+    """an array of `shape` filled with `value`, in the family and on the device of `like`; `like`'s dtype unless given"""
+    shape = tuple(int(v) for v in shape)
     if isinstance(like, numpy.ndarray):
-        return numpy.full(shape, value, dtype=dtype_name)
+        return numpy.full(shape, value, dtype=like.dtype if dtype is None else dtype)
     torch = _torch()
-    return torch.full(shape, value, dtype=getattr(torch, dtype_name), device=like.device)
+    return torch.full(shape, value, dtype=like.dtype if dtype is None else getattr(torch, dtype), device=like.device)
+
+
+def _check_iteration(max_iter, tol):
+    if int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError("max_iter should be a positive integer.")
+    if not float(tol) > 0.0:
+        raise ValueError("tol should be positive.")
+
+
+def _plan_of(arrays, batch, displacement, order, mode, cval, crop, axis, affine, rotate, zoom):
+    """the Plan of deform_grid on `arrays` (or _host.ShapeOnly stand-ins): a list of inputs, or [the stacked batch]"""
+    if batch:
+        return _batch_plan(arrays[0], displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
+    return _host.cached_plan(arrays, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
+
+
+def _shape_only(shape, nbatch=None):
+    """[the stand-in of an array of `shape` -- of a stacked batch of `nbatch` of them --] for _plan_of"""
+    return [_host.ShapeOnly(((int(nbatch),) if nbatch is not None else ()) + tuple(shape))]
+
+
+def _grid_axes(dd, batch):
+    return range(2 if batch else 1, dd.ndim)
+
+
+def _prefiltered_grid(dd, batch, device, stream):
+    """the control grid prefiltered like deform_grid's (order 3, mirror, rounded to its own dtype per axis)"""
+    return _filter_axes(dd, _grid_axes(dd, batch), 3, False, device, stream=stream)
+
+
+def _sample(t, batch):
+    """(descriptor of t -- of sample 0 of a stacked t --, byte distance between samples); (None, 0) for None"""
+    if t is None:
+        return None, 0
+    return _desc_sample0(t) if batch else (_desc(t), 0)
+
+
+def _forward_linear(K, n):
+    """M = (K[:, :n])^-1, where the Newton iteration starts; None without an affine map"""
+    return numpy.linalg.inv(numpy.asarray(K, dtype=numpy.float64)[:, :n]) if K is not None else None
+
+
+def _list_or_one(results, extras, paired, like):
+    """a list in gives a list out; with `paired`, (result, extra) pairs"""
+    out = list(zip(results, extras)) if paired else results
+    return out if isinstance(like, list) else out[0]
+
+
+def _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom):
+    """(Plan of the image call on an array of X_shape, naxis, the leading dimensions of the points)"""
+    if batch and pts.ndim != 3:
+        raise ValueError("points should have shape (batch, N, naxis).")
+    plan = _plan_of(_shape_only(X_shape, pts.shape[0] if batch else None), batch, displacement, 3, 'constant', 0.0,
+                    crop, axis, affine, rotate, zoom)
+    n = plan.naxis
+    if pts.ndim < 1 or int(pts.shape[-1]) != n:
+        raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
+                         "but their shape is %s." % (n, str(tuple(pts.shape))))
+    return plan, n, tuple(int(v) for v in pts.shape[:-1])
 
 
 def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, jacobian, max_iter, tol,
@@ -1208,61 +1268,34 @@ def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom,
     if X_shape is None:
         raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
     if inverse:
-        if int(max_iter) != max_iter or int(max_iter) < 1:
-            raise ValueError("max_iter should be a positive integer.")
-        if not float(tol) > 0.0:
-            raise ValueError("tol should be positive.")
+        _check_iteration(max_iter, tol)
     X_shape = tuple(int(v) for v in X_shape)
     pts = _as_points(points)
-    if batch:
-        if pts.ndim != 3:
-            raise ValueError("points should have shape (batch, N, naxis).")
-        plan = _batch_plan(_host.ShapeOnly((int(pts.shape[0]),) + X_shape), displacement, 3, 'constant', 0.0, crop,
-                           axis, affine, rotate, zoom)
-    else:
-        plan = _host.cached_plan([_host.ShapeOnly(X_shape)], displacement, 3, 'constant', 0.0, crop, axis, affine,
-                                 rotate, zoom)
-    n = plan.naxis
-    if pts.ndim < 1 or int(pts.shape[-1]) != n:
-        raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
-                         "but their shape is %s." % (n, str(tuple(pts.shape))))
-    lead = tuple(int(v) for v in pts.shape[:-1])
-    name = _volume_dtype_name(pts)
+    plan, n, lead = _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom)
 
     if any(int(d) == 1 for d in plan.deform_shape):
         # a deformed axis of length 1: the control coordinate divides by I - 1 = 0 (the image call maps every voxel
         # to cval there) -- no coordinate is defined and nothing converges
-        return (_points_fill(pts, lead + (n,), float('nan'), name),
-                _points_fill(pts, lead + (n, n), float('nan'), 'float64') if jacobian else None,
-                _points_fill(pts, lead, False, 'bool') if inverse else None)
+        return (_fill(pts, lead + (n,), float('nan')),
+                _fill(pts, lead + (n, n), float('nan'), 'float64') if jacobian else None,
+                _fill(pts, lead, False, 'bool') if inverse else None)
 
     K = plan.inverse_affine
-    M = numpy.linalg.inv(numpy.asarray(K, dtype=numpy.float64)[:, :n]) if (inverse and K is not None) else None
+    M = _forward_linear(K, n) if inverse else None
     torch = _torch()
     device = _device_for([pts, displacement])
     with torch.cuda.device(device):
+        stream = _stream(device)
         pd = _to_device(pts, device)
         if not batch:
             pd = pd.reshape(-1, n)
-        dd = _to_device(displacement, device)
-        # the control grid is prefiltered like the image call's (order 3, mirror, rounded to its own dtype per axis)
-        df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device)
+        df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
         res = torch.empty(tuple(pd.shape), dtype=pd.dtype, device=device)
         jac = torch.empty(tuple(pd.shape) + (n,), dtype=torch.float64, device=device) if jacobian else None
         ok = torch.empty(tuple(pd.shape[:-1]), dtype=torch.uint8, device=device) if inverse else None
-        if batch:
-            nb = int(pd.shape[0])
-            (p0, ps), (d0, ds), (r0, rs) = _desc_sample0(pd), _desc_sample0(df), _desc_sample0(res)
-            j0, js = _desc_sample0(jac) if jac is not None else (None, 0)
-            s0, ss = _desc_sample0(ok) if ok is not None else (None, 0)
-        else:
-            nb = 1
-            p0, d0, r0 = _desc(pd), _desc(df), _desc(res)
-            j0 = _desc(jac) if jac is not None else None
-            s0 = _desc(ok) if ok is not None else None
-            ps = ds = rs = js = ss = 0
-        _lib.deform_points(inverse, nb, p0, ps, d0, ds, plan.deform_shape, plan.output_offset, K, M, r0, rs, j0, js,
-                           s0, ss, int(max_iter), float(tol), 0, _stream(device))
+        _lib.deform_points(inverse, lead[0] if batch else 1, *_sample(pd, batch), *_sample(df, batch),
+                           plan.deform_shape, plan.output_offset, K, M, *_sample(res, batch), *_sample(jac, batch),
+                           *_sample(ok, batch), int(max_iter), float(tol), 0, stream)
         res = _from_device(res.reshape(lead + (n,)), pts)
         if jac is not None:
             jac = _from_device(jac.reshape(lead + (n, n)), pts)
@@ -1360,25 +1393,11 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
     if X_shape is None:
         raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
     if inverse and positions is None:
-        if int(max_iter) != max_iter or int(max_iter) < 1:
-            raise ValueError("max_iter should be a positive integer.")
-        if not float(tol) > 0.0:
-            raise ValueError("tol should be positive.")
+        _check_iteration(max_iter, tol)
     X_shape = tuple(int(v) for v in X_shape)
     pts = _as_points(points)
     cot = _as_points(cotangent)
-    if batch:
-        if pts.ndim != 3:
-            raise ValueError("points should have shape (batch, N, naxis).")
-        plan = _batch_plan(_host.ShapeOnly((int(pts.shape[0]),) + X_shape), displacement, 3, 'constant', 0.0, crop,
-                           axis, affine, rotate, zoom)
-    else:
-        plan = _host.cached_plan([_host.ShapeOnly(X_shape)], displacement, 3, 'constant', 0.0, crop, axis, affine,
-                                 rotate, zoom)
-    n = plan.naxis
-    if pts.ndim < 1 or int(pts.shape[-1]) != n:
-        raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
-                         "but their shape is %s." % (n, str(tuple(pts.shape))))
+    plan, n, lead = _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom)
     if tuple(int(v) for v in cot.shape) != tuple(int(v) for v in pts.shape):
         raise ValueError("The cotangent should have the shape of the points, %s, but its shape is %s."
                          % (str(tuple(pts.shape)), str(tuple(cot.shape))))
@@ -1389,8 +1408,6 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
                              % (str(tuple(pts.shape)), str(tuple(positions.shape))))
     if want_map and zoom is not None and float(zoom) == 0:
         raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
-    lead = tuple(int(v) for v in pts.shape[:-1])
-    name = _volume_dtype_name(pts)
     dk_shape = ((lead[0],) if batch else ()) + (n, n + 1)
     torch = _torch()
 
@@ -1399,7 +1416,7 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
         dk = None
         if want_map:
             dk = torch.zeros(dk_shape, dtype=torch.float64, device=pts.device if torch.is_tensor(pts) else 'cpu')
-        return (plan, _points_fill(pts, lead + (n,), 0.0, name) if want_points else None,
+        return (plan, _fill(pts, lead + (n,), 0.0) if want_points else None,
                 _dgrad_zeros(displacement, pts) if want_disp else None, dk)
 
     device = _device_for([pts, cot, displacement])
@@ -1424,31 +1441,18 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
         if not batch:
             qd, cd = qd.reshape(-1, n), cd.reshape(-1, n)
             ok = ok.reshape(-1) if ok is not None else None
-        grid_axes = range(2 if batch else 1, dd.ndim)
-        # the control grid is prefiltered as the forward call prefilters it
-        df = _filter_axes(dd, grid_axes, 3, False, device, stream=stream)
+        df = _prefiltered_grid(dd, batch, device, stream)
         rows = torch.empty(tuple(qd.shape), dtype=pd.dtype, device=device) if want_points else None
         dp = torch.empty(tuple(int(v) for v in dd.shape), dtype=torch.float64, device=device) if want_disp else None
         dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
-        none = (None, 0)
-        if batch:
-            nb = int(qd.shape[0])
-            (q0, qs), (c0, cs), (d0, ds) = _desc_sample0(qd), _desc_sample0(cd), _desc_sample0(df)
-            (s0, ss) = _desc_sample0(ok) if ok is not None else none
-            (r0, rs) = _desc_sample0(rows) if rows is not None else none
-            (p0, ps) = _desc_sample0(dp) if dp is not None else none
-            (k0, ks) = _desc_sample0(dk) if dk is not None else none
-        else:
-            nb = 1
-            q0, c0, d0 = _desc(qd), _desc(cd), _desc(df)
-            s0, r0, p0, k0 = [_desc(t) if t is not None else None for t in (ok, rows, dp, dk)]
-            qs = cs = ds = ss = rs = ps = ks = 0
-        _lib.deform_points_gradient(inverse, nb, q0, qs, c0, cs, s0, ss, d0, ds, plan.deform_shape,
-                                    plan.output_offset, plan.inverse_affine, r0, rs, p0, ps, k0, ks, 0, stream)
+        _lib.deform_points_gradient(inverse, lead[0] if batch else 1, *_sample(qd, batch), *_sample(cd, batch),
+                                    *_sample(ok, batch), *_sample(df, batch), plan.deform_shape, plan.output_offset,
+                                    plan.inverse_affine, *_sample(rows, batch), *_sample(dp, batch),
+                                    *_sample(dk, batch), 0, stream)
         out = None
         if dp is not None:
             # dD = (order-3 mirror prefilter)^T dP in fp64, rounded once to the result's dtype
-            dp = _filter_axes(dp, grid_axes, 3, True, device, overwrite=True, stream=stream)
+            dp = _filter_axes(dp, _grid_axes(dd, batch), 3, True, device, overwrite=True, stream=stream)
             out = _from_device(dp.to(_result_tensor_dtype(displacement)), pts)
         if rows is not None:
             rows = _from_device(rows.reshape(lead + (n,)), pts)
@@ -1550,26 +1554,12 @@ def _label_cval(cval, name):
     return value
 
 
-def _label_fill(like, shape, value, dtype=None):
-    """an array of `shape` filled with `value`, in the family and on the device of `like`; `like`'s dtype unless given"""
-    shape = tuple(int(v) for v in shape)
-    if isinstance(like, numpy.ndarray):
-        return numpy.full(shape, value, dtype=like.dtype if dtype is None else dtype)
-    torch = _torch()
-    return torch.full(shape, value, dtype=like.dtype if dtype is None else getattr(torch, dtype), device=like.device)
-
-
 def _labels_run(L, displacement, mode, cval, crop, axis, affine, rotate, zoom, return_weight, batch):
     """Both forms of deform_grid_labels.  Every argument check runs before the device is touched; offsets, the inverse
     map and the rotate / zoom centre are deform_grid's own for order 1 (the same Plan)."""
-    if batch:
-        plan = _batch_plan(L, displacement, 1, mode, cval, crop, axis, affine, rotate, zoom)
-        Ls = [L]
-        shapes = [tuple(int(v) for v in L.shape[1:])]
-    else:
-        Ls = _host.normalize_inputs(L)
-        plan = _host.cached_plan(Ls, displacement, 1, mode, cval, crop, axis, affine, rotate, zoom)
-        shapes = [tuple(int(v) for v in x.shape) for x in Ls]
+    Ls = [L] if batch else _host.normalize_inputs(L)
+    plan = _plan_of(Ls, batch, displacement, 1, mode, cval, crop, axis, affine, rotate, zoom)
+    shapes = [tuple(int(v) for v in x.shape[1 if batch else 0:]) for x in Ls]
     n = len(Ls)
     names = [_volume_dtype_name(x) for x in Ls]
     if any(name not in _LABEL_RANGE for name in names):
@@ -1582,37 +1572,26 @@ def _labels_run(L, displacement, mode, cval, crop, axis, affine, rotate, zoom, r
 
     if _host.degenerate_axis(shapes, plan.axis):
         # a deformed axis of length 1: every voxel maps to the constant, as in deform_grid (_host.degenerate_axis)
-        labels = [_label_fill(x, s, c) for x, s, c in zip(Ls, out_shapes, cvals)]
-        weights = [_label_fill(x, s, 1.0, 'float32') for x, s in zip(Ls, out_shapes)]
+        labels = [_fill(x, s, c) for x, s, c in zip(Ls, out_shapes, cvals)]
+        weights = [_fill(x, s, 1.0, 'float32') for x, s in zip(Ls, out_shapes)]
     else:
         torch = _torch()
         device = _device_for(list(Ls) + [displacement])
         labels, weights = [], []
         with torch.cuda.device(device):
             stream = _stream(device)
-            dd = _to_device(displacement, device)
-            # the control grid is prefiltered like deform_grid's (order 3, mirror, rounded to its own dtype per axis)
-            df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device, stream=stream)
+            df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
             for i, x in enumerate(Ls):
                 xd = _to_device(x, device)
                 out = torch.empty(out_shapes[i], dtype=xd.dtype, device=device)
                 wt = torch.empty(out_shapes[i], dtype=torch.float32, device=device) if return_weight else None
-                if batch:
-                    (x0, xs), (d0, ds), (o0, os_) = _desc_sample0(xd), _desc_sample0(df), _desc_sample0(out)
-                    w0, ws = _desc_sample0(wt) if wt is not None else (None, 0)
-                else:
-                    x0, d0, o0 = _desc(xd), _desc(df), _desc(out)
-                    w0 = _desc(wt) if wt is not None else None
-                    xs = ds = os_ = ws = 0
                 # one library call (one launch) per input
-                _lib.deform_labels(lead[0] if batch else 1, x0, xs, d0, ds, plan.output_offset, o0, os_, w0, ws,
-                                   plan.axis[i], int(plan.mode[i]), float(cvals[i]), plan.inverse_affine, 0, stream)
+                _lib.deform_labels(lead[0] if batch else 1, *_sample(xd, batch), *_sample(df, batch),
+                                   plan.output_offset, *_sample(out, batch), *_sample(wt, batch), plan.axis[i],
+                                   int(plan.mode[i]), float(cvals[i]), plan.inverse_affine, 0, stream)
                 labels.append(_from_device(out, x))
                 weights.append(_from_device(wt, x) if wt is not None else None)
-    if return_weight:
-        res = list(zip(labels, weights))
-        return res if isinstance(L, list) else res[0]
-    return labels if isinstance(L, list) else labels[0]
+    return _list_or_one(labels, weights, return_weight, L)
 
 
 def deform_grid_labels(L, displacement, mode='constant', cval=0, crop=None, axis=None, affine=None, rotate=None,
@@ -1674,24 +1653,14 @@ def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, a
                  return_valid, batch):
     """Both forms of deform_grid_inverse.  Every argument check runs before the device is touched; offsets, the inverse
     map K and the rotate / zoom centre are those of the forward call on an array of shape X_shape (the same Plan)."""
-    if int(max_iter) != max_iter or int(max_iter) < 1:
-        raise ValueError("max_iter should be a positive integer.")
-    if not float(tol) > 0.0:
-        raise ValueError("tol should be positive.")
-    if batch:
-        if not _host.is_array(Y) or Y.ndim < 2:
-            raise Exception('Y should be an array with a leading batch axis.')
-        Ys = [Y]
-        X_shapes = _inverse_shapes(X_shape, Ys, True)
-        plan = _batch_plan(_host.ShapeOnly((int(Y.shape[0]),) + X_shapes[0]), displacement, order, mode, cval, crop,
-                           axis, affine, rotate, zoom)
-        y_shapes = [tuple(int(v) for v in Y.shape[1:])]
-    else:
-        Ys = _host.normalize_inputs(Y)
-        X_shapes = _inverse_shapes(X_shape, Ys, False)
-        plan = _host.cached_plan([_host.ShapeOnly(s) for s in X_shapes], displacement, order, mode, cval, crop, axis,
-                                 affine, rotate, zoom)
-        y_shapes = [tuple(int(v) for v in y.shape) for y in Ys]
+    _check_iteration(max_iter, tol)
+    if batch and (not _host.is_array(Y) or Y.ndim < 2):
+        raise Exception('Y should be an array with a leading batch axis.')
+    Ys = [Y] if batch else _host.normalize_inputs(Y)
+    X_shapes = _inverse_shapes(X_shape, Ys, batch)
+    stand_ins = _shape_only(X_shapes[0], Y.shape[0]) if batch else [_host.ShapeOnly(s) for s in X_shapes]
+    plan = _plan_of(stand_ins, batch, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
+    y_shapes = [tuple(int(v) for v in y.shape[1 if batch else 0:]) for y in Ys]
     if [tuple(int(v) for v in s) for s in plan.output_shapes] != y_shapes:
         raise ValueError("Y does not match X_shape and cropping. Expected shape of Y is %s, but %s given."
                          % (str([tuple(s) for s in plan.output_shapes]), str(y_shapes)))
@@ -1713,18 +1682,16 @@ def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, a
         # a deformed axis of X of length 1: the forward call maps every voxel to the constant and no position is
         # defined (deform_points solves nothing there) -- cval everywhere, nothing valid
         Zs = [_constant_result(y, lead + s, c) for y, s, c in zip(Ys, X_shapes, plan.cval)]
-        valids = [_label_fill(y, lead + deformed, 0, 'uint8') for y in Ys]
+        valids = [_fill(y, lead + deformed, 0, 'uint8') for y in Ys]
     else:
         K = plan.inverse_affine
-        M = numpy.linalg.inv(numpy.asarray(K, dtype=numpy.float64)[:, :n]) if K is not None else None
+        M = _forward_linear(K, n)
         torch = _torch()
         device = _device_for(list(Ys) + [displacement])
         Zs, valids = [], []
         with torch.cuda.device(device):
             stream = _stream(device)
-            dd = _to_device(displacement, device)
-            # the control grid is prefiltered like deform_grid's (order 3, mirror, rounded to its own dtype per axis)
-            df = _filter_axes(dd, range(2 if batch else 1, dd.ndim), 3, False, device, stream=stream)
+            df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
             for i, y in enumerate(Ys):
                 yd = _to_device(y, device)
                 o = int(plan.order[i])
@@ -1735,23 +1702,13 @@ def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, a
                     yf = _filter_axes(yd, [a + 1 for a in ax] if batch else ax, o, False, device, stream=stream)
                 out = torch.empty(lead + X_shapes[i], dtype=yd.dtype, device=device)
                 ok = torch.empty(lead + deformed, dtype=torch.uint8, device=device) if return_valid else None
-                if batch:
-                    (y0, ys), (d0, ds), (o0, os_) = _desc_sample0(yf), _desc_sample0(df), _desc_sample0(out)
-                    v0, vs = _desc_sample0(ok) if ok is not None else (None, 0)
-                else:
-                    y0, d0, o0 = _desc(yf), _desc(df), _desc(out)
-                    v0 = _desc(ok) if ok is not None else None
-                    ys = ds = os_ = vs = 0
                 # one library call (one launch) per input: the solve is done again for each
-                _lib.deform_inverse(lead[0] if batch else 1, y0, ys, d0, ds, deformed, plan.output_offset, o0, os_, v0,
-                                    vs, ax, o, int(plan.mode[i]), float(plan.cval[i]), K, M, int(max_iter), float(tol),
-                                    0, stream)
+                _lib.deform_inverse(lead[0] if batch else 1, *_sample(yf, batch), *_sample(df, batch), deformed,
+                                    plan.output_offset, *_sample(out, batch), *_sample(ok, batch), ax, o,
+                                    int(plan.mode[i]), float(plan.cval[i]), K, M, int(max_iter), float(tol), 0, stream)
                 Zs.append(_from_device(out, y))
                 valids.append(_from_device(ok, y) if ok is not None else None)
-    if return_valid:
-        res = list(zip(Zs, valids))
-        return res if isinstance(Y, list) else res[0]
-    return Zs if isinstance(Y, list) else Zs[0]
+    return _list_or_one(Zs, valids, return_valid, Y)
 
 
 def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,

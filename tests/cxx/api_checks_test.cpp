@@ -1,9 +1,12 @@
 // Host-only check of the argument checks the C entry points share (edhip_api.hip: check_naxis, check_displacement,
-// check_pairs, deformed_lengths, sample, fill_geometry) on hostile descriptors -- no HIP call is made.  The helpers
+// check_pairs, deformed_lengths, sample, fill_geometry, and what the strided-batch calls on the prefiltered grid share:
+// check_batch_call, check_axes_1_to_3, check_prefiltered, check_batch_limit, has_shape, f32_or_f64, check_status,
+// check_iteration, batch_array) on hostile descriptors -- no HIP call is made.  The helpers
 // live in that file's anonymous namespace, so the file is included; link against libedhip.so for the launchers it
 // names.  Every array is a heap block of exactly the size the ABI promises, so that a build with
 // -Xarch_host -fsanitize=address,undefined reports any read beyond it.  Built and run by
 // tests/test_api_checks_host.py.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -155,6 +158,95 @@ int main()
         std::vector<double> aff7(7 * 8, 0.5);
         CHECK(fill_geometry(d7.get(), l7.data(), l7.data(), l7.data(), 7, aff7.data(), *g, msg, n) == EDHIP_OK);
         CHECK(g->nvox == 16384 && g->ncp[6] == 2 && g->affine[55] == 0.5 && g->disp_stride[7] == 8);
+    }
+    // ---- the preamble, the axis count of the image-side calls, the flag and the batch limit ----------------------
+    strcpy(msg, "stale");
+    CHECK(check_batch_call(0, true, msg, n) == EDHIP_OK && said(""));
+    CHECK(check_batch_call(-1, true, msg, n) == EDHIP_ERR_INVALID && said("invalid batch"));
+    CHECK(check_batch_call(3, false, msg, n) == EDHIP_ERR_INVALID && said("invalid batch"));
+    CHECK(check_batch_call(-1, false, nullptr, 0) == EDHIP_ERR_INVALID);
+    CHECK(check_batch_call(1, true, msg, 0) == EDHIP_OK && said("invalid batch"));                 // errlen 0: msg is not touched
+    {
+        std::unique_ptr<int32_t[]> none(new int32_t[0]);           // the list itself is never read
+        CHECK(check_axes_1_to_3("f", nullptr, 2, msg, n) == EDHIP_ERR_INVALID && said("invalid axis list"));
+        CHECK(check_axes_1_to_3("f", none.get(), 0, msg, n) == EDHIP_ERR_INVALID && said("invalid axis list"));
+        CHECK(check_axes_1_to_3("f", none.get(), -7, nullptr, 0) == EDHIP_ERR_INVALID);
+        CHECK(check_axes_1_to_3("edhip_f", none.get(), 4, msg, n) == EDHIP_ERR_UNSUPPORTED && said("edhip_f takes 1 to 3 deformed axes"));
+        CHECK(check_axes_1_to_3("f", none.get(), 1, msg, n) == EDHIP_OK && check_axes_1_to_3("f", none.get(), 3, msg, n) == EDHIP_OK);
+    }
+    CHECK(check_prefiltered("edhip_f", EDHIP_FLAG_RAW_DISPLACEMENT | EDHIP_FLAG_FAST, msg, n) == EDHIP_ERR_INVALID &&
+          said("edhip_f takes the prefiltered control grid"));
+    CHECK(check_prefiltered("edhip_f", EDHIP_FLAG_FAST, msg, n) == EDHIP_OK && check_prefiltered("f", 0, nullptr, 0) == EDHIP_OK);
+    CHECK(check_batch_limit("edhip_f", 65536, msg, n) == EDHIP_ERR_UNSUPPORTED && said("edhip_f: too many samples"));
+    CHECK(check_batch_limit("f", 65535, msg, n) == EDHIP_OK && check_batch_limit("f", 0, msg, n) == EDHIP_OK);
+
+    // ---- has_shape, f32_or_f64 ---------------------------------------------------------------------------------
+    {
+        std::vector<int64_t> want{5, 2, 2};
+        std::unique_ptr<int64_t[]> none(new int64_t[0]);           // rank 0: no extent is read
+        CHECK(has_shape(desc(3, {5, 2, 2}).get(), 3, want.data()) && has_shape(desc(2, {5, 2}).get(), 2, want.data()));
+        CHECK(!has_shape(desc(3, {5, 2, 3}).get(), 3, want.data()) && !has_shape(desc(2, {5, 2}).get(), 3, want.data()));
+        CHECK(!has_shape(desc(0, {}).get(), 3, want.data()) && !has_shape(desc(9, {5, 2, 2}).get(), 3, want.data()));
+        CHECK(!has_shape(desc(-1, {5, 2, 2}).get(), 3, want.data()));
+        CHECK(has_shape(desc(0, {}).get(), 0, none.get()) && !has_shape(desc(9, {5, 2, 2}).get(), 0, none.get()));
+        CHECK(!has_shape(desc(3, {5, -2, 2}).get(), 3, want.data()));
+        want[0] = -5;                                          // a negative extent equals itself: the callers refuse it before
+        CHECK(has_shape(desc(3, {-5, 2, 2}).get(), 3, want.data()));
+        CHECK(f32_or_f64(desc(1, {4}, EDHIP_F32).get()) && f32_or_f64(desc(0, {}, EDHIP_F64).get()));
+        CHECK(!f32_or_f64(desc(1, {4}, EDHIP_F16).get()) && !f32_or_f64(desc(1, {4}, EDHIP_I32).get()));
+        CHECK(!f32_or_f64(desc(1, {4}, -1).get()) && !f32_or_f64(desc(9, {4}, 13).get()));
+    }
+
+    // ---- check_status ------------------------------------------------------------------------------------------
+    CHECK(check_status(nullptr, false, 5, msg, n) == EDHIP_OK && check_status(nullptr, true, -1, nullptr, 0) == EDHIP_OK);
+    CHECK(check_status(desc(1, {5}, EDHIP_U8).get(), true, 5, msg, n) == EDHIP_OK);
+    CHECK(check_status(desc(1, {0}, EDHIP_U8).get(), true, 0, msg, n) == EDHIP_OK);
+    CHECK(check_status(desc(9, {4}, EDHIP_BOOL).get(), false, 5, msg, n) == EDHIP_ERR_INVALID &&
+          said("the status belongs to the inverse direction"));                                    // the direction before the array
+    CHECK(check_status(desc(1, {4}, EDHIP_BOOL).get(), true, 5, msg, n) == EDHIP_ERR_INVALID && said("status must have shape (N)"));
+    CHECK(check_status(desc(0, {}, EDHIP_U8).get(), true, 5, msg, n) == EDHIP_ERR_INVALID);
+    CHECK(check_status(desc(9, {5}, EDHIP_U8).get(), true, 5, msg, n) == EDHIP_ERR_INVALID);
+    CHECK(check_status(desc(2, {5, 1}, EDHIP_U8).get(), true, 5, msg, n) == EDHIP_ERR_INVALID);
+    CHECK(check_status(desc(1, {-5}, EDHIP_U8).get(), true, 5, msg, n) == EDHIP_ERR_INVALID);
+    CHECK(check_status(desc(1, {5}, EDHIP_BOOL).get(), true, 5, msg, n) == EDHIP_ERR_DTYPE && said("status must be uint8"));
+    CHECK(check_status(desc(1, {5}, -1).get(), true, 5, nullptr, 0) == EDHIP_ERR_DTYPE);
+
+    // ---- check_iteration ---------------------------------------------------------------------------------------
+    {
+        std::vector<double> aff{1, 0, 0, 0, 1, 0}, lin{1, 0, 0, 1};
+        CHECK(check_iteration(1, 1e-300, nullptr, nullptr, msg, n) == EDHIP_OK);
+        CHECK(check_iteration(32, 1e-9, aff.data(), lin.data(), msg, n) == EDHIP_OK);
+        CHECK(check_iteration(32, 1e-9, nullptr, lin.data(), nullptr, 0) == EDHIP_OK);
+        CHECK(check_iteration(0, 0.0, aff.data(), nullptr, msg, n) == EDHIP_ERR_INVALID && said("max_iter must be at least 1"));
+        CHECK(check_iteration(-3, 1e-9, nullptr, nullptr, msg, n) == EDHIP_ERR_INVALID);
+        CHECK(check_iteration(1, 0.0, aff.data(), nullptr, msg, n) == EDHIP_ERR_INVALID && said("tol must be positive"));
+        CHECK(check_iteration(1, -1.0, nullptr, nullptr, msg, n) == EDHIP_ERR_INVALID);
+        CHECK(check_iteration(1, std::nan(""), nullptr, nullptr, msg, n) == EDHIP_ERR_INVALID && said("tol must be positive"));
+        CHECK(check_iteration(1, 1e-9, aff.data(), nullptr, msg, n) == EDHIP_ERR_INVALID &&
+              said("forward_linear is required with an affine map"));
+    }
+
+    // ---- batch_array -------------------------------------------------------------------------------------------
+    {
+        std::unique_ptr<BatchArray> zero(new BatchArray);
+        memset(zero.get(), 0, sizeof(BatchArray));
+        const BatchArray none = batch_array(nullptr, 4096);        // a null optional array: all zero, the stride too
+        CHECK(memcmp(&none, zero.get(), sizeof(BatchArray)) == 0);
+        auto a = desc(3, {4, 8, 9}, EDHIP_I16);
+        const BatchArray s = batch_array(a.get(), -720);
+        CHECK(s.ptr == (char*)a->data && s.dtype == EDHIP_I16 && s.bstride == -720);
+        CHECK(s.stride[0] == a->stride_bytes[0] && s.stride[1] == 72 && s.stride[2] == 8 && s.stride[3] == 0 && s.stride[7] == 0);
+        a->stride_bytes[5] = 77;                               // beyond the rank: not the array's, not copied
+        CHECK(batch_array(a.get(), 0).stride[5] == 0);
+        const BatchArray r0 = batch_array(desc(0, {}).get(), 8);
+        CHECK(r0.ptr == (char*)0x1000 && r0.stride[0] == 0 && r0.bstride == 8);
+        const BatchArray neg = batch_array(desc(-4, {3}).get(), 8);
+        CHECK(neg.stride[0] == 0 && neg.bstride == 8);
+        auto nine = desc(9, {2, 2, 2, 2, 2, 2, 2, 2});             // rank 9: the eight strides the descriptor has, not a ninth
+        const BatchArray r9 = batch_array(nine.get(), 0);
+        CHECK(r9.stride[0] == nine->stride_bytes[0] && r9.stride[7] == 8);
+        const BatchArray negext = batch_array(desc(2, {-5, 3}).get(), 1);   // extents are not this helper's business
+        CHECK(negext.stride[1] == 8 && negext.stride[0] == 24);
     }
     std::printf("ok\n");
     return 0;

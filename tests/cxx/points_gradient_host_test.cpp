@@ -108,28 +108,28 @@ static Result run(int n, int ncp, int64_t npts, int inverse, int nbatch, const s
     call.nbatch = nbatch;
     call.npts = npts;
     call.disp_bstride = values * 4;
-    call.pos = (const char*)pos.p;
-    call.cot = (const char*)cot.p;
-    call.dpts = (char*)rows.p;
-    call.pos_dtype = call.cot_dtype = call.dpts_dtype = EDHIP_F64;
-    call.pos_stride[0] = call.cot_stride[0] = call.dpts_stride[0] = n * 8;
-    call.pos_stride[1] = call.cot_stride[1] = call.dpts_stride[1] = 8;
-    call.pos_bstride = call.cot_bstride = call.dpts_bstride = npts * n * 8;
-    call.status = inverse ? status.p : nullptr;
-    call.status_stride = 1;
-    call.status_bstride = npts;
-    call.ddisp = (char*)dP.p;
-    call.ddisp_dtype = EDHIP_F64;
-    call.ddisp_bstride = values * 8;
+    call.pos.ptr = (char*)pos.p;
+    call.cot.ptr = (char*)cot.p;
+    call.dpts.ptr = (char*)rows.p;
+    call.pos.dtype = call.cot.dtype = call.dpts.dtype = EDHIP_F64;
+    call.pos.stride[0] = call.cot.stride[0] = call.dpts.stride[0] = n * 8;
+    call.pos.stride[1] = call.cot.stride[1] = call.dpts.stride[1] = 8;
+    call.pos.bstride = call.cot.bstride = call.dpts.bstride = npts * n * 8;
+    call.status.ptr = inverse ? (char*)status.p : nullptr;
+    call.status.stride[0] = 1;
+    call.status.bstride = npts;
+    call.ddisp.ptr = (char*)dP.p;
+    call.ddisp.dtype = EDHIP_F64;
+    call.ddisp.bstride = values * 8;
     stride = 8;
     for (int k = n; k >= 0; --k) {
-        call.ddisp_stride[k] = stride;
+        call.ddisp.stride[k] = stride;
         stride *= k > 0 ? ncp : 1;
     }
-    call.dK = (char*)dK.p;
-    call.dK_stride[0] = (n + 1) * 8;
-    call.dK_stride[1] = 8;
-    call.dK_bstride = n * (n + 1) * 8;
+    call.dK.ptr = (char*)dK.p;
+    call.dK.stride[0] = (n + 1) * 8;
+    call.dK.stride[1] = 8;
+    call.dK.bstride = n * (n + 1) * 8;
     Block<char> scratch(points_grad_scratch_bytes(g, nbatch, npts));
     memset(scratch.p, 0xff, scratch.n);                      // nothing may rely on what an earlier call left
     call.scratch = scratch.p;

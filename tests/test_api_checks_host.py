@@ -1,7 +1,8 @@
 """
 CPU test of the argument checks the C entry points share (csrc/edhip_api.hip: check_naxis, check_displacement,
-check_pairs, deformed_lengths, sample, fill_geometry), driven by a host-only C++ program on hostile descriptors -- rank 0
-and 9, negative extents, 0 and 8 deformed axes, null pointers where the ABI allows them.  No GPU, no HIP call.  The
+check_pairs, deformed_lengths, sample, fill_geometry, and the helpers of the strided-batch calls on the prefiltered grid:
+check_batch_call ... batch_array), driven by a host-only C++ program on hostile descriptors -- rank 0 and 9, negative
+extents, 0 and 8 deformed axes, null pointers where the ABI allows them.  No GPU, no HIP call.  The
 program is tests/cxx/api_checks_test.cpp; its arrays are heap blocks of exactly the promised size, so the same build
 with ``-Xarch_host -fsanitize=address,undefined`` added turns any read beyond them into a report.
 """

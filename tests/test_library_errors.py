@@ -196,6 +196,25 @@ def labels(nb=1, inp=L8, disp=D2, out=_DEF, wt=None, naxis=2, axis=(0, 1), mode=
                i32(axis), mode, cval, None, flags, None)
 
 
+def pgrad(inverse=0, nb=1, pos=PTS, cot=_DEF, status=None, disp=D2, in_len=(8, 9), naxis=2, dpts=_DEF, ddisp=_DEF,
+          dinv=_DEF, flags=0):
+    cot = pos if cot is _DEF else cot
+    dpts = pos if dpts is _DEF else dpts
+    ddisp = disp if ddisp is _DEF else ddisp
+    dinv = DINV if dinv is _DEF else dinv
+    return run(_lib.load().edhip_deform_points_gradient, inverse, nb, ref(pos), 0, ref(cot), 0, ref(status), 0,
+               ref(disp), 0, i64(in_len), None, naxis, None, ref(dpts), 0, ref(ddisp), 0, ref(dinv), 0, flags, None)
+
+
+Y2, Z2 = A((6, 7)), A((8, 9))
+
+
+def inverse(nb=1, inp=Y2, disp=D2, in_len=(8, 9), out=Z2, valid=None, naxis=2, axis=(0, 1), order=3, mode=0, aff=None,
+            lin=None, max_iter=20, tol=1e-9, flags=0):
+    return run(_lib.load().edhip_deform_inverse, nb, ref(inp), 0, ref(disp), 0, i64(in_len), None, ref(out), 0,
+               ref(valid), 0, naxis, i32(axis), order, mode, 0.0, f64(aff), f64(lin), max_iter, tol, flags, None)
+
+
 AX8 = list(range(8))
 X8 = A((2,) * 8)
 D5 = A((5, 2, 2, 2, 2, 2), "float64")
@@ -568,6 +587,200 @@ CASES = [
     ("labels-no-voxels-length-1", lambda: labels(inp=A((1, 9), "uint8"), out=A((0, 9), "uint8")), (OK, "")),
     ("labels-no-steps", lambda: labels(inp=A((0, 8, 9), "uint8"), axis=(1, 2)), (OK, "")),
     ("labels-cval-extremes", lambda: labels(nb=0, inp=A((8, 9), "int64"), cval=-2.0 ** 63), (OK, "")),
+    # ---- edhip_deform_points_gradient --------------------------------------------------------------------------------
+    ("pgrad-negative-batch", lambda: pgrad(nb=-1), (INVALID, M_BATCH)),
+    ("pgrad-null-positions", lambda: pgrad(pos=None, cot=PTS, dpts=PTS), (INVALID, M_BATCH)),
+    ("pgrad-null-cotangent", lambda: pgrad(cot=None), (INVALID, M_BATCH)),
+    ("pgrad-null-displacement", lambda: pgrad(disp=None, ddisp=D2), (INVALID, M_BATCH)),
+    ("pgrad-null-lengths", lambda: pgrad(in_len=None), (INVALID, M_BATCH)),
+    ("pgrad-null-cotangent+naxis-0", lambda: pgrad(cot=None, naxis=0), (INVALID, M_BATCH)),
+    ("pgrad-naxis-0", lambda: pgrad(naxis=0), (INVALID, M_AXES)),
+    ("pgrad-naxis-8", lambda: pgrad(naxis=8, in_len=(4,) * 8), (UNSUPPORTED, M_NAXIS)),
+    ("pgrad-naxis-8+raw+none", lambda: pgrad(naxis=8, in_len=(4,) * 8, flags=RAW, dpts=None, ddisp=None, dinv=None),
+     (UNSUPPORTED, M_NAXIS)),
+    ("pgrad-raw", lambda: pgrad(flags=RAW),
+     (INVALID, "edhip_deform_points_gradient takes the prefiltered control grid")),
+    ("pgrad-raw+none", lambda: pgrad(flags=RAW, dpts=None, ddisp=None, dinv=None),
+     (INVALID, "edhip_deform_points_gradient takes the prefiltered control grid")),
+    ("pgrad-none", lambda: pgrad(dpts=None, ddisp=None, dinv=None),
+     (INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested")),
+    ("pgrad-none+shape", lambda: pgrad(pos=A((5, 3), "float64"), dpts=None, ddisp=None, dinv=None),
+     (INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested")),
+    ("pgrad-none-empty-batch", lambda: pgrad(nb=0, dpts=None, ddisp=None, dinv=None),
+     (INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested")),
+    ("pgrad-shape", lambda: pgrad(pos=A((5, 3), "float64")), (INVALID, "positions must have shape (N, naxis)")),
+    ("pgrad-rank", lambda: pgrad(pos=A((10,), "float64")), (INVALID, "positions must have shape (N, naxis)")),
+    ("pgrad-rank-0", lambda: pgrad(pos=H(0)), (INVALID, "positions must have shape (N, naxis)")),
+    ("pgrad-rank-9", lambda: pgrad(pos=H(9, (5, 2) + (1,) * 6, 10)), (INVALID, "positions must have shape (N, naxis)")),
+    ("pgrad-negative-count", lambda: pgrad(pos=H(2, (-1, 2), 10)), (INVALID, "positions must have shape (N, naxis)")),
+    ("pgrad-cotangent-shape", lambda: pgrad(cot=A((4, 2), "float64")),
+     (INVALID, "cotangent must have the shape of positions")),
+    ("pgrad-cotangent-rank", lambda: pgrad(cot=A((5, 2, 1), "float64")),
+     (INVALID, "cotangent must have the shape of positions")),
+    ("pgrad-cotangent-shape+dtype", lambda: pgrad(cot=A((4, 2), "int32")),
+     (INVALID, "cotangent must have the shape of positions")),
+    ("pgrad-dtype", lambda: pgrad(pos=A((5, 2), "int32"), cot=PTS, dpts=PTS), (DTYPE, M_DTYPE)),
+    ("pgrad-cotangent-dtype", lambda: pgrad(cot=A((5, 2), "float16")), (DTYPE, M_DTYPE)),
+    ("pgrad-dtype-13", lambda: pgrad(cot=H(2, (5, 2), 13)), (DTYPE, M_DTYPE)),
+    ("pgrad-dtype+status-forward", lambda: pgrad(cot=A((5, 2), "float16"), status=A((5,), "uint8")),
+     (DTYPE, M_DTYPE)),
+    ("pgrad-status-forward", lambda: pgrad(status=A((5,), "uint8")),
+     (INVALID, "the status belongs to the inverse direction")),
+    ("pgrad-status-forward+shape", lambda: pgrad(status=A((4,), "bool")),
+     (INVALID, "the status belongs to the inverse direction")),
+    ("pgrad-status-shape", lambda: pgrad(inverse=1, status=A((4,), "uint8")), (INVALID, "status must have shape (N)")),
+    ("pgrad-status-rank", lambda: pgrad(inverse=1, status=A((5, 1), "uint8")), (INVALID, "status must have shape (N)")),
+    ("pgrad-status-dtype", lambda: pgrad(inverse=1, status=A((5,), "bool")), (DTYPE, "status must be uint8")),
+    ("pgrad-status-shape+dtype", lambda: pgrad(inverse=1, status=A((4,), "bool")),
+     (INVALID, "status must have shape (N)")),
+    ("pgrad-status-dtype+displacement", lambda: pgrad(inverse=1, status=A((5,), "bool"), disp=A((2, 3), "float64"),
+                                                      ddisp=None), (DTYPE, "status must be uint8")),
+    ("pgrad-displacement-rank", lambda: pgrad(disp=A((2, 3), "float64"), ddisp=None), (INVALID, M_DISP)),
+    ("pgrad-displacement-components", lambda: pgrad(disp=A((3, 3, 3), "float64")), (INVALID, M_DISP)),
+    ("pgrad-displacement-dtype", lambda: pgrad(disp=H(3, (2, 3, 3), 13), ddisp=D2), (DTYPE, M_DTYPE)),
+    ("pgrad-displacement-empty", lambda: pgrad(disp=A((2, 0, 3), "float64")), (INVALID, M_DISP)),
+    ("pgrad-displacement-negative", lambda: pgrad(disp=H(3, (2, 3, -3), 10), ddisp=None), (INVALID, M_DISP)),
+    ("pgrad-displacement+dpoints", lambda: pgrad(disp=A((2, 0, 3), "float64"), dpts=A((5, 3), "float64")),
+     (INVALID, M_DISP)),
+    ("pgrad-dpoints-shape", lambda: pgrad(dpts=A((5, 3), "float64")),
+     (INVALID, "dpoints must have the shape of positions")),
+    ("pgrad-dpoints-rank", lambda: pgrad(dpts=A((10,), "float64")),
+     (INVALID, "dpoints must have the shape of positions")),
+    ("pgrad-dpoints-dtype", lambda: pgrad(dpts=A((5, 2), "int64")), (DTYPE, M_DTYPE)),
+    ("pgrad-dpoints-shape+dtype", lambda: pgrad(dpts=A((4, 2), "int64")),
+     (INVALID, "dpoints must have the shape of positions")),
+    ("pgrad-dpoints-dtype+ddisp-shape", lambda: pgrad(dpts=A((5, 2), "int64"), ddisp=A((2, 3, 4), "float64")),
+     (DTYPE, M_DTYPE)),
+    ("pgrad-ddisp-rank", lambda: pgrad(ddisp=A((2, 3), "float64")), (INVALID, M_DDISP)),
+    ("pgrad-ddisp-rank-9", lambda: pgrad(ddisp=H(9, (2, 3, 3) + (1,) * 5, 10)), (INVALID, M_DDISP)),
+    ("pgrad-ddisp-shape", lambda: pgrad(ddisp=A((2, 3, 4), "float64")), (INVALID, M_DDISP)),
+    ("pgrad-ddisp-integer", lambda: pgrad(ddisp=A((2, 3, 3), "int32")),
+     (DTYPE, "ddisplacement must have a floating-point dtype")),
+    ("pgrad-ddisp-dtype-13", lambda: pgrad(ddisp=H(3, (2, 3, 3), 13)),
+     (DTYPE, "ddisplacement must have a floating-point dtype")),
+    ("pgrad-ddisp-shape+dtype", lambda: pgrad(ddisp=A((2, 3, 4), "int32")), (INVALID, M_DDISP)),
+    ("pgrad-ddisp-dtype+dinv-shape", lambda: pgrad(ddisp=A((2, 3, 3), "int32"), dinv=A((3, 2), "float64")),
+     (DTYPE, "ddisplacement must have a floating-point dtype")),
+    ("pgrad-dinv-shape", lambda: pgrad(dinv=A((3, 2), "float64")), (INVALID, M_DINV)),
+    ("pgrad-dinv-rank", lambda: pgrad(dinv=A((6,), "float64")), (INVALID, M_DINV)),
+    ("pgrad-dinv-float32", lambda: pgrad(dinv=A((2, 3), "float32")), (DTYPE, M_DINV64)),
+    ("pgrad-dinv-shape+float32", lambda: pgrad(dinv=A((3, 2), "float32")), (INVALID, M_DINV)),
+    ("pgrad-dinv-float32+65536", lambda: pgrad(nb=65536, dinv=A((2, 3), "float32")), (DTYPE, M_DINV64)),
+    ("pgrad-65536", lambda: pgrad(nb=65536), (UNSUPPORTED, "edhip_deform_points_gradient: too many samples")),
+    ("pgrad-65536+length-1", lambda: pgrad(nb=65536, in_len=(8, 1)),
+     (UNSUPPORTED, "edhip_deform_points_gradient: too many samples")),
+    ("pgrad-length-1", lambda: pgrad(in_len=(8, 1)), (INVALID, M_LEN2)),
+    ("pgrad-length-1-empty-batch", lambda: pgrad(nb=0, in_len=(8, 1)), (INVALID, M_LEN2)),
+    ("pgrad-length-1-no-points", lambda: pgrad(pos=A((0, 2), "float64"), in_len=(1, 9), ddisp=None, dinv=None),
+     (INVALID, M_LEN2)),
+    ("pgrad-empty-batch", lambda: pgrad(nb=0), (OK, "")),
+    ("pgrad-empty-batch-inverse", lambda: pgrad(inverse=1, nb=0, status=A((5,), "uint8")), (OK, "")),
+    ("pgrad-empty-batch-no-points", lambda: pgrad(nb=0, pos=A((0, 2), "float32")), (OK, "")),
+    ("pgrad-no-points-rows-only", lambda: pgrad(pos=A((0, 2), "float64"), ddisp=None, dinv=None), (OK, "")),
+    ("pgrad-no-points-rows-only-inverse", lambda: pgrad(inverse=1, pos=A((0, 2), "float32"),
+                                                        status=A((0,), "uint8"), ddisp=None, dinv=None), (OK, "")),
+    # ---- edhip_deform_inverse ----------------------------------------------------------------------------------------
+    ("inverse-negative-batch", lambda: inverse(nb=-1), (INVALID, M_BATCH)),
+    ("inverse-null-input", lambda: inverse(inp=None), (INVALID, M_BATCH)),
+    ("inverse-null-displacement", lambda: inverse(disp=None), (INVALID, M_BATCH)),
+    ("inverse-null-output", lambda: inverse(out=None), (INVALID, M_BATCH)),
+    ("inverse-null-lengths", lambda: inverse(in_len=None), (INVALID, M_BATCH)),
+    ("inverse-null-lengths+null-axis", lambda: inverse(in_len=None, axis=None), (INVALID, M_BATCH)),
+    ("inverse-null-axis", lambda: inverse(axis=None), (INVALID, M_AXES)),
+    ("inverse-naxis-0", lambda: inverse(naxis=0), (INVALID, M_AXES)),
+    ("inverse-naxis-4", lambda: inverse(inp=A((3,) * 4), out=A((3,) * 4), disp=A((4, 2, 2, 2, 2), "float64"),
+                                        in_len=(3,) * 4, naxis=4, axis=(0, 1, 2, 3)),
+     (UNSUPPORTED, "edhip_deform_inverse takes 1 to 3 deformed axes")),
+    ("inverse-naxis-8+displacement+raw", lambda: inverse(naxis=8, axis=AX8, in_len=(4,) * 8, flags=RAW),
+     (UNSUPPORTED, "edhip_deform_inverse takes 1 to 3 deformed axes")),
+    ("inverse-raw", lambda: inverse(flags=RAW), (INVALID, "edhip_deform_inverse takes the prefiltered control grid")),
+    ("inverse-raw+rank", lambda: inverse(flags=RAW, out=A((8, 9, 1))),
+     (INVALID, "edhip_deform_inverse takes the prefiltered control grid")),
+    ("inverse-rank-mismatch", lambda: inverse(out=A((8, 9, 1))), (INVALID, M_NDIM)),
+    ("inverse-ndim-0", lambda: inverse(inp=H(0), out=H(0)), (UNSUPPORTED, M_RANK)),
+    ("inverse-ndim-9", lambda: inverse(inp=H(9, (2,) * 8), out=H(9, (2,) * 8)), (UNSUPPORTED, M_RANK)),
+    ("inverse-rank-mismatch+ndim-9", lambda: inverse(inp=H(9, (2,) * 8)), (INVALID, M_NDIM)),
+    ("inverse-dtype-13", lambda: inverse(inp=H(2, (6, 7), 13)), (DTYPE, M_DTYPE)),
+    ("inverse-dtype-negative", lambda: inverse(out=H(2, (8, 9), -1)), (DTYPE, M_DTYPE)),
+    ("inverse-dtype+axis", lambda: inverse(inp=H(2, (6, 7), 13), axis=(0, 2)), (DTYPE, M_DTYPE)),
+    ("inverse-axis-high", lambda: inverse(axis=(0, 2)), (INVALID, M_AXIS)),
+    ("inverse-axis-negative", lambda: inverse(axis=(-1, 1)), (INVALID, M_AXIS)),
+    ("inverse-axis+order", lambda: inverse(axis=(0, 2), order=6), (INVALID, M_AXIS)),
+    ("inverse-order-6", lambda: inverse(order=6), (INVALID, M_ORDER)),
+    ("inverse-order-negative", lambda: inverse(order=-1), (INVALID, M_ORDER)),
+    ("inverse-order+mode", lambda: inverse(order=6, mode=5), (INVALID, M_ORDER)),
+    ("inverse-mode", lambda: inverse(mode=5), (INVALID, M_MODE)),
+    ("inverse-mode+unsorted", lambda: inverse(mode=5, axis=(1, 0)), (INVALID, M_MODE)),
+    ("inverse-axis-unsorted", lambda: inverse(inp=A((7, 7)), out=A((9, 9)), in_len=(9, 9), axis=(1, 0)),
+     (INVALID, M_AXIS)),
+    ("inverse-axis-repeated", lambda: inverse(inp=A((7, 7)), out=A((9, 9)), in_len=(9, 9), axis=(1, 1)),
+     (INVALID, M_AXIS)),
+    ("inverse-unsorted+two-dtypes", lambda: inverse(out=A((8, 9), "float64"), axis=(1, 0)), (INVALID, M_AXIS)),
+    ("inverse-two-dtypes", lambda: inverse(out=A((8, 9), "float64")),
+     (DTYPE, "input and output must have one dtype")),
+    ("inverse-two-dtypes+half", lambda: inverse(inp=A((6, 7), "float16")),
+     (DTYPE, "input and output must have one dtype")),
+    ("inverse-half", lambda: inverse(inp=A((6, 7), "float16"), out=A((8, 9), "float16")), (DTYPE, M_DTYPE)),
+    ("inverse-bfloat16", lambda: inverse(inp=H(2, (6, 7), 12), out=H(2, (8, 9), 12)), (DTYPE, M_DTYPE)),
+    ("inverse-half+extents", lambda: inverse(inp=A((6, 7), "float16"), out=A((8, 10), "float16")), (DTYPE, M_DTYPE)),
+    ("inverse-extents", lambda: inverse(out=A((8, 10))),
+     (INVALID, "the output's deformed axes must have the extents in_len")),
+    ("inverse-extents-first-axis", lambda: inverse(out=A((7, 9))),
+     (INVALID, "the output's deformed axes must have the extents in_len")),
+    ("inverse-sampled-length-1", lambda: inverse(inp=A((6, 1))), (INVALID, M_LEN2)),
+    ("inverse-sampled-length-0", lambda: inverse(inp=A((0, 7))), (INVALID, M_LEN2)),
+    ("inverse-first-length-1+second-extents", lambda: inverse(inp=A((1, 7)), out=A((8, 10))), (INVALID, M_LEN2)),
+    ("inverse-first-extents+second-length-1", lambda: inverse(inp=A((6, 1)), out=A((7, 9))),
+     (INVALID, "the output's deformed axes must have the extents in_len")),
+    ("inverse-extents+valid", lambda: inverse(out=A((8, 10)), valid=A((8, 8), "uint8")),
+     (INVALID, "the output's deformed axes must have the extents in_len")),
+    ("inverse-valid-shape", lambda: inverse(valid=A((8, 8), "uint8")),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-rank", lambda: inverse(valid=A((72,), "uint8")),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-rank-0", lambda: inverse(valid=H(0, (), 1)),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-rank-9", lambda: inverse(valid=H(9, (8, 9) + (1,) * 6, 1)),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-step-axes", lambda: inverse(inp=A((4, 6, 7)), out=A((4, 8, 9)), axis=(1, 2),
+                                                valid=A((4, 8, 9), "uint8")),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-bool", lambda: inverse(valid=A((8, 9), "bool")), (DTYPE, "valid must be uint8")),
+    ("inverse-valid-shape+dtype", lambda: inverse(valid=A((8, 8), "bool")),
+     (INVALID, "valid must have the output's deformed shape")),
+    ("inverse-valid-dtype+max-iter", lambda: inverse(valid=A((8, 9), "bool"), max_iter=0),
+     (DTYPE, "valid must be uint8")),
+    ("inverse-max-iter", lambda: inverse(max_iter=0), (INVALID, "max_iter must be at least 1")),
+    ("inverse-tol", lambda: inverse(tol=0.0), (INVALID, "tol must be positive")),
+    ("inverse-tol-nan", lambda: inverse(tol=float("nan")), (INVALID, "tol must be positive")),
+    ("inverse-max-iter+tol", lambda: inverse(max_iter=0, tol=0.0), (INVALID, "max_iter must be at least 1")),
+    ("inverse-affine-without-linear", lambda: inverse(aff=[1, 0, 0, 0, 1, 0]),
+     (INVALID, "forward_linear is required with an affine map")),
+    ("inverse-tol+affine-without-linear", lambda: inverse(tol=-1.0, aff=[1, 0, 0, 0, 1, 0]),
+     (INVALID, "tol must be positive")),
+    ("inverse-tol+displacement", lambda: inverse(tol=0.0, disp=A((2, 3), "float64")),
+     (INVALID, "tol must be positive")),
+    ("inverse-displacement-rank", lambda: inverse(disp=A((2, 3), "float64")), (INVALID, M_DISP)),
+    ("inverse-displacement-components", lambda: inverse(disp=A((3, 3, 3), "float64")), (INVALID, M_DISP)),
+    ("inverse-displacement-dtype", lambda: inverse(disp=H(3, (2, 3, 3), 13)), (DTYPE, M_DTYPE)),
+    ("inverse-displacement-empty", lambda: inverse(disp=A((2, 3, 0), "float64")), (INVALID, M_DISP)),
+    ("inverse-displacement+65536", lambda: inverse(nb=65536, disp=A((2, 0, 3), "float64")), (INVALID, M_DISP)),
+    ("inverse-65536", lambda: inverse(nb=65536), (UNSUPPORTED, "edhip_deform_inverse: too many samples")),
+    ("inverse-65536+length-1", lambda: inverse(nb=65536, out=A((8, 1)), in_len=(8, 1)),
+     (UNSUPPORTED, "edhip_deform_inverse: too many samples")),
+    ("inverse-length-1", lambda: inverse(out=A((8, 1)), in_len=(8, 1)), (INVALID, M_LEN2)),
+    ("inverse-length-1-empty-batch", lambda: inverse(nb=0, out=A((8, 1)), in_len=(8, 1)), (INVALID, M_LEN2)),
+    ("inverse-length-1+step-axes", lambda: inverse(inp=A((4, 6, 7)), out=A((5, 8, 1)), in_len=(8, 1), axis=(1, 2)),
+     (INVALID, M_LEN2)),
+    ("inverse-step-axes", lambda: inverse(inp=A((4, 6, 7)), out=A((5, 8, 9)), axis=(1, 2)), (INVALID, M_STEP)),
+    ("inverse-step-axes-empty-batch", lambda: inverse(nb=0, inp=A((4, 6, 7)), out=A((5, 8, 9)), axis=(1, 2)),
+     (INVALID, M_STEP)),
+    ("inverse-empty-batch", lambda: inverse(nb=0), (OK, "")),
+    ("inverse-empty-batch-valid-affine", lambda: inverse(nb=0, valid=A((8, 9), "uint8"), aff=[1, 0, 0, 0, 1, 0],
+                                                         lin=[1, 0, 0, 1]), (OK, "")),
+    ("inverse-no-steps", lambda: inverse(inp=A((0, 6, 7)), out=A((0, 8, 9)), axis=(1, 2)), (OK, "")),
+    ("inverse-no-steps-valid", lambda: inverse(inp=A((6, 0, 7), "int16"), out=A((8, 0, 9), "int16"), axis=(0, 2),
+                                               valid=A((8, 9), "uint8")), (OK, "")),
 ]
 
 

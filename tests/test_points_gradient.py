@@ -448,6 +448,28 @@ def test_autograd_gives_the_bits_of_the_gradient_functions(inverse):
     _same_bits(Dt.grad.cpu().numpy(), want.displacement)
 
 
+_SUBSETS = [s for s in itertools.product([False, True], repeat=3) if any(s)]
+
+
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+@pytest.mark.parametrize("want", _SUBSETS, ids=["+".join(n for n, w in zip(("rows", "ddisp", "dK"), s) if w)
+                                                for s in _SUBSETS])
+def test_every_subset_of_the_results_has_the_bits_of_the_full_call(inverse, want):
+    """the one library call behind both gradients, asked for any subset of (rows, d displacement, dK) as the autograd
+    backward asks it: what is asked for has the bits of the call that asks for all three, the rest is None"""
+    I, D, q, u, kw = _contract_case()
+    if inverse:
+        q = restate(q, D, I, _offsets(kw["crop"], 2), _K(I, **kw))
+    args = (q, u, D, I, kw["crop"], None, kw["affine"], None, None, inverse, False)
+    full = etorch._api._points_gradient(*args)[1:]
+    got = etorch._api._points_gradient(*args, want_points=want[0], want_disp=want[1], want_map=want[2])[1:]
+    for g, f, wanted in zip(got, full, want):
+        if wanted:
+            _same_bits(g.cpu().numpy() if torch.is_tensor(g) else g, f.cpu().numpy() if torch.is_tensor(f) else f)
+        else:
+            assert g is None
+
+
 # ---- 8. a landmark fit's derivative ----------------------------------------------------------------------------
 
 def test_landmark_fit_derivative_and_descent():
