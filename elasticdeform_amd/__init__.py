@@ -24,6 +24,8 @@ gradient of a loss on mapped points with respect to the points, the displacement
 the argmax of the order-1 deformed one-hot channels without the one-hot volumes.
 ``deform_grid_inverse`` / ``deform_grid_inverse_batch`` resample an image back through the deformation, from the
 deformed frame into the source frame: the image-side counterpart of ``deform_points``.
+``deform_grid_inverse_gradient`` / ``deform_grid_inverse_gradient_batch`` are their adjoints with respect to the image;
+a tensor that requires grad carries autograd through ``deform_grid_inverse``.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
@@ -35,7 +37,8 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_labels, deform_grid_labels_batch, PointsGradient,
                           deform_grid_coordinates_gradient, deform_points_gradient,
                           deform_grid_coordinates_gradient_batch, deform_points_gradient_batch,
-                          deform_grid_inverse, deform_grid_inverse_batch)
+                          deform_grid_inverse, deform_grid_inverse_batch, deform_grid_inverse_gradient,
+                          deform_grid_inverse_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

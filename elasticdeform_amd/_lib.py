@@ -55,7 +55,7 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
-           'edhip_deform_points_gradient', 'edhip_deform_inverse')
+           'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -198,6 +198,13 @@ def load():
             ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
             ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
             ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_inverse_gradient.restype = ctypes.c_int
+        L.edhip_deform_inverse_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double,
+            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -449,6 +456,24 @@ def deform_inverse(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, in_len,
           (int(nbatch), *_pairs(in_desc, in_bstride, disp_desc, disp_bstride), lens, off,
            *_pairs(out_desc, out_bstride, valid_desc, valid_bstride), len(axis), ax, int(order), int(mode),
            float(cval), aff, lin, int(max_iter), float(tol)), flags, stream)
+
+
+def deform_inverse_gradient(nbatch, cot_desc, cot_bstride, disp_desc, disp_bstride, in_len, output_offset, din_desc,
+                            din_bstride, axis, order, mode, inverse_affine, forward_linear, max_iter, tol, flags,
+                            stream):
+    """edhip_deform_inverse_gradient: the adjoint of deform_inverse() with respect to its input -- `cot_desc` (dZ,
+    deformed extents `in_len`, float32 / float64) times the tap weights at the solved positions ADDED into `din_desc`
+    (the accumulator, the input's shape, the same dtype) with float atomics.  The caller zeroes `din_desc` and applies
+    the transposed prefilter afterwards.  Sample 0's descriptors plus byte strides; `disp_desc` is the PREFILTERED
+    control grid."""
+    lens, _lens = _ptr(in_len, numpy.int64)
+    ax, axis = _ptr(axis, numpy.int32)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    lin, _lin = _ptr(forward_linear, numpy.float64)
+    _call(load().edhip_deform_inverse_gradient,
+          (int(nbatch), *_pairs(cot_desc, cot_bstride, disp_desc, disp_bstride), lens, off,
+           *_pairs(din_desc, din_bstride), len(axis), ax, int(order), int(mode), aff, lin, int(max_iter),
+           float(tol)), flags, stream)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):

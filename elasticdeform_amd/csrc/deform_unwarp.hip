@@ -22,18 +22,16 @@
 // leaves Y: tap indices are clamped to [0, O_k - 1] (no effect on a coordinate the boundary map produced).  No
 // atomics, no workspace, no synchronisation beyond the staging barrier: a voxel's result depends on the call's
 // arguments alone, so a sample of a batch and a repeated call give the same bits.
+//
+// The front of the kernel (staging, voxel index, Newton phase: solve_voxel) and the formation of the taps and weights
+// (form_taps) live in ed_unwarp.h: deform_unwarp_grad.hip, the adjoint, runs the same code.
 #include <cstring>
 
-#include "ed_device.h"
-#include "ed_exact_coord.h"
-#include "ed_params.h"
-#include "ed_points.h"
+#include "ed_unwarp.h"
 
 namespace ed {
 
 namespace {
-
-constexpr int kUnwarpThreads = 256;
 
 // what the gather phase reads (never written in the kernel: its step arrays are indexed at run time)
 struct UnwarpView {
@@ -43,33 +41,6 @@ struct UnwarpView {
     int64_t valid_stride[3], valid_bstride;
     int64_t nsrc;                             // prod I_k: the work size
 };
-
-// spline_weights for a constant order; every order writes all six slots (zeros past the order), so that no store to
-// w is ever indexed by the order at run time
-template <int ORDER>
-__device__ __forceinline__ void weights_of_order(double c, double (&w)[6])
-{
-    double tmp[ORDER + 1];
-    spline_weights(c, ORDER, tmp);
-#pragma unroll
-    for (int l = 0; l < 6; ++l)
-        w[l] = l <= ORDER ? tmp[l <= ORDER ? l : 0] : 0.0;
-}
-__device__ __forceinline__ void weights_by_order(double c, int order, double (&w)[6])
-{
-    switch (order) {
-    case 1: weights_of_order<1>(c, w); break;
-    case 2: weights_of_order<2>(c, w); break;
-    case 3: weights_of_order<3>(c, w); break;
-    case 4: weights_of_order<4>(c, w); break;
-    case 5: weights_of_order<5>(c, w); break;
-    default:                                  // order 0: one tap, no weight
-#pragma unroll
-        for (int l = 0; l < 6; ++l)
-            w[l] = 0.0;
-        break;
-    }
-}
 
 // The (order + 1)^N taps from deformed axis D on, added to t in the reference's order.  wo[k], k < D: the weight of
 // the current tap on the outer axes.  S: the element type (its conversion to double is the plain C one).
@@ -137,37 +108,8 @@ __device__ __forceinline__ void resample(const GridGeom& g, const UnwarpView& u,
     const int order = v.order;
     double w[N][6];
     int64_t tap[N][6];                        // byte offsets of the taps on each deformed axis of Y
-    bool constant = !solved, inside = solved;
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        const int64_t len = g.out_len[h];
-        const double qh = solved ? q[h] : 0.0;
-        inside = inside && qh >= 0.0 && qh <= (double)(len - 1);
-        // boundary map, window and weights as deform_exact.hip has them (deform.c:768-824)
-        const double cc = map_coordinate(qh, len, v.mode);
-        const bool in = cc > -1.0;
-        constant = constant || !in;           // 'constant' outside the array (or a NaN coordinate): cval
-        const double c = in ? cc : 0.0;       // (a voxel that takes cval forms taps inside the array and loads nothing)
-        const int64_t start = window_start(c, order);
-        // (a tap past the order repeats tap 0: the row loads below need no branch, and its value is never added)
-        if (start < 0 || start + order >= len) {
-            int64_t first = 0;
-#pragma unroll
-            for (int l = 0; l < 6; ++l) {
-                int64_t idx = mirror_index(start + l, len);
-                // no load leaves the array, whatever the coordinate (no effect on a coordinate the boundary map produced)
-                idx = idx < 0 ? 0 : (idx > len - 1 ? len - 1 : idx);
-                if (l == 0)
-                    first = idx;
-                tap[h][l] = (l <= order ? idx : first) * v.in_stride[h];
-            }
-        } else {
-#pragma unroll
-            for (int l = 0; l < 6; ++l)
-                tap[h][l] = (l <= order ? start + l : start) * v.in_stride[h];
-        }
-        weights_by_order(c, order, w[h]);
-    }
+    bool constant, inside;
+    form_taps<N>(g, v, q, solved, w, tap, constant, inside);
 
     int64_t out_vox = 0;
 #pragma unroll
@@ -222,53 +164,13 @@ template <int N, bool LDS>
 __global__ __launch_bounds__(kUnwarpThreads) void unwarp_kernel(PointsArgs a, const UnwarpView u)
 {
     extern __shared__ double s_grid[];        // LDS: [N][ncp_0]...[ncp_{N-1}]
-    const int64_t b = blockIdx.y;
-    a.g.disp += b * a.disp_bstride;           // this sample's control grid
-    const GridGeom& g = a.g;
-    int64_t tstride[N];
-    int per = 0;
-    if constexpr (LDS) {
-        per = stage_grid_lds<N>(g, s_grid);
-        __syncthreads();
-        int64_t cs = 1;
-#pragma unroll
-        for (int k = N - 1; k >= 0; --k) {
-            tstride[k] = cs;
-            cs *= g.ncp[k];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            tstride[k] = g.disp_stride[k + 1];
-    }
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= u.nsrc)
-        return;
-    // source voxel index (extents I), last deformed axis fastest
     int64_t o[N];
-    {
-        int64_t r = tid;
-#pragma unroll
-        for (int k = N - 1; k >= 0; --k) {
-            const int64_t d = r / g.in_len[k];
-            o[k] = r - d * g.in_len[k];
-            r = d;
-        }
-    }
-    // the Newton phase: q with r(q) = p
-    double p[N], q[N];
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        p[h] = (double)o[h];
-        q[h] = 0.0;
-    }
+    double q[N];
     bool solved;
-    if constexpr (LDS)
-        solved = invert_map<N>(a, LdsGrid{s_grid, per}, tstride, p, q);
-    else
-        solved = invert_map<N>(a, GlobalGrid{g.disp, g.disp_stride[0], g.disp_dtype}, tstride, p, q);
+    if (!solve_voxel<N, LDS>(a, s_grid, u.nsrc, o, q, solved))
+        return;
     // the gather phase
-    resample<N>(g, u, b, o, q, solved);
+    resample<N>(a.g, u, blockIdx.y, o, q, solved);
 }
 
 template <int N>

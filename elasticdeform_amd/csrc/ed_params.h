@@ -257,6 +257,7 @@ hipError_t launch_deform_labels(const LabelsCall& c, hipStream_t stream);
 struct InverseCall {
     GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len = I (>= 2 each), out_len = O
     IOView v;                     // sample 0: v.in = Y (read, extents O), v.out = Z (written, extents I); order, mode, cval
+                                  // (the gradient: v.in = dY, added into; v.out = dZ, read)
     int nbatch;
     int64_t in_bstride, out_bstride, disp_bstride;   // bytes between samples
     BatchArray valid;             // uint8, deformed extents I: 1 = solved and inside Y
@@ -265,6 +266,10 @@ struct InverseCall {
     double tol;
 };
 hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream);
+// Its adjoint with respect to the image (deform_unwarp_grad.hip): the same solve and taps per source voxel, and
+// v.out (dZ, read, extents I) times the tap weights ADDED into v.in (dY, extents O) with float atomics.  float32 /
+// float64 only, v.in_dtype == v.out_dtype; v.cval and `valid` play no part.  One launch, no scratch.
+hipError_t launch_deform_inverse_gradient(const InverseCall& c, hipStream_t stream);
 
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;

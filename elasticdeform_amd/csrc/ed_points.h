@@ -1,6 +1,6 @@
 // ed_points.h -- what the kernels of deform_points.hip (the coordinate map at real positions and its inverse), of
-// deform_points_grad.hip (their adjoint) and of deform_unwarp.hip (an image resampled back through the deformation)
-// share: the argument block, the control grid's readers, the separable tap sum, r(q) with its Jacobian, the n x n solve
+// deform_points_grad.hip (their adjoint) and of deform_unwarp.hip / deform_unwarp_grad.hip (an image resampled back
+// through the deformation, and the adjoint of that) share: the argument block, the control grid's readers, the separable tap sum, r(q) with its Jacobian, the n x n solve
 // and the damped Newton inversion.  Notation: the head of deform_points.hip.
 #pragma once
 

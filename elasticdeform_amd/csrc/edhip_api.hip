@@ -1593,38 +1593,44 @@ int edhip_deform_labels(int nbatch, const edhip_array* input0, int64_t input_bat
     return EDHIP_OK;
 }
 
-// ---- an image carried back through the deformation (deform_unwarp.hip) ----------------------------------------
-int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
-                         const edhip_array* displacement0, int64_t displacement_batch_stride, const int64_t* in_len,
-                         const int64_t* output_offset, const edhip_array* output0, int64_t output_batch_stride,
-                         const edhip_array* valid0, int64_t valid_batch_stride, int naxis, const int32_t* axis,
-                         int32_t order, int32_t mode, double cval, const double* affine, const double* forward_linear,
-                         int max_iter, double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+// ---- an image carried back through the deformation (deform_unwarp.hip) and its adjoint (deform_unwarp_grad.hip) --
+// What edhip_deform_inverse and edhip_deform_inverse_gradient check and fill alike.  sampled0: the array of deformed
+// extents O (Y, or the accumulator dY); lattice0: the one of deformed extents in_len (Z, or the cotangent dZ), called
+// `lattice_name` in the messages; valid0: the forward's (nullptr otherwise).  float_only: float32 / float64 arrays
+// (the gradient); otherwise every dtype but the 16-bit floats.  *launch: there is something to launch.
+static int fill_inverse_call(const char* entry, int nbatch, const edhip_array* sampled0, int64_t sampled_batch_stride,
+                      const edhip_array* displacement0, int64_t displacement_batch_stride, const int64_t* in_len,
+                      const int64_t* output_offset, const edhip_array* lattice0, const char* lattice_name,
+                      int64_t lattice_batch_stride, const edhip_array* valid0, int64_t valid_batch_stride, int naxis,
+                      const int32_t* axis, int32_t order, int32_t mode, double cval, const double* affine,
+                      const double* forward_linear, int max_iter, double tol, uint32_t flags, bool float_only,
+                      ed::InverseCall& c, bool* launch, char* err, size_t errlen)
 {
     using namespace ed;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (int st = check_batch_call(nbatch, input0 && displacement0 && output0 && in_len, err, errlen))
+    *launch = false;
+    if (int st = check_batch_call(nbatch, sampled0 && displacement0 && lattice0 && in_len, err, errlen))
         return st;
-    if (int st = check_axes_1_to_3("edhip_deform_inverse", axis, naxis, err, errlen))
+    if (int st = check_axes_1_to_3(entry, axis, naxis, err, errlen))
         return st;
-    if (int st = check_prefiltered("edhip_deform_inverse", flags, err, errlen))
+    if (int st = check_prefiltered(entry, flags, err, errlen))
         return st;
-    const edhip_array& in = *input0;
-    const edhip_array& out = *output0;
-    if (int st = check_pairs(input0, output0, 1, naxis, axis, &order, &mode, &cval, false, err, errlen))
+    const edhip_array& in = *sampled0;
+    const edhip_array& out = *lattice0;
+    if (int st = check_pairs(sampled0, lattice0, 1, naxis, axis, &order, &mode, &cval, false, err, errlen))
         return st;
     for (int j = 1; j < naxis; ++j)
         if (axis[j] <= axis[j - 1])
             return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
     if (in.dtype != out.dtype)
         return fail(err, errlen, EDHIP_ERR_DTYPE, "input and output must have one dtype");
-    if (in.dtype == EDHIP_F16 || in.dtype == EDHIP_BF16)
+    if (float_only ? !f32_or_f64(&in) : (in.dtype == EDHIP_F16 || in.dtype == EDHIP_BF16))
         return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     int64_t sampled_len[kMaxAxes];
     for (int k = 0; k < naxis; ++k) {
         sampled_len[k] = in.shape[axis[k]];
         if (out.shape[axis[k]] != in_len[k])
-            return fail(err, errlen, EDHIP_ERR_INVALID, "the output's deformed axes must have the extents in_len");
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the %s's deformed axes must have the extents in_len",
+                        lattice_name);
         if (sampled_len[k] < 2)
             return fail(err, errlen, EDHIP_ERR_INVALID, "deformed axes must have at least 2 elements");
     }
@@ -1638,11 +1644,10 @@ int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_ba
         return st;
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
-    if (int st = check_batch_limit("edhip_deform_inverse", nbatch, err, errlen))
+    if (int st = check_batch_limit(entry, nbatch, err, errlen))
         return st;
-    InverseCall c;
     memset(&c, 0, sizeof(c));
-    // the solve's geometry is the forward call's (extents in_len); the sampled array has the input's own extents
+    // the solve's geometry is the forward call's (extents in_len); the sampled array has its own extents
     if (int st = fill_geometry(displacement0, in_len, sampled_len, output_offset, naxis, affine, c.g, err, errlen))
         return st;
     if (int st = make_view(in, out, naxis, axis, order, mode, cval, c.v, err, errlen))
@@ -1650,16 +1655,58 @@ int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_ba
     if (nbatch == 0 || c.v.nsteps <= 0)
         return EDHIP_OK;
     c.nbatch = nbatch;
-    c.in_bstride = input_batch_stride;
-    c.out_bstride = output_batch_stride;
+    c.in_bstride = sampled_batch_stride;
+    c.out_bstride = lattice_batch_stride;
     c.disp_bstride = displacement_batch_stride;
     c.valid = batch_array(valid0, valid_batch_stride);
     c.forward_linear = affine ? forward_linear : nullptr;
     c.max_iter = max_iter;
     c.tol = tol;
-    const hipError_t e = launch_deform_inverse(c, stream);
+    *launch = true;
+    return EDHIP_OK;
+}
+
+int edhip_deform_inverse(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                         const edhip_array* displacement0, int64_t displacement_batch_stride, const int64_t* in_len,
+                         const int64_t* output_offset, const edhip_array* output0, int64_t output_batch_stride,
+                         const edhip_array* valid0, int64_t valid_batch_stride, int naxis, const int32_t* axis,
+                         int32_t order, int32_t mode, double cval, const double* affine, const double* forward_linear,
+                         int max_iter, double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    ed::InverseCall c;
+    bool launch;
+    if (int st = fill_inverse_call("edhip_deform_inverse", nbatch, input0, input_batch_stride, displacement0,
+                                   displacement_batch_stride, in_len, output_offset, output0, "output",
+                                   output_batch_stride, valid0, valid_batch_stride, naxis, axis, order, mode, cval,
+                                   affine, forward_linear, max_iter, tol, flags, false, c, &launch, err, errlen))
+        return st;
+    if (!launch)
+        return EDHIP_OK;
+    const hipError_t e = ed::launch_deform_inverse(c, (hipStream_t)hip_stream);
     if (e != hipSuccess)
         return hip_fail(err, errlen, e, "deform inverse launch");
+    return EDHIP_OK;
+}
+
+int edhip_deform_inverse_gradient(int nbatch, const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                  const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                  const int64_t* in_len, const int64_t* output_offset, const edhip_array* dinput0,
+                                  int64_t dinput_batch_stride, int naxis, const int32_t* axis, int32_t order,
+                                  int32_t mode, const double* affine, const double* forward_linear, int max_iter,
+                                  double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    ed::InverseCall c;
+    bool launch;
+    if (int st = fill_inverse_call("edhip_deform_inverse_gradient", nbatch, dinput0, dinput_batch_stride,
+                                   displacement0, displacement_batch_stride, in_len, output_offset, cotangent0,
+                                   "cotangent", cotangent_batch_stride, nullptr, 0, naxis, axis, order, mode, 0.0,
+                                   affine, forward_linear, max_iter, tol, flags, true, c, &launch, err, errlen))
+        return st;
+    if (!launch)
+        return EDHIP_OK;
+    const hipError_t e = ed::launch_deform_inverse_gradient(c, (hipStream_t)hip_stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform inverse gradient launch");
     return EDHIP_OK;
 }
 

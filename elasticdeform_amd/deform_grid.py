@@ -1649,28 +1649,33 @@ def _inverse_shapes(X_shape, Ys, batch):
     return shapes
 
 
-def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter, tol,
-                 return_valid, batch):
-    """Both forms of deform_grid_inverse.  Every argument check runs before the device is touched; offsets, the inverse
-    map K and the rotate / zoom centre are those of the forward call on an array of shape X_shape (the same Plan)."""
+def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter,
+                  tol, return_valid, batch, gradient):
+    """The host path of deform_grid_inverse (A = Y) and of deform_grid_inverse_gradient (`gradient`: A = dZ, which has
+    the shape of X, so X_shape is not given; the result has the shape of Y), single call and batch.  Every argument
+    check runs before the device is touched; offsets, the inverse map K and the rotate / zoom centre are those of the
+    forward call on an array of shape X_shape (the same Plan)."""
     _check_iteration(max_iter, tol)
-    if batch and (not _host.is_array(Y) or Y.ndim < 2):
-        raise Exception('Y should be an array with a leading batch axis.')
-    Ys = [Y] if batch else _host.normalize_inputs(Y)
-    X_shapes = _inverse_shapes(X_shape, Ys, batch)
-    stand_ins = _shape_only(X_shapes[0], Y.shape[0]) if batch else [_host.ShapeOnly(s) for s in X_shapes]
+    if batch and (not _host.is_array(A) or A.ndim < 2):
+        raise Exception('%s should be an array with a leading batch axis.' % ('dZ' if gradient else 'Y'))
+    As = [A] if batch else _host.normalize_inputs(A)
+    a_shapes = [tuple(int(v) for v in a.shape[1 if batch else 0:]) for a in As]
+    X_shapes = a_shapes if gradient else _inverse_shapes(X_shape, As, batch)
+    stand_ins = _shape_only(X_shapes[0], A.shape[0]) if batch else [_host.ShapeOnly(s) for s in X_shapes]
     plan = _plan_of(stand_ins, batch, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
-    y_shapes = [tuple(int(v) for v in y.shape[1 if batch else 0:]) for y in Ys]
-    if [tuple(int(v) for v in s) for s in plan.output_shapes] != y_shapes:
+    y_shapes = [tuple(int(v) for v in s) for s in plan.output_shapes]
+    if not gradient and y_shapes != a_shapes:
         raise ValueError("Y does not match X_shape and cropping. Expected shape of Y is %s, but %s given."
-                         % (str([tuple(s) for s in plan.output_shapes]), str(y_shapes)))
-    names = [_volume_dtype_name(y) for y in Ys]
-    if any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in names):
+                         % (str(y_shapes), str(a_shapes)))
+    names = [_volume_dtype_name(a) for a in As]
+    if gradient:
+        _check_float_volumes(As)                          # cotangent and accumulator share a float32 / float64 dtype
+    elif any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in names):
         raise RuntimeError('data type not supported')     # complex, 16-bit floats
     n = plan.naxis
     if n > 3:
         raise RuntimeError('deform_grid_inverse takes 1 to 3 deformed axes')   # (the library's own limit)
-    lead = (int(Y.shape[0]),) if batch else ()
+    lead = (int(A.shape[0]),) if batch else ()
     deformed = tuple(int(v) for v in plan.deform_shape)
     sampled = tuple(int(y_shapes[0][a]) for a in plan.axis[0])
     degenerate = any(v == 1 for v in deformed)
@@ -1680,35 +1685,63 @@ def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, a
 
     if degenerate:
         # a deformed axis of X of length 1: the forward call maps every voxel to the constant and no position is
-        # defined (deform_points solves nothing there) -- cval everywhere, nothing valid
-        Zs = [_constant_result(y, lead + s, c) for y, s, c in zip(Ys, X_shapes, plan.cval)]
-        valids = [_fill(y, lead + deformed, 0, 'uint8') for y in Ys]
-    else:
-        K = plan.inverse_affine
-        M = _forward_linear(K, n)
-        torch = _torch()
-        device = _device_for(list(Ys) + [displacement])
-        Zs, valids = [], []
-        with torch.cuda.device(device):
-            stream = _stream(device)
-            df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
-            for i, y in enumerate(Ys):
-                yd = _to_device(y, device)
-                o = int(plan.order[i])
-                ax = plan.axis[i]
-                # Y is prepared as deform_grid prepares its input: filtered along its deformed axes (deform_grid.py:155-164)
-                yf = yd
-                if prefilter and o > 1:
-                    yf = _filter_axes(yd, [a + 1 for a in ax] if batch else ax, o, False, device, stream=stream)
-                out = torch.empty(lead + X_shapes[i], dtype=yd.dtype, device=device)
+        # defined (deform_points solves nothing there) -- cval everywhere, nothing valid, and nothing depends on Y
+        if gradient:
+            return _list_or_one([_fill(a, lead + s, 0.0) for a, s in zip(As, y_shapes)], None, False, A)
+        Zs = [_constant_result(y, lead + s, c) for y, s, c in zip(As, X_shapes, plan.cval)]
+        valids = [_fill(y, lead + deformed, 0, 'uint8') for y in As]
+        return _list_or_one(Zs, valids, return_valid, A)
+
+    K = plan.inverse_affine
+    M = _forward_linear(K, n)
+    torch = _torch()
+    device = _device_for(list(As) + [displacement])
+    results, valids = [], []
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
+        for i, a in enumerate(As):
+            ad = _to_device(a, device)
+            o = int(plan.order[i])
+            ax = plan.axis[i]
+            # Y is prepared as deform_grid prepares its input: filtered along its deformed axes (deform_grid.py:155-164);
+            # the gradient applies the transposed filter to its result
+            filter_axes = ([d + 1 for d in ax] if batch else ax) if prefilter and o > 1 else []
+            nb = lead[0] if batch else 1
+            # one library call (one launch) per input: the solve is done again for each
+            if gradient:
+                acc = torch.zeros(lead + y_shapes[i], dtype=ad.dtype, device=device)
+                _lib.deform_inverse_gradient(nb, *_sample(ad, batch), *_sample(df, batch), deformed,
+                                             plan.output_offset, *_sample(acc, batch), ax, o, int(plan.mode[i]), K, M,
+                                             int(max_iter), float(tol), 0, stream)
+                acc = _filter_axes(acc, filter_axes, o, True, device, overwrite=True, stream=stream)
+                results.append(_from_device(acc, a))
+            else:
+                yf = _filter_axes(ad, filter_axes, o, False, device, stream=stream)
+                out = torch.empty(lead + X_shapes[i], dtype=ad.dtype, device=device)
                 ok = torch.empty(lead + deformed, dtype=torch.uint8, device=device) if return_valid else None
-                # one library call (one launch) per input: the solve is done again for each
-                _lib.deform_inverse(lead[0] if batch else 1, *_sample(yf, batch), *_sample(df, batch), deformed,
-                                    plan.output_offset, *_sample(out, batch), *_sample(ok, batch), ax, o,
-                                    int(plan.mode[i]), float(plan.cval[i]), K, M, int(max_iter), float(tol), 0, stream)
-                Zs.append(_from_device(out, y))
-                valids.append(_from_device(ok, y) if ok is not None else None)
-    return _list_or_one(Zs, valids, return_valid, Y)
+                _lib.deform_inverse(nb, *_sample(yf, batch), *_sample(df, batch), deformed, plan.output_offset,
+                                    *_sample(out, batch), *_sample(ok, batch), ax, o, int(plan.mode[i]),
+                                    float(plan.cval[i]), K, M, int(max_iter), float(tol), 0, stream)
+                results.append(_from_device(out, a))
+                valids.append(_from_device(ok, a) if ok is not None else None)
+    return _list_or_one(results, valids, return_valid and not gradient, A)
+
+
+def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter, tol,
+                 return_valid, batch):
+    """Both forms of deform_grid_inverse.  With grad mode on and a floating-point tensor Y that requires grad, the call
+    goes through the autograd Function of elasticdeform_amd.torch, whose forward comes back here with grad mode off:
+    the plain path."""
+    torch = sys.modules.get('torch')                      # (a tensor can only arrive with torch imported)
+    if torch is not None and torch.is_grad_enabled() and any(
+            torch.is_tensor(y) and y.is_floating_point() and y.requires_grad
+            for y in (Y if isinstance(Y, list) else [Y])):
+        from . import torch as _autograd
+        return _autograd._inverse_with_autograd(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine,
+                                                rotate, zoom, max_iter, tol, return_valid, batch)
+    return _inverse_host(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                         max_iter, tol, return_valid, batch, False)
 
 
 def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
@@ -1741,7 +1774,13 @@ def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval
     ``order > 1``, as deform_grid prepares its input.  ``displacement``, ``crop``, ``axis``, ``affine``, ``rotate`` and
     ``zoom`` are the forward call's own, checked the same way; ``Y`` must have the shape that call returns.  A deformed
     axis of ``X`` of length 1 gives ``cval`` everywhere and nothing valid; every deformed axis of ``Y`` needs at least
-    2 elements.  numpy in gives numpy out, tensors stay on their device.  No autograd flows through this call.
+    2 elements.  numpy in gives numpy out, tensors stay on their device.
+
+    Autograd: with grad mode on, a floating-point tensor ``Y`` that requires grad gives a ``Z`` with a ``grad_fn``; its
+    backward is :func:`deform_grid_inverse_gradient`, the exact adjoint in ``Y`` (float atomics: the last bits of
+    ``Y.grad`` may differ between runs).  ``valid`` is not differentiable, and no gradient goes to ``displacement``,
+    ``affine``, ``rotate`` or ``zoom``.  In a list, each ``Y`` that requires grad gets its gradient.  Every other call
+    -- numpy arrays, integer tensors, tensors that do not require grad -- is untouched by this.
     """
     return _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
                         max_iter, tol, return_valid, False)
@@ -1756,3 +1795,43 @@ def deform_grid_inverse_batch(Y, displacements, X_shape, order=3, mode='constant
     sample b, bit for bit (``Z`` and ``valid``)."""
     return _inverse_run(Y, displacements, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
                         max_iter, tol, return_valid, True)
+
+
+def deform_grid_inverse_gradient(dZ, displacement, order=3, mode='constant', crop=None, prefilter=True, axis=None,
+                                 affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9):
+    """
+    Gradient of :func:`deform_grid_inverse` with respect to ``Y``: for ``L`` with ``dZ = dL / dZ`` and
+    ``Z = deform_grid_inverse(Y, displacement, X_shape, ...)``, returns ``dL / dY``.  ``dZ`` has the shape of ``X``
+    (channels included; it takes the place of ``X_shape``), the result the shape of ``Y`` -- the shape the forward call
+    returns for the crop -- and ``dZ``'s dtype.
+
+    For fixed deformation arguments and ``cval = 0`` the call is linear in ``Y``: ``Z[p] = sum_j A[p, j] Yf[j]`` with
+    ``Yf`` the prefiltered ``Y`` and the row ``A[p, :]`` the ``(order + 1)^naxis`` products of tap weights at ``q(p)``
+    (taps that the mirror edge rule folds onto one cell add up).  The row is empty where ``p`` is not solved, and where
+    ``mode='constant'`` and ``q(p)`` lies outside ``Y``.  The result is ``P^T A^T dZ``, ``P^T`` the transposed
+    prefilter along the deformed axes (``order > 1`` and ``prefilter=True``): the exact adjoint, in the sense
+    :func:`deform_grid_gradient` is for :func:`deform_grid`.  ``q(p)`` is solved again, exactly as the forward solves
+    it (``max_iter``, ``tol``).  ``cval`` plays no part, ``valid`` is not differentiable, and **no gradient goes to
+    the displacement or to affine / rotate / zoom** through this call.
+
+    ``dZ``: a float32 or float64 array, or a list of them (per-input ``order`` / ``mode`` / ``axis`` lists as in
+    :func:`deform_grid_inverse`); everything else raises ``RuntimeError('data type not supported')``.  The products
+    are formed in fp64 and added with float atomics in ``dZ``'s dtype: which cell receives what is fixed, but the
+    order of the adds is not, so the last bits may differ between two calls, and between a batch sample and the
+    single call (the caveat of ``set_gradient_accumulation('float')`` and of the float64 route of
+    :func:`deform_grid_gradient`).  Sums of exactly representable terms -- order 0 with integer-valued ``dZ`` -- are
+    exact and reproducible.  A deformed axis of ``X`` of length 1 gives zeros.  numpy in gives numpy out, tensors stay
+    on their device.
+    """
+    return _inverse_host(dZ, displacement, None, order, mode, 0.0, crop, prefilter, axis, affine, rotate, zoom,
+                         max_iter, tol, False, False, True)
+
+
+def deform_grid_inverse_gradient_batch(dZ, displacements, order=3, mode='constant', crop=None, prefilter=True,
+                                       axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9):
+    """:func:`deform_grid_inverse_gradient` over a batch with one control grid per sample
+    (:func:`deform_grid_inverse_batch`): ``dZ`` ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``axis`` counts
+    the axes of one sample; everything else is shared.  One launch for the batch; sample b equals the single call on
+    sample b up to the order of the float adds."""
+    return _inverse_host(dZ, displacements, None, order, mode, 0.0, crop, prefilter, axis, affine, rotate, zoom,
+                         max_iter, tol, False, True, True)

@@ -27,8 +27,10 @@ from . import deform_grid_coordinates as _deform_grid_coordinates_fn
 from . import deform_points as _deform_points_fn
 # label-aware linear resampling of label maps (integer tensors stay on their device; no autograd)
 from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
-# an image resampled back through the deformation (tensors stay on their device; no autograd)
+# an image resampled back through the deformation and its adjoint: the package's own names (tensors stay on their
+# device).  A Y that requires grad makes deform_grid_inverse itself go through DeformGridInverse below.
 from . import deform_grid_inverse, deform_grid_inverse_batch  # noqa: F401
+from . import deform_grid_inverse_gradient, deform_grid_inverse_gradient_batch  # noqa: F401
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)
@@ -412,3 +414,61 @@ def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=No
                                dict(X_shape=X_shape, crop=crop, axis=axis, max_iter=max_iter, tol=tol),
                                bool(displacement_grad))
     return (q, ok) if return_converged else q
+
+
+# ---- an image carried back through the deformation, with autograd -----------------------------------------------------
+
+def _per_input_subset(value, idx, n):
+    """a per-input list of `n` arguments cut down to the inputs `idx`; a shared value stays as it is"""
+    return [value[i] for i in idx] if isinstance(value, list) and len(value) == n else value
+
+
+class DeformGridInverse(torch.autograd.Function):
+    """forward: deform_grid_inverse(_batch), the plain path (grad mode is off in here); backward:
+    deform_grid_inverse_gradient(_batch) on the cotangents of the Z whose Y needs a gradient.  Inputs: the
+    displacement, the call's keywords, the batch flag, whether Y came as a list, then every Y; outputs: every Z, then
+    every valid."""
+
+    @staticmethod
+    def forward(ctx, displacement, kw, batch, as_list, *ys):
+        ctx.displacement = displacement.detach() if torch.is_tensor(displacement) else displacement
+        ctx.kw, ctx.batch, ctx.n = kw, batch, len(ys)
+        res = _api._inverse_run(list(ys) if as_list else ys[0], ctx.displacement, batch=batch, **kw)
+        res = res if as_list else [res]
+        zs, valids = (zip(*res) if kw['return_valid'] else (res, ()))
+        needs = ctx.needs_input_grad[4:]
+        ctx.mark_non_differentiable(*[t for t in valids if torch.is_tensor(t)],
+                                    *[z for z, need in zip(zs, needs) if torch.is_tensor(z) and not need])
+        return tuple(zs) + tuple(valids)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *douts):
+        n, kw = ctx.n, ctx.kw
+        idx = [i for i in range(n) if ctx.needs_input_grad[4 + i]]
+        grads = [None] * n
+        if idx:
+            call = dict(crop=kw['crop'], prefilter=kw['prefilter'], affine=kw['affine'], rotate=kw['rotate'],
+                        zoom=kw['zoom'], max_iter=kw['max_iter'], tol=kw['tol'])
+            if ctx.batch:
+                grads[0] = deform_grid_inverse_gradient_batch(douts[0].detach(), ctx.displacement, order=kw['order'],
+                                                              mode=kw['mode'], axis=kw['axis'], **call)
+            else:
+                per_input = {k: _per_input_subset(kw[k], idx, n) for k in ('order', 'mode', 'axis')}
+                for i, g in zip(idx, deform_grid_inverse_gradient([douts[i].detach() for i in idx], ctx.displacement,
+                                                                  **per_input, **call)):
+                    grads[i] = g
+        return (None, None, None, None) + tuple(grads)
+
+
+def _inverse_with_autograd(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                           max_iter, tol, return_valid, batch):
+    """deform_grid_inverse(_batch) through DeformGridInverse (elasticdeform_amd.deform_grid._inverse_run sends a Y that
+    requires grad here); results in the plain call's form"""
+    as_list = isinstance(Y, list)
+    ys = Y if as_list else [Y]
+    kw = dict(X_shape=X_shape, order=order, mode=mode, cval=cval, crop=crop, prefilter=prefilter, axis=axis,
+              affine=affine, rotate=rotate, zoom=zoom, max_iter=max_iter, tol=tol, return_valid=return_valid)
+    outs = DeformGridInverse.apply(displacement, kw, batch, as_list, *ys)
+    res = list(zip(outs[:len(ys)], outs[len(ys):])) if return_valid else list(outs)
+    return res if as_list else res[0]

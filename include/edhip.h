@@ -581,6 +581,45 @@ int edhip_deform_inverse(int nbatch,
                          char* err, size_t errlen);
 
 /*
+ * The adjoint of edhip_deform_inverse with respect to its input (no counterpart in the reference).  For fixed
+ * deformation arguments and cval = 0, Z = edhip_deform_inverse(Y) is linear in Y: Z[p, step] = sum_j A[p, j] Y[j, step],
+ * the row A[p, :] holding the (order + 1)^naxis products of tap weights at q(p); taps that the mirror edge rule folds
+ * onto one cell add up.  The row is empty where p is not solved, and where the mode is 'constant' and q(p) lies
+ * outside Y.  This call ADDS A^T dZ into dinput0:
+ *   dinput0[j, step] += sum_p A[p, j] cotangent0[p, step].
+ * The caller zeroes dinput0 beforehand and, for order > 1, applies the transposed prefilter along the deformed axes
+ * afterwards (edhip_spline_filter_axes with transpose) -- as it prefilters Y before edhip_deform_inverse.  cval plays
+ * no part; nothing flows to the control grid or to the affine map.  The solve (start, step, halvings, tol, max_iter)
+ * and the taps and weights are those of edhip_deform_inverse: the same device code.
+ * Arguments as for edhip_deform_inverse, except:
+ *   cotangent0           dZ, read: float32 / float64 (anything else: EDHIP_ERR_DTYPE), deformed extents in_len
+ *                        (EDHIP_ERR_INVALID), any strides.  Takes the place of output0.
+ *   dinput0              the accumulator dY, added into: cotangent0's dtype (EDHIP_ERR_DTYPE) and non-deformed axes,
+ *                        deformed extents O (>= 2 each: EDHIP_ERR_INVALID), any strides.  Takes the place of input0.
+ *   (no valid0, no cval)
+ * The products are formed in fp64 and rounded once to the accumulator's type; the adds are device-scope float atomics
+ * in that type.  Which cell receives which product is fixed by the arguments, but the ORDER in which the adds arrive
+ * is not: the last bits of a sum may differ from call to call, and between a sample of a batch and the single call
+ * (the caveat of the float64 gradient of edhip_deform).  Sums of exactly representable terms (order 0 with integer
+ * cotangents) are exact and reproducible.  No add leaves dinput0, whatever the coordinate.
+ * Every shape, dtype and flag check answers before any launch.  One launch, one thread per source voxel.  The call
+ * enqueues on hip_stream, never synchronises and uses no workspace, so it can be captured into a HIP graph.
+ */
+int edhip_deform_inverse_gradient(int nbatch,
+                                  const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                  const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                  const int64_t* in_len,
+                                  const int64_t* output_offset,
+                                  const edhip_array* dinput0, int64_t dinput_batch_stride,
+                                  int naxis, const int32_t* axis,
+                                  int32_t order, int32_t mode,
+                                  const double* affine,
+                                  const double* forward_linear,
+                                  int max_iter, double tol,
+                                  uint32_t flags, void* hip_stream,
+                                  char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
