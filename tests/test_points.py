@@ -14,8 +14,6 @@ Expected values come from sources that share no code with the kernel:
 Tolerance for coordinates: 1e-10 absolute (coordinates and coefficients below 1e3; both sides are fp64 sums of at
 most 4^n terms and the two CPU sources agree to 1.6e-14; a wrong tap, weight or offset shows at 1e-3 or more).
 """
-import itertools
-
 import numpy as np
 import pytest
 
@@ -30,53 +28,9 @@ import elasticdeform_amd.torch as etorch  # noqa: E402
 TOL = 1e-10
 
 
-# ---- the NumPy restatement -----------------------------------------------------------------------------------
+# ---- the NumPy restatement (oracle/dgrad_reference.py, shared with the gradient tests) ----------------------------
 
-def _prefiltered(D):
-    import scipy.ndimage
-    P = np.array(D, dtype=np.float64)
-    for d in range(1, P.ndim):
-        P = scipy.ndimage.spline_filter1d(P, order=3, axis=d, mode="mirror")
-    return P
-
-
-def _mirror(i, n):
-    if n == 1:
-        return np.zeros_like(i)
-    period = 2 * n - 2
-    j = np.mod(i, period)
-    return np.where(j >= n, period - j, j)
-
-
-def _weights(x):
-    z = 1.0 - x
-    w0 = z * z * z / 6.0
-    w1 = (x * x * (x - 2.0) * 3.0 + 4.0) / 6.0
-    w2 = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0
-    return np.stack([w0, w1, w2, 1.0 - w0 - w1 - w2], axis=-1)
-
-
-def restate(q, D, I, off=None, K=None):
-    """r(q) for q of shape (N, n): the formulas of the issue, vectorised over the points"""
-    q = np.asarray(q, dtype=np.float64)
-    n = D.shape[0]
-    ncp = D.shape[1:]
-    P = _prefiltered(D)
-    off = np.zeros(n) if off is None else np.asarray(off, dtype=np.float64)
-    K = np.concatenate([np.eye(n), np.zeros((n, 1))], axis=1) if K is None else np.asarray(K, dtype=np.float64)
-    idx, W = [], []
-    for k in range(n):
-        cp = (ncp[k] - 1) * (q[:, k] + off[k]) / (I[k] - 1)
-        fl = np.floor(cp)
-        W.append(_weights(cp - fl))
-        idx.append(_mirror(fl.astype(np.int64)[:, None] - 1 + np.arange(4)[None, :], ncp[k]))
-    delta = np.zeros((q.shape[0], n))
-    for taps in itertools.product(range(4), repeat=n):
-        w = np.ones(q.shape[0])
-        for k in range(n):
-            w = w * W[k][:, taps[k]]
-        delta += P[(slice(None),) + tuple(idx[k][:, taps[k]] for k in range(n))].T * w[:, None]
-    return q @ K[:, :n].T + K[:, n] + off + delta
+from oracle.dgrad_reference import coordinate as restate  # noqa: E402
 
 
 def restate_jacobian(q, D, I, off=None, K=None, h=1e-4):
