@@ -1,7 +1,7 @@
 // deform_k1.hip -- K1, the forward gather of the benchmark case: float32 volumes, 3 deformed axes, unit stride
 // along x on both sides, spline orders 1-3 (deform.c:649-924).  Round 5: rebuilt around the VALU issue budget
 // (profiles/r04_pmc_summary.txt: the round-4 kernel issued 340 vector instructions per 64 voxels, 84 of them
-// the gather's FMAs).  What is different from the kernel it replaces (csrc/experiments/deform_hot_r4.hip):
+// the gather's FMAs).  What is different from the kernel it replaced (the round-4 hot_fwd_kernel):
 //
 //   * SAMPLED TILE BOXES.  The source box of an 8^3 output tile used to be the exact bounding box of the tile's
 //     512 tap windows: every voxel's window start went through 12 min / max, a 36-step DPP reduction and six LDS

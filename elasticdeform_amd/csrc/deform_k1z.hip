@@ -176,18 +176,6 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
     int* sCls = reinterpret_cast<int*>(sZ + 4 * hg.tiles[0]);        // [tiles_z]: class of every tile of the column
     int* sBox = sCls + hg.tiles[0];                                  // [tiles_z][raw | mapped][4 sampled slices][8]: sample ranges
     int* sCnt = sBox + 64 * hg.tiles[0];                             // [4]          // [tiles_z][4]: z entries of the sampled slices
-    if ((int)blockIdx.x >= hg.tiles[1] * hg.tiles[2]) {
-        // spare workgroups: clear the gradient accumulators (EDHIP_FLAG_ZERO_GRADIENT) while the others compute the tables
-        const long long nfill = (long long)(gridDim.x - hg.tiles[1] * hg.tiles[2]) * kGeoBlock;
-        const long long me = (long long)(blockIdx.x - hg.tiles[1] * hg.tiles[2]) * kGeoBlock + tid;
-        const long long n16 = zg.zero_bytes >> 4;
-        int4* p16 = reinterpret_cast<int4*>(zg.zero_ptr);
-        for (long long i = me; i < n16; i += nfill)
-            p16[i] = make_int4(0, 0, 0, 0);
-        if (me < (zg.zero_bytes & 15))
-            zg.zero_ptr[(n16 << 4) + me] = 0;
-        return;
-    }
     const int ty = blockIdx.x / hg.tiles[2], tx = blockIdx.x - ty * hg.tiles[2];
     if (ED_DBG(hg.dbg, 1 << 23))
         return;
@@ -245,7 +233,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
         zaxis_entry(g, a, oi, t.w, t.idx);
         sAx[tid] = t;
     }
-    for (int e = tid; e < 4 * hg.tiles[0] && !zg.tables_only && !ED_DBG(hg.dbg, 1 << 26); e += kGeoBlock) {
+    for (int e = tid; e < 4 * hg.tiles[0] && !ED_DBG(hg.dbg, 1 << 26); e += kGeoBlock) {
         const int tz = e >> 2, nz = min(kT, hg.out_len[0] - tz * kT);
         AxTab t;
         zaxis_entry(g, 0, tz * kT + ((e & 3) * (nz - 1)) / 3, t.w, t.idx);
@@ -344,8 +332,6 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
                 rg[((int64_t)oy * hg.out_len[2] + ox) * (4 * ncpz) + jj] = h < 3 ? sR[(py * 8 + px) * (ncpz * 3) + kz * 3 + h] : 0.0;
         }
     }
-    if (zg.tables_only)
-        return;          // (the gradient route: R, the z table and ZGen are all it reads)
     __syncthreads();
     ZTICK(5);
     // ---- tile boxes of the patch's z column: wave w samples tiles w, w + 8, ...; lane 63 leaves the reduced ranges in LDS
@@ -1362,15 +1348,10 @@ bool k1z_supported(const GridGeom& g)
 hipError_t launch_k1z_geo(const GridGeom& g, const HotGeom& hg, const ZGeom& zg, const GridPrefilter& gp, int nbatch,
                           hipStream_t stream)
 {
-    unsigned fill = 0;
-    if (zg.zero_ptr && zg.zero_bytes > 0) {
-        const long long want = (zg.zero_bytes + 65535) / 65536;       // 64 KiB per workgroup and round
-        fill = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-    }
-    hipLaunchKernelGGL(k1z_geo_kernel, dim3((unsigned)(hg.tiles[1] * hg.tiles[2]) + fill, (unsigned)nbatch), dim3(kGeoBlock),
+    hipLaunchKernelGGL(k1z_geo_kernel, dim3((unsigned)(hg.tiles[1] * hg.tiles[2]), (unsigned)nbatch), dim3(kGeoBlock),
                        k1z_geo_lds_bytes(g, hg), stream, g, hg, zg, gp);
     if (ed_env("EDHIP_GEO_TWICE"))        // (profiling build: the launch again, warm -- what of its 34 us is a cold instruction cache?)
-        hipLaunchKernelGGL(k1z_geo_kernel, dim3((unsigned)(hg.tiles[1] * hg.tiles[2]) + fill, (unsigned)nbatch), dim3(kGeoBlock),
+        hipLaunchKernelGGL(k1z_geo_kernel, dim3((unsigned)(hg.tiles[1] * hg.tiles[2]), (unsigned)nbatch), dim3(kGeoBlock),
                            k1z_geo_lds_bytes(g, hg), stream, g, hg, zg, gp);
     return hipGetLastError();
 }

@@ -182,31 +182,6 @@ __global__ __launch_bounds__(kBlock) void tile_tables_kernel(const GridGeom g, c
     };
     if (tid == 0)
         entry(0, oz, tz_);
-    if (oz == 0 && tg.keep_mode) {
-        // the control-grid values this call works from: kept for (1) / compared with (2) the gradient
-        // call that wants to use the forward call's coordinate records
-        const int nz = (int)g.ncp[0];
-        const int ntot = 3 * nz * nyx;
-        double* stash = tg.keep_stash + (int64_t)sample * ntot;
-        int same = 1;
-        for (int e = tid; e < ntot; e += kBlock) {
-            const int h = e / (nz * nyx), r = e - h * (nz * nyx);
-            const int j0 = r / nyx, j = r - j0 * nyx;
-            const int j1 = j / ncpx, j2 = j - j1 * ncpx;
-            const double val = dval(h, j0, j1, j2);
-            if (tg.keep_mode == 1) {
-                stash[e] = val;
-            } else if (__double_as_longlong(stash[e]) != __double_as_longlong(val)) {
-                same = 0;
-                stash[e] = val;       // the records-only launch behind this kernel remakes the records from `val`
-            }
-        }
-        if (tg.keep_mode == 2) {
-            same = __syncthreads_and(same);
-            if (tid == 0)
-                tg.keep_flags[sample] = same;
-        }
-    }
     // wide control grids (TileGeom::q_win): the lowest control column each x-strip touches
     __shared__ int c0s[256];
     if (tg.q_win) {
@@ -1151,16 +1126,64 @@ inline size_t q_global_bytes(const GridGeom& g, bool wide_opt = false)
     }
     return 8 * (size_t)g.out_len[0] * (size_t)g.out_len[1] * 4 * cols;
 }
-// The geometry buffer of the forward route of deform_k1z.hip (ed::GeoBuffer, its own allocation):
-//   counters (4 KiB, cleared at allocation) | ZGen (512) | z table | tile records (32 bytes per tile), flags and summaries
-//   (4 + 4 per strip, at most one strip per tile), two work lists dealt per XCD (entry k of XCD x at slot 8 k + x: 32 + 32
-//   per strip, in case one XCD gets them all), records of the tiles' z halves (64) | step offsets | R
+// The geometry buffer of the forward route of deform_k1z.hip (ed::GeoBuffer, its own allocation), size and layout:
+//   counters (4 KiB, cleared at allocation) | ZGen (512) | z table | the per-tile arrays | step offsets | R per sample
+// Per tile: its record (8 ints), a flag and a summary (1 + 1 per strip, at most one strip per tile), a slot in each of the
+// two work lists dealt per XCD (entry k of XCD x at slot 8 k + x: 8 + 8 per strip, in case one XCD gets them all) and the
+// records of its z halves (16).
 constexpr size_t kK1zMaxSteps = 4096;
-inline size_t k1z_zt_bytes(const GridGeom& g) { return (sizeof(AxTab) * (size_t)g.out_len[0] + 63) & ~(size_t)63; }
-inline size_t k1z_geo_bytes(const GridGeom& g, int64_t ntiles, int nbatch)
+constexpr size_t kK1zRecInts = 8, kK1zMissedInts = 1, kK1zInfoInts = 1, kK1zListInts = 8, kK1zHalfInts = 16;
+constexpr size_t kK1zTileBytes = sizeof(int) * (kK1zRecInts + kK1zMissedInts + kK1zInfoInts + 2 * kK1zListInts + kK1zHalfInts);
+struct K1zGeoLayout {
+    size_t zgen, zt, recs, missed, sinfo, list_g, list_f, recs_half, steps, r;   // byte offsets
+    size_t r_stride;      // bytes between the R tables of consecutive samples
+    size_t total;
+};
+inline K1zGeoLayout k1z_geo_layout(const GridGeom& g, int64_t ntiles, int nbatch)
 {
-    return 4096 + 512 + k1z_zt_bytes(g) + (((size_t)ntiles * (size_t)nbatch * 168 + 63) & ~(size_t)63) + kK1zMaxSteps * 16 +
-           ((k1z_r_bytes(g) * (size_t)nbatch + 63) & ~(size_t)63);
+    auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t nt = (size_t)ntiles * (size_t)nbatch;
+    K1zGeoLayout l;
+    l.zgen = 4096;
+    l.zt = l.zgen + 512;
+    l.recs = l.zt + pad64(sizeof(AxTab) * (size_t)g.out_len[0]);
+    l.missed = l.recs + nt * kK1zRecInts * sizeof(int);
+    l.sinfo = l.missed + nt * kK1zMissedInts * sizeof(int);
+    l.list_g = l.sinfo + nt * kK1zInfoInts * sizeof(int);
+    l.list_f = l.list_g + nt * kK1zListInts * sizeof(int);
+    l.recs_half = l.list_f + nt * kK1zListInts * sizeof(int);
+    l.steps = l.recs + pad64(nt * kK1zTileBytes);
+    l.r = l.steps + kK1zMaxSteps * 2 * sizeof(long long);
+    l.r_stride = pad64(k1z_r_bytes(g));
+    l.total = l.r + l.r_stride * (size_t)nbatch;
+    return l;
+}
+
+// margin of the sampled tile boxes (deform_k1.hip, deform_k1z.hip): 15 % of the rigorous bound of multilinear
+// interpolation between samples (see the tables kernel) -- everything of it but the largest control coefficient
+inline double box_margin_scale(const GridGeom& g)
+{
+    double r2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double r = g.in_len[k] > 1 ? (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1) : 0.0;
+        r2 += r * r;
+    }
+    return 0.15 * 1.125 * 4.0 * r2;
+}
+
+// A raw control grid (EDHIP_FLAG_RAW_DISPLACEMENT) is filtered inside the tables launch or the geometry launch when that
+// launch's LDS holds it next to the `lds_beside` bytes the kernel keeps there anyway; returns whether `gp` now says so
+// (otherwise gp.total == 0, gridpf_done stays false and edhip_deform issues the one-workgroup prefilter first).
+inline bool take_grid_prefilter(const DeformBatch* batch, int nb, size_t lds_beside, GridPrefilter& gp)
+{
+    memset(&gp, 0, sizeof(gp));
+    if (!(batch && batch->gridpf && nb == 1 && batch->gridpf->total <= 4096 &&
+          lds_beside + sizeof(double) * (size_t)batch->gridpf->total <= 60 * 1024))
+        return false;
+    gp = *batch->gridpf;
+    gp.zero_ptr = nullptr;
+    gp.zero_bytes = 0;
+    return true;
 }
 
 // ================================================================================================
@@ -1284,6 +1307,118 @@ void profile_mark(bool after, hipStream_t stream)
         t_ev_pending = true;
 }
 
+// Level-1 spill feedback (float32, orders 1-5: the kernels of deform_hot.hip, deform_k1.hip, deform_k1z.hip and
+// deform_wave.hip): what the recent calls of this geometry on this stream reported (ed_workspace.h, SpillHint) decides
+// between the standard, the large and the huge boxes, and whether level 1 serves every tile itself.
+struct SpillFeedback {
+    bool large_boxes = false, huge_boxes = false;
+    // self-serve: the recent calls of this geometry left at most a handful of tiles to the spill list -- level 1
+    // then takes such tiles itself (straight from / to global memory) and the two spill launches are not made
+    // (self_serve_boxes: the same for a gradient call that works from the forward call's boxes)
+    bool self_serve = false, self_serve_boxes = false;
+    unsigned long long* hint_host = nullptr;       // TileGeom::hint_host; nullptr: this call takes no part in the feedback
+    unsigned hint_seq = 0;
+};
+SpillFeedback spill_feedback(const GridGeom& g, int mode, int order, bool grad, int nb, int64_t ntiles, hipStream_t stream)
+{
+    SpillFeedback f;
+    SpillHint* sh = ed_env("EDHIP_NO_SPILL_HINT") ? nullptr : spill_hint(stream);
+    if (!sh)
+        return f;
+    auto geometry_key = [&](bool gradient) {
+        unsigned long long key = 1469598103934665603ull;
+        auto mix = [&](unsigned long long x) { key = (key ^ x) * 1099511628211ull; };
+        for (int k = 0; k < 3; ++k) {
+            mix((unsigned long long)g.in_len[k]);
+            mix((unsigned long long)g.out_len[k]);
+            mix((unsigned long long)g.off[k]);
+            mix((unsigned long long)g.ncp[k]);
+        }
+        mix((unsigned long long)order | ((unsigned long long)gradient << 8) | ((unsigned long long)mode << 16) |
+            ((unsigned long long)g.has_affine << 24) | ((unsigned long long)nb << 32));
+        return key;
+    };
+    const unsigned long long key = geometry_key(grad);
+    sh->absorb();
+    // (forward, K1z: the large boxes pay from ~6 % of the tiles beyond the standard box -- 256^3, sigma 7.5: 1.2 %,
+    // 202 against 225 us; sigma 10: 8.9 %, 249 against 237 us -- profiles/r06_sigma_sweep.txt)
+    f.large_boxes = sh->fraction(key) > (grad ? 0.10f : 0.06f);
+    // (K2 counts a tile beyond the LARGE box kHintHuge times: a tenth of the tiles there -> the huge boxes)
+    f.huge_boxes = grad && sh->fraction(key) > 0.10f * (float)tile::kHintHuge;
+    // Forward: a tile gathered straight from global memory costs its workgroup ~10 us, so a handful may stay.
+    // Gradient: 64 global float atomics per voxel, ~50 us per 16-wide tile (31 such tiles of a 128^3 volume
+    // took K2 from 56 to 141 us).  A gradient call WITH the forward call's boxes takes its oversize tiles as
+    // x-halves, and what is left is what the forward call could not hold either: it serves itself when the
+    // FORWARD calls of the geometry left at most a few tiles (decided in launch_tile, where the boxes are known to
+    // be there); without the boxes only where its own recent calls left nothing at all.
+    f.self_serve = sh->known(key) && sh->fraction(key) * (float)(ntiles * nb) <= (grad ? 0.5f : 64.f);
+    if (grad) {
+        const unsigned long long fkey = geometry_key(false);
+        f.self_serve_boxes = sh->known(fkey) && sh->fraction(fkey) * (float)(ntiles * nb) <= 8.f;
+    }
+#ifdef EDHIP_EXPERIMENTS
+    if (const char* ss = ed_env("EDHIP_SELF_SERVE"))
+        f.self_serve = f.self_serve_boxes = atoi(ss) != 0;
+    if (const char* lb = ed_env("EDHIP_LARGE_BOXES"))       // 0 never, 1 always, 2 forward only, 3 gradient only
+        f.large_boxes = atoi(lb) == 1 || (atoi(lb) == 2 && !grad) || (atoi(lb) == 3 && grad) || atoi(lb) == 4;
+    if (const char* lb = ed_env("EDHIP_LARGE_BOXES"))
+        f.huge_boxes = grad && atoi(lb) == 4;
+#endif
+    f.hint_host = sh->dev;
+    f.hint_seq = sh->begin_call(key, (unsigned)(ntiles * nb));
+    return f;
+}
+
+// The argument block of the level-1 kernels (ed_tile.h) from the tile geometry, the element-stride view `ve` and the
+// caller's view `v`; box sizes, spill feedback, the boxes hand-over and the lists are the caller's.
+void fill_hot_geom(HotGeom& hg, const TileGeom& tg, const IOView& ve, const IOView& v)
+{
+    memset(&hg, 0, sizeof(hg));
+    hg.vol_r = reinterpret_cast<const float*>(ve.in);
+    hg.vol_w = reinterpret_cast<float*>(const_cast<char*>(ve.in));
+    hg.img_r = reinterpret_cast<const float*>(ve.out);
+    hg.img_w = reinterpret_cast<float*>(ve.out);
+    hg.q = tg.q_global;
+    hg.xt = tg.xt_global;
+    hg.spill = tg.spill;
+    hg.vol_bstride = tg.in_bstride;
+    hg.img_bstride = tg.out_bstride;
+    hg.q_bstride = tg.q_bstride;
+    for (int k = 0; k < 3; ++k) {
+        hg.in_len[k] = tg.in_len[k];
+        hg.out_len[k] = tg.out_len[k];
+        hg.off[k] = tg.off[k];
+        hg.tiles[k] = tg.tiles[k];
+        hg.period[k] = tg.period[k];
+        hg.inv_period[k] = tg.inv_period[k];
+    }
+    hg.vol_sz = tg.in_stride[0];
+    hg.vol_sy = tg.in_stride[1];
+    hg.img_sz = tg.out_stride[0];
+    hg.img_sy = tg.out_stride[1];
+    hg.strips_x = tg.strips_x;
+    hg.strip_tiles = tg.strip_tiles;
+    hg.nstrips = tg.nstrips;
+    hg.total_strips = tg.nstrips * tg.nbatch;
+    hg.ntiles = tg.ntiles;
+    hg.ncpx = tg.ncpx;                  // (wide grids: the strip's window of columns, TileGeom::q_win)
+    hg.q_strips = tg.q_strips;
+    hg.mode = tg.mode;
+    hg.has_affine = tg.has_affine;
+    hg.dbg = tg.dbg;
+    hg.io16 = v.out16;
+    hg.cval = (float)ve.cval;
+    hg.nstep = ve.nstep;
+    hg.nsteps = ve.nsteps;
+    for (int l = 0; l < ve.nstep; ++l) {
+        hg.step_len[l] = ve.step_len[l];
+        hg.vol_step[l] = ve.in_step_stride[l];
+        hg.img_step[l] = ve.out_step_stride[l];
+    }
+    for (int k = 0; k < 12; ++k)
+        hg.affine[k] = tg.affine[k];
+}
+
 template <typename T, int ORDER, bool PAIR, bool GRAD>
 hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, const DeformBatch* batch)
 {
@@ -1323,7 +1458,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
     // (hipErrorNotSupported before anything is launched: the row kernel of deform_fast.hip then takes the call --
     // at 24.7 ms for the gradient of a 256^3 volume with a 16^3 grid, where this route takes 0.x ms)
     const bool wide_opt = sizeof(T) == 8 && std::is_floating_point<T>::value && ORDER >= 1 && nb == 1 &&
-                          !ed_env("EDHIP_RECORDS") && !ed_env("EDHIP_NO_WIDE64") && wide_optional(g);
+                          !ed_env("EDHIP_NO_WIDE64") && wide_optional(g);
     const bool wide = wide_grid(g) || wide_opt;
     tg.q_win = tg.q_strip_vox = 0;
     tg.q_strips = 1;
@@ -1340,7 +1475,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
     if (wide) {
         if constexpr (!(std::is_floating_point<T>::value && ORDER >= 1))
             return hipErrorNotSupported;
-        if (nb != 1 || ed_env("EDHIP_RECORDS"))
+        if (nb != 1)
             return hipErrorNotSupported;
         wide_hot = std::is_same<T, float>::value && tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ed_env("EDHIP_NO_HOT") &&
                    !ed_env("EDHIP_WAVE");
@@ -1358,8 +1493,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
         // 16-bit output side: the level-1 kernels of deform_hot.hip (orders 1-3) in self-serve form, or nothing
         if constexpr (!(std::is_same<T, float>::value && ORDER >= 1 && ORDER <= 3))
             return hipErrorNotSupported;
-        if (nb != 1 || tg.in_stride[2] != 1 || tg.out_stride[2] != 1 || ed_env("EDHIP_NO_HOT") || ed_env("EDHIP_WAVE") ||
-            ed_env("EDHIP_RECORDS"))
+        if (nb != 1 || tg.in_stride[2] != 1 || tg.out_stride[2] != 1 || ed_env("EDHIP_NO_HOT") || ed_env("EDHIP_WAVE"))
             return hipErrorNotSupported;
     }
     // (the forward kernels prefer strips of 4: 256^3 order 3, K1 call 237.5 -> 228.7 us, sigma 10 342.8 -> 338.0, order 1
@@ -1447,8 +1581,6 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
     // (a fixed place in the stream's workspace, whatever the geometry of the call: the unused tail of the
     // control-grid head, in front of edhip_source_box's 64 result bytes)
     tg.hint = (int*)((char*)ws - 128);
-    tg.hint_host = nullptr;
-    tg.hint_seq = 0;
     tg.xt_global = (const AxTab*)((char*)ws + 2 * list_bytes);
     tg.slack = nullptr;          // (set by the route that reads it: K1 of deform_k1.hip)
     tg.slack_scale = 0.0;
@@ -1462,69 +1594,18 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
         tg.label_list = (int*)((char*)ws + 2 * list_bytes + xt_bytes + q_all);
         tg.label_cap = (int)(label_list_bytes(g) / sizeof(int)) - 32;
     }
-    // level-1 spill feedback (float32, the kernels of deform_hot.hip and deform_wave.hip): what the recent
-    // calls of this geometry on this stream reported decides between the standard and the large boxes
-    SpillHint* sh = nullptr;
-    bool large_boxes = false, huge_boxes = false;
-    // self-serve: the recent calls of this geometry left at most a handful of tiles to the spill list -- level 1
-    // then takes such tiles itself (straight from / to global memory) and the two spill launches are not made
-    bool self_serve = false, self_serve_boxes = false;
-    if constexpr (std::is_same<T, float>::value && ORDER >= 1) {
-        sh = ed_env("EDHIP_NO_SPILL_HINT") ? nullptr : spill_hint(stream);
-        if (sh) {
-            auto geometry_key = [&](bool grad) {
-                unsigned long long key = 1469598103934665603ull;
-                auto mix = [&](unsigned long long x) { key = (key ^ x) * 1099511628211ull; };
-                for (int k = 0; k < 3; ++k) {
-                    mix((unsigned long long)g.in_len[k]);
-                    mix((unsigned long long)g.out_len[k]);
-                    mix((unsigned long long)g.off[k]);
-                    mix((unsigned long long)g.ncp[k]);
-                }
-                mix((unsigned long long)ORDER | ((unsigned long long)grad << 8) | ((unsigned long long)v.mode << 16) |
-                    ((unsigned long long)g.has_affine << 24) | ((unsigned long long)nb << 32));
-                return key;
-            };
-            const unsigned long long key = geometry_key(GRAD);
-            sh->absorb();
-            // (forward, K1z: the large boxes pay from ~6 % of the tiles beyond the standard box -- 256^3, sigma 7.5: 1.2 %,
-            // 202 against 225 us; sigma 10: 8.9 %, 249 against 237 us -- profiles/r06_sigma_sweep.txt)
-            large_boxes = sh->fraction(key) > (GRAD ? 0.10f : 0.06f);
-            // (K2 counts a tile beyond the LARGE box kHintHuge times: a tenth of the tiles there -> the huge boxes)
-            huge_boxes = GRAD && sh->fraction(key) > 0.10f * (float)tile::kHintHuge;
-            // Forward: a tile gathered straight from global memory costs its workgroup ~10 us, so a handful may stay.
-            // Gradient: 64 global float atomics per voxel, ~50 us per 16-wide tile (31 such tiles of a 128^3 volume
-            // took K2 from 56 to 141 us).  A gradient call WITH the forward call's boxes takes its oversize tiles as
-            // x-halves, and what is left is what the forward call could not hold either: it serves itself when the
-            // FORWARD calls of the geometry left at most a few tiles (decided below, where the boxes are known to be
-            // there); without the boxes only where its own recent calls left nothing at all.
-            self_serve = sh->known(key) && sh->fraction(key) * (float)(ntiles * nb) <= (GRAD ? 0.5f : 64.f);
-            if (GRAD) {
-                const unsigned long long fkey = geometry_key(false);
-                self_serve_boxes = sh->known(fkey) && sh->fraction(fkey) * (float)(ntiles * nb) <= 8.f;
-            }
-#ifdef EDHIP_EXPERIMENTS
-            if (const char* ss = ed_env("EDHIP_SELF_SERVE"))
-                self_serve = self_serve_boxes = atoi(ss) != 0;
-            if (const char* lb = ed_env("EDHIP_LARGE_BOXES"))       // 0 never, 1 always, 2 forward only, 3 gradient only
-                large_boxes = atoi(lb) == 1 || (atoi(lb) == 2 && !GRAD) || (atoi(lb) == 3 && GRAD) || atoi(lb) == 4;
-            if (const char* lb = ed_env("EDHIP_LARGE_BOXES"))
-                huge_boxes = GRAD && atoi(lb) == 4;
-#endif
-            tg.hint_host = sh->dev;
-            tg.hint_seq = sh->begin_call(key, (unsigned)(ntiles * nb));
-        }
-    }
+    // level-1 spill feedback (float32, orders 1-5): standard, large or huge boxes, self-serve or the spill levels
+    SpillFeedback fb;
+    if constexpr (std::is_same<T, float>::value && ORDER >= 1)
+        fb = spill_feedback(g, v.mode, ORDER, GRAD, nb, ntiles, stream);
+    tg.hint_host = fb.hint_host;
+    tg.hint_seq = fb.hint_seq;
     // (a call without spill feedback -- integer volumes, order 0 -- must leave the counters of the float call in
     // front of it alone: its tables kernel used to reset them unreported, and a multi-input call such as
     // BASELINE cfg4 never learned that its geometry does not spill)
-    if (!sh)
+    if (!fb.hint_host)
         tg.hint = nullptr;
-    tg.keep_mode = 0;
-    tg.keep_stash = nullptr;
-    tg.keep_flags = nullptr;
-    // the per-call tables launch; the float32 benchmark route decides about the forward -> gradient
-    // hand-over first (the tables kernel keeps / checks the control-grid values for it)
+    // the per-call tables launch (the z-walk route launches its geometry kernel in its place)
     bool tables_done = false;
     auto launch_tables = [&]() {
         if (tables_done || e != hipSuccess)
@@ -1540,19 +1621,10 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
             fill_blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
             batch->zero_done = true;
         }
+        // (a raw grid is filtered inside this launch when it fits next to the plane slab; the kernel has ~1.2 KB of
+        // static LDS on top: a flat grid of 1342-1365 points would pass 64 KiB)
         GridPrefilter gp;
-        memset(&gp, 0, sizeof(gp));
-        // a raw grid is filtered inside this launch when the launch's LDS holds it next to the plane slab (the kernel
-        // has ~1.2 KB of static LDS on top: a flat grid of 1342-1365 points would pass 64 KiB); otherwise gridpf_done
-        // stays false and edhip_deform issues the one-workgroup prefilter first
-        bool own = false;
-        if (batch && batch->gridpf && nb == 1 && batch->gridpf->total <= 4096 &&
-            sizeof(double) * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)batch->gridpf->total) <= 60 * 1024) {
-            gp = *batch->gridpf;
-            gp.zero_ptr = nullptr;
-            gp.zero_bytes = 0;
-            own = true;
-        }
+        const bool own = take_grid_prefilter(batch, nb, sizeof(double) * 3 * (size_t)g.ncp[1] * (size_t)g.ncp[2], gp);
         hipLaunchKernelGGL(tile_tables_kernel, dim3((unsigned)g.out_len[0] + fill_blocks, (unsigned)nb), dim3(kBlock),
                            sizeof(double) * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)gp.total), stream, g, tg,
                            gp);
@@ -1569,38 +1641,8 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
             // 8- / 16-bit integer volumes, orders 1-5: the wave-per-tile kernel with fp64 taps; the voxels it
             // lists (value near a rounding tie, coordinate on a boundary) are redone by the exact kernel
             HotGeom hg;
-            memset(&hg, 0, sizeof(hg));
-            hg.q = tg.q_global;
-            hg.xt = tg.xt_global;
-            hg.spill = tg.spill;
-            hg.q_bstride = tg.q_bstride;
-            for (int k = 0; k < 3; ++k) {
-                hg.in_len[k] = tg.in_len[k];
-                hg.out_len[k] = tg.out_len[k];
-                hg.off[k] = tg.off[k];
-                hg.tiles[k] = tg.tiles[k];
-                hg.period[k] = tg.period[k];
-                hg.inv_period[k] = tg.inv_period[k];
-            }
-            hg.vol_sz = tg.in_stride[0];
-            hg.vol_sy = tg.in_stride[1];
-            hg.img_sz = tg.out_stride[0];
-            hg.img_sy = tg.out_stride[1];
-            hg.ntiles = tg.ntiles;
-            hg.ncpx = tg.ncpx;
-            hg.mode = tg.mode;
-            hg.has_affine = tg.has_affine;
-            hg.cval = (float)ve.cval;
+            fill_hot_geom(hg, tg, ve, v);
             hg.cvald = ve.cval;
-            hg.nstep = ve.nstep;
-            hg.nsteps = ve.nsteps;
-            for (int l = 0; l < ve.nstep; ++l) {
-                hg.step_len[l] = ve.step_len[l];
-                hg.vol_step[l] = ve.in_step_stride[l];
-                hg.img_step[l] = ve.out_step_stride[l];
-            }
-            for (int k = 0; k < 12; ++k)
-                hg.affine[k] = tg.affine[k];
             hg.tie_list = tg.label_list;
             hg.tie_cap = tg.label_cap;
             hg.strip_tiles = 4;
@@ -1652,59 +1694,16 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
         if constexpr (std::is_same<T, float>::value && ORDER >= 1) {
             // float32, unit stride along x on both sides: the benchmark kernels of deform_hot.hip
             if (tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ED_DBG(tg.dbg, 512) && !ed_env("EDHIP_NO_HOT")) {
-                memset(&hg, 0, sizeof(hg));
-                hg.vol_r = reinterpret_cast<const float*>(ve.in);
-                hg.vol_w = reinterpret_cast<float*>(const_cast<char*>(ve.in));
-                hg.img_r = reinterpret_cast<const float*>(ve.out);
-                hg.img_w = reinterpret_cast<float*>(ve.out);
-                hg.q = tg.q_global;
-                hg.xt = tg.xt_global;
-                hg.spill = tg.spill;
-                hg.vol_bstride = tg.in_bstride;
-                hg.img_bstride = tg.out_bstride;
-                hg.q_bstride = tg.q_bstride;
-                for (int k = 0; k < 3; ++k) {
-                    hg.in_len[k] = tg.in_len[k];
-                    hg.out_len[k] = tg.out_len[k];
-                    hg.off[k] = tg.off[k];
-                    hg.tiles[k] = tg.tiles[k];
-                    hg.period[k] = tg.period[k];
-                    hg.inv_period[k] = tg.inv_period[k];
-                }
-                hg.vol_sz = tg.in_stride[0];
-                hg.vol_sy = tg.in_stride[1];
-                hg.img_sz = tg.out_stride[0];
-                hg.img_sy = tg.out_stride[1];
-                hg.strips_x = tg.strips_x;
-                hg.strip_tiles = tg.strip_tiles;
-                hg.nstrips = tg.nstrips;
-                hg.total_strips = tg.nstrips * nb;
-                hg.ntiles = tg.ntiles;
-                const int hot_cols = tg.q_win ? tg.q_win : tg.ncpx;       // (wide grids: the strip's window of columns)
-                hg.ncpx = hot_cols;
-                hg.q_strips = tg.q_strips;
-                hg.mode = tg.mode;
-                hg.has_affine = tg.has_affine;
-                hg.dbg = tg.dbg;
-                hg.self_serve = (self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
-                hg.io16 = v.out16;
+                fill_hot_geom(hg, tg, ve, v);
+                hg.self_serve = (fb.self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
                 if (v.out16 || wide)
                     hg.self_serve = 1;          // (the spill levels know neither 16-bit storage nor per-strip tables)
-                hg.cval = (float)ve.cval;
-                hg.nstep = ve.nstep;
-                hg.nsteps = ve.nsteps;
-                for (int l = 0; l < ve.nstep; ++l) {
-                    hg.step_len[l] = ve.step_len[l];
-                    hg.vol_step[l] = ve.in_step_stride[l];
-                    hg.img_step[l] = ve.out_step_stride[l];
-                }
-                for (int k = 0; k < 12; ++k)
-                    hg.affine[k] = tg.affine[k];
+                hg.hint = tg.hint;              // (nullptr: a call without spill feedback)
                 size_t hlds = 0;
-                // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles); the profiling
-                // build can still run the kernel it replaced (EDHIP_K1_OLD)
-                [[maybe_unused]] const bool k1_new = !GRAD && ORDER <= 3 && tg.strip_tiles <= 8 && !ed_env("EDHIP_K1_OLD") &&
-                                                     !ed_env("EDHIP_RECORDS");
+                // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles) -- a function of the
+                // template arguments alone (the forward strips chosen above have at most 4 tiles, K1's limit; a longer one
+                // asked for with EDHIP_STRIP makes launch_k1_level1 decline, and the general kernels take the call)
+                constexpr bool kK1 = !GRAD && ORDER <= 3;
                 // round 6: strips along z on R tables (deform_k1z.hip) for every grid its geometry kernel holds in LDS
 #ifdef EDHIP_NO_K1Z          // (A/B build of the shipped library without the z-walk route: tools/abl_k1_size.sh)
                 const bool k1z = false;
@@ -1719,39 +1718,33 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                 const bool z_shape = nb == 1 && g.out_len[0] % 256 == 0 && g.out_len[1] % 256 == 0 && g.in_len[0] % 256 == 0 &&
                                      g.in_len[1] % 256 == 0;
                 const bool z_pick = ed_env("EDHIP_K1Z_ALWAYS") || (batch && batch->strong) || z_shape;
-                const bool k1z = k1_new && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
+                const bool k1z = kK1 && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
 #endif
                 ZGeom zg;
                 memset(&zg, 0, sizeof(zg));
                 GeoBuffer* zgeo = nullptr;
                 if (k1z) {
                     (void)k1z_lds_bytes(&hg.small_cap, false);
-                    hlds = k1z_lds_bytes(&hg.box_cap, large_boxes);
+                    hlds = k1z_lds_bytes(&hg.box_cap, fb.large_boxes);
                     hg.off_box = 0;
-                    hg.hint = sh ? tg.hint : nullptr;
-                    double r2 = 0.0;
-                    for (int k = 0; k < 3; ++k) {
-                        const double r = g.in_len[k] > 1 ? (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1) : 0.0;
-                        r2 += r * r;
-                    }
-                    zg.slack_scale = 0.15 * 1.125 * 4.0 * r2;
+                    zg.slack_scale = box_margin_scale(g);
                     zgeo = geo_buffer(stream);
-                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
+                    const K1zGeoLayout gl = k1z_geo_layout(g, ntiles, nb);
+                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, gl.total, &e) : nullptr;
                     if (!gb)
                         return e != hipSuccess ? e : hipErrorOutOfMemory;
                     zg.ctl = (int*)gb;                       // the lists' counters: 32 ints in the cleared head
-                    zg.zgen = gb + 4096;
-                    char* zx = gb + 4096 + 512;
-                    zg.zt = (const AxTab*)zx;
-                    zg.recs = (int*)(zx + k1z_zt_bytes(g));
-                    zg.missed = zg.recs + (size_t)ntiles * nb * 8;
-                    zg.sinfo = zg.missed + (size_t)ntiles * nb;
-                    zg.list_g = zg.sinfo + (size_t)ntiles * nb;
-                    zg.list_f = zg.list_g + (size_t)ntiles * nb * 8;
-                    zg.recs_half = zg.list_f + (size_t)ntiles * nb * 8;
-                    zg.steps = (long long*)(zx + k1z_zt_bytes(g) + (((size_t)ntiles * nb * 168 + 63) & ~(size_t)63));
-                    zg.r = (const double*)((char*)zg.steps + kK1zMaxSteps * 16);
-                    zg.r_bstride = (long long)(((k1z_r_bytes(g) + 63) & ~(size_t)63) / 8);
+                    zg.zgen = gb + gl.zgen;
+                    zg.zt = (const AxTab*)(gb + gl.zt);
+                    zg.recs = (int*)(gb + gl.recs);
+                    zg.missed = (int*)(gb + gl.missed);
+                    zg.sinfo = (int*)(gb + gl.sinfo);
+                    zg.list_g = (int*)(gb + gl.list_g);
+                    zg.list_f = (int*)(gb + gl.list_f);
+                    zg.recs_half = (int*)(gb + gl.recs_half);
+                    zg.steps = (long long*)(gb + gl.steps);
+                    zg.r = (const double*)(gb + gl.r);
+                    zg.r_bstride = (long long)(gl.r_stride / 8);
                     zg.parity = (int)(zgeo->parity & 1);
                     zg.disp_bstride = tg.disp_bstride;
                     zg.ncpz = (int)g.ncp[0];
@@ -1778,87 +1771,53 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                     if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
                         hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
 #endif
-                } else if (k1_new) {
+                } else if (kK1) {
                     int off_small = 0;
-                    (void)k1_lds_bytes(hot_cols, &hg.small_cap, &off_small, false);
-                    if (large_boxes)
-                        hlds = k1_lds_bytes(hot_cols, &hg.box_cap, &hg.off_box, true);
+                    (void)k1_lds_bytes(hg.ncpx, &hg.small_cap, &off_small, false);
+                    if (fb.large_boxes)
+                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, true);
                     if (!hlds)
-                        hlds = k1_lds_bytes(hot_cols, &hg.box_cap, &hg.off_box, false);
-                    hg.hint = sh ? tg.hint : nullptr;
-                    // margin of the sampled boxes: 15 % of the rigorous interpolation bound (see the tables kernel)
-                    double r2 = 0.0;
-                    for (int k = 0; k < 3; ++k) {
-                        const double r = g.in_len[k] > 1 ? (double)(g.ncp[k] - 1) / (double)(g.in_len[k] - 1) : 0.0;
-                        r2 += r * r;
-                    }
+                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, false);
                     tg.slack = (double*)((char*)ws + 2 * list_bytes + xt_only_bytes(g));
-                    tg.slack_scale = 0.15 * 1.125 * 4.0 * r2;
+                    tg.slack_scale = box_margin_scale(g);
                     hg.slack = tg.slack;
 #ifdef EDHIP_EXPERIMENTS
                     if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
                         hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
 #endif
                 } else {
+                    // the gradient (deform_hot.hip); forward, orders 4 / 5: only whether a box fits next to the Q rows at
+                    // all is asked here -- the one-wave kernels below size their own
                     int off_small = 0;
-                    (void)hot_lds_bytes(GRAD, hot_cols, &hg.small_cap, &off_small, 0);
-                    (void)hot_lds_bytes(GRAD, hot_cols, &hg.large_cap, &off_small, 1);
-                    if (huge_boxes)
-                        hlds = hot_lds_bytes(GRAD, hot_cols, &hg.box_cap, &hg.off_box, 2);
-                    if (!hlds && large_boxes)
-                        hlds = hot_lds_bytes(GRAD, hot_cols, &hg.box_cap, &hg.off_box, 1);
+                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.small_cap, &off_small, 0);
+                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.large_cap, &off_small, 1);
+                    if (fb.huge_boxes)
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 2);
+                    if (!hlds && fb.large_boxes)
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 1);
                     if (!hlds)
-                        hlds = hot_lds_bytes(GRAD, hot_cols, &hg.box_cap, &hg.off_box, 0);
-                    hg.hint = sh ? tg.hint : nullptr;
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 0);
                 }
                 if (v.out16 && !hlds)
                     return hipErrorNotSupported;        // (nothing has been launched yet)
                 // (a wide grid whose window leaves no room for a hot box: the general kernels below, same tables)
                 hg.lds_grp = (int)((hlds + 15) & ~(size_t)15);
-                // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes -- and, orders 1-3, its
-                // per-voxel coordinate records -- live in a buffer of their own (nothing else writes it) under
-                // a host-side key of everything they depend on.  Layout: boxes | flags | grid copy | records.
+                // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes live in a buffer of their own (nothing
+                // else writes it) under a host-side key of everything they depend on.
                 KeepKey* key = nullptr;
                 KeepKey cur;
                 memset(&cur, 0, sizeof(cur));
                 const int box_mode = batch ? batch->box_mode : 0;
-                const size_t ngrid = 3 * (size_t)g.ncp[0] * (size_t)g.ncp[1] * (size_t)g.ncp[2];
-                const size_t nvox = (size_t)g.out_len[0] * (size_t)g.out_len[1] * (size_t)g.out_len[2];
-                const size_t kb_boxes = ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255;
-                const size_t kb_flags = ((size_t)nb * sizeof(int) + 255) & ~(size_t)255;
-                const size_t kb_stash = ((size_t)nb * ngrid * sizeof(double) + 255) & ~(size_t)255;
-                // records: orders 1-3 on the 4-wave kernels (the one-wave kernels of orders 4 / 5 keep to boxes)
-                // Measured (profiles/r04_records_route.txt): with the records the gradient kernel of the benchmark
-                // step takes 290-305 us against hot_grad_kernel's 303-306, and K1 pays 15-20 us for writing them;
-                // the route stays in the tree for the profiling build (EDHIP_RECORDS=1), the shipped library keeps
-                // the boxes-only hand-over.
-                bool want_rec = ORDER <= 3 && ngrid <= 65536 && (double)nvox * nb * 16.0 <= (double)((size_t)16 << 30) &&
-                                ed_env("EDHIP_RECORDS") != nullptr;
-#ifdef EDHIP_EXPERIMENTS
-                if (ed_env("EDHIP_WAVE"))
-                    want_rec = false;
-#endif
-                // a gradient call takes the records route whenever it can: with the forward call's records
-                // when the key matches (and the tables kernel finds the grid values unchanged), with its own
-                // records-only launch otherwise
-                const bool rec_grad = GRAD && want_rec;
-                bool rec_route = false;
-                if (hlds && (box_mode || rec_grad) && !ed_env("EDHIP_NO_BOXES")) {
+                if (hlds && box_mode && !ed_env("EDHIP_NO_BOXES")) {
                     hipError_t ke = hipSuccess;
-                    const bool with_rec = want_rec && (rec_grad || box_mode == 1);
-                    char* kbuf = (char*)keep_reserve(stream, kb_boxes + kb_flags + kb_stash + (with_rec ? nvox * nb * 16 : 0),
-                                                     &key, &ke);
-                    if (kbuf) {
-                        int* kb = (int*)kbuf;
-                        int* kflags = (int*)(kbuf + kb_boxes);
-                        double* kstash = (double*)(kbuf + kb_boxes + kb_flags);
-                        float4* krec = (float4*)(kbuf + kb_boxes + kb_flags + kb_stash);
+                    int* kb = (int*)keep_reserve(stream, ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255, &key, &ke);
+                    if (kb) {
                         int n = 0;
                         cur.w[n++] = 1;                                   // valid
                         cur.w[n++] = (unsigned long long)(size_t)batch->disp_id;
                         cur.w[n++] = (unsigned long long)g.disp_dtype | ((unsigned long long)batch->raw << 8) |
                                      ((unsigned long long)ORDER << 16) | ((unsigned long long)tg.mode << 24) |
-                                     ((unsigned long long)g.has_affine << 32) | ((unsigned long long)with_rec << 40);
+                                     ((unsigned long long)g.has_affine << 32);
                         cur.w[n++] = (unsigned long long)nb;
                         cur.w[n++] = (unsigned long long)batch->disp_bstride;
                         for (int k = 0; k < 3; ++k) {
@@ -1874,33 +1833,13 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                                 memcpy(&cur.w[n++], &g.affine[k], sizeof(double));
                         if (!GRAD && box_mode == 1) {
                             hg.boxes = kb;
-                            if (with_rec) {
-                                hg.rec = krec;
-                                hg.rec_bstride = (long long)nvox;
-                                tg.keep_mode = 1;
-                                tg.keep_stash = kstash;
-                            }
                             *key = KeepKey();                  // not valid until this launch is in the stream
-                        } else if (rec_grad) {
-                            const bool match = box_mode == 2 && memcmp(key, &cur, sizeof(cur)) == 0;
-                            hg.boxes = kb;
-                            hg.rec = krec;
-                            hg.rec_bstride = (long long)nvox;
-                            hg.rec_valid = match ? kflags : nullptr;
-                            if (match) {
-                                tg.keep_mode = 2;
-                                tg.keep_stash = kstash;
-                                tg.keep_flags = kflags;
-                            } else {
-                                *key = KeepKey();              // this call's own records replace whatever was kept
-                            }
-                            rec_route = true;
                         } else if (GRAD && box_mode == 2 && ORDER >= 3 && memcmp(key, &cur, sizeof(cur)) == 0) {
                             // (orders 1 / 2: the box pass is a small part of a short tile, and the
                             // hand-over's bookkeeping costs more than it saves: 190 -> 196, 242 -> 252 us)
                             hg.boxes = kb;
                             hg.use_boxes = 1;
-                            if (self_serve_boxes && ORDER <= 3)
+                            if (fb.self_serve_boxes && ORDER <= 3)
                                 hg.self_serve = 1;
                         }
                     }
@@ -1908,147 +1847,28 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                 if (k1z && e == hipSuccess) {
                     // the geometry kernel in place of the tables kernel: R, the z table, tile records (and boxes), work lists
                     GridPrefilter gp;
-                    memset(&gp, 0, sizeof(gp));
-                    const bool own = batch && batch->gridpf && nb == 1 && batch->gridpf->total <= 4096;
-                    if (own) {
-                        gp = *batch->gridpf;
-                        gp.zero_ptr = nullptr;
-                        gp.zero_bytes = 0;
-                    }
-                    if (!tables_done && e == hipSuccess) {
-                        e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
-                        if (e == hipSuccess)
-                            ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
-                        if (own && e == hipSuccess)
-                            batch->gridpf_done = true;
-                        tables_done = true;
-                    }
-                }
-                // round 6, gradient, PROFILING BUILD ONLY: the scatter on the z-walk tables (tools/experiments/
-                // deform_k2z.hip; EDHIP_K2Z / EDHIP_K2Y / EDHIP_K2S pick the variant) for the geometries that serve
-                // themselves.  Measured against hot_grad_kernel (profiles/r06_k2_zwalk.txt): 327 / 514 / 391 against 323 us
-                // per gradient call -- not shipped; everything the shipped library launches here is tables + hot_grad_kernel
-                bool k2z = false;
-#ifdef EDHIP_EXPERIMENTS
-                if constexpr (GRAD && ORDER <= 3) {
-                    k2z = hlds && !rec_route && !wide && !v.out16 && hg.self_serve && k1z_supported(g) &&
-                          ve.nsteps <= (int64_t)kK1zMaxSteps && (ed_env("EDHIP_K2Z") || ed_env("EDHIP_K2Y") || ed_env("EDHIP_K2S")) &&
-                          !ed_env("EDHIP_WAVE") && e == hipSuccess;
-                }
-#endif
-                size_t k2lds = 0;
-                if (k2z) {
-                    zgeo = geo_buffer(stream);
-                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, k1z_geo_bytes(g, ntiles, nb), &e) : nullptr;
-                    if (!gb)
-                        return e != hipSuccess ? e : hipErrorOutOfMemory;
-                    zg.ctl = (int*)gb;
-                    zg.zgen = gb + 4096;
-                    char* zx = gb + 4096 + 512;
-                    zg.zt = (const AxTab*)zx;
-                    zg.steps = (long long*)(zx + k1z_zt_bytes(g) + (((size_t)ntiles * nb * 168 + 63) & ~(size_t)63));
-                    zg.r = (const double*)((char*)zg.steps + kK1zMaxSteps * 16);
-                    zg.r_bstride = (long long)(((k1z_r_bytes(g) + 63) & ~(size_t)63) / 8);
-                    zg.disp_bstride = tg.disp_bstride;
-                    zg.ncpz = (int)g.ncp[0];
-                    zg.order = ORDER;
-                    zg.tables_only = 1;
-                    zg.strip_tiles = 4;
-                    while (zg.strip_tiles > 1 && (int64_t)nb * tg.tiles[1] * ((tg.tiles[2] + 1) / 2) *
-                                                         ((tg.tiles[0] + zg.strip_tiles - 1) / zg.strip_tiles) < 1024)
-                        zg.strip_tiles >>= 1;
-                    zg.hint = hg.hint;
-                    zg.hint_host = tg.hint_host;
-                    zg.hint_seq = tg.hint_seq;
-                    if (batch && batch->zero_ptr && !batch->zero_done && nb == 1 && ((uintptr_t)batch->zero_ptr & 15) == 0) {
-                        zg.zero_ptr = batch->zero_ptr;
-                        zg.zero_bytes = batch->zero_bytes;
-                    }
-                    GridPrefilter gp;
-                    memset(&gp, 0, sizeof(gp));
-                    const bool own = batch && batch->gridpf && nb == 1 && batch->gridpf->total <= 4096;
-                    if (own) {
-                        gp = *batch->gridpf;
-                        gp.zero_ptr = nullptr;
-                        gp.zero_bytes = 0;
-                    }
-#ifdef EDHIP_EXPERIMENTS
-                    k2lds = k2z_lds_bytes(&hg.box_cap);
-#endif
-                    hg.small_cap = hg.box_cap;
+                    const bool own = take_grid_prefilter(batch, nb, 0, gp);
                     e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
-                    if (e == hipSuccess) {
-                        if (zg.zero_ptr)
-                            batch->zero_done = true;
-                        if (own)
-                            batch->gridpf_done = true;
-                    }
+                    if (e == hipSuccess)
+                        ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
+                    if (own && e == hipSuccess)
+                        batch->gridpf_done = true;
                     tables_done = true;
                 }
-                if (!tables_done)
-                    launch_tables();
-#ifdef EDHIP_EXPERIMENTS
-                if (k2z && e == hipSuccess) {
-                    profile_mark(false, stream);
-                    e = launch_k2z(hg, zg, ORDER, k2lds, stream);
-                    hot_done = true;
-                    served_all = true;
-                }
-#endif
-                if (rec_route && e == hipSuccess) {
-                    // gradient from records: (1) K1 in records-only form -- its workgroups leave at once for the
-                    // samples whose records the forward call made from these very grid values -- (2) the
-                    // gradient kernel that reads records and boxes
-                    HotGeom rg = hg;
-                    rg.self_serve = 0;
-                    int fcap = 0, foff = 0;
-                    const size_t flds = hot_lds_bytes(false, tg.ncpx, &fcap, &foff, false);
-                    rg.box_cap = fcap;
-                    rg.off_box = foff;
-                    rg.small_cap = fcap;
-                    rg.hint = nullptr;
-                    rg.rec_only = 1;
-                    hipError_t he = flds ? launch_hot_records(rg, ORDER, nblk, flds, stream) : hipErrorNotSupported;
-                    if (he == hipSuccess) {
-                        HotGeom gg = hg;
-                        gg.self_serve = 0;
-                        gg.rec_valid = nullptr;
-                        int gcap = 0, scap = 0;
-                        (void)hot_grad2_lds_bytes(&scap, false);
-                        const size_t glds = hot_grad2_lds_bytes(&gcap, large_boxes);
-                        gg.box_cap = gcap;
-                        gg.small_cap = scap;
-#ifdef EDHIP_EXPERIMENTS
-                        if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                            gg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
-#endif
-                        profile_mark(false, stream);
-                        he = launch_hot_grad2(gg, ORDER, nblk, glds, stream);
-                        if (he == hipSuccess)
-                            hot_done = true;
-                    }
-                    if (he != hipSuccess && he != hipErrorNotSupported)
-                        e = he;
-                    if (!hot_done) {          // (cannot happen for orders 1-3; the old route needs its own state)
-                        hg.boxes = nullptr;
-                        hg.rec = nullptr;
-                    }
-                }
-                if (!hot_done)
-                    profile_mark(false, stream);
+                launch_tables();
+                profile_mark(false, stream);
                 // Orders 4 / 5 run on the wave-per-tile kernels (deform_wave.hip: one wavefront per tile,
                 // one copy of the box, tiles that do not fit taken as two x-halves): the 4-wave kernels
                 // give up on a tile as soon as its 5- / 6-tap windows need the wide row pitch, and at
                 // these orders that is a large share of the tiles (256^3, sigma 5, whole call: order 4
                 // forward 419 -> 339 us, order 5 gradient 944 -> 886 us; profiles/r03_wave_vs_4wave.txt).
                 // Orders 1-3 stay on the 4-wave kernels, which are 10-30 % faster there.
-                bool wave_done = false;
                 int wave_mode = ORDER >= 4 ? 3 : 0;
 #ifdef EDHIP_EXPERIMENTS
                 if (const char* wm = ed_env("EDHIP_WAVE"))        // 1 forward, 2 gradient, 3 both, 0 neither
                     wave_mode = atoi(wm);
 #endif
-                if ((hlds || wide_wave) && !hot_done && (wave_mode & (GRAD ? 2 : 1))) {
+                if ((hlds || wide_wave) && (wave_mode & (GRAD ? 2 : 1))) {
                     HotGeom wg = hg;
                     wg.self_serve = 0;
                     wg.strip_tiles = 4;
@@ -2074,8 +1894,7 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                         // 256^3 sigma 10, whole call: order 4 forward 453 -> 420 us, gradient 694 -> 662;
                         // order 5 forward 1019 -> 657, gradient 1238 -> 1055 (sigma 5: +20 .. +40 us)
                         wg.small_cap = wg.box_cap;
-                        wg.hint = sh ? tg.hint : nullptr;
-                        if (large_boxes) {
+                        if (fb.large_boxes) {
                             wlds = (ORDER == 5 && !GRAD) ? 20480 : 16384;
                             wg.box_cap = (int)((wlds - 416) / 4);
                         }
@@ -2090,19 +1909,24 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                         const unsigned wblk = (unsigned)(((wstrips * nb + 7) / 8) * 8);
                         const hipError_t he = launch_wave_level1(wg, ORDER, GRAD, wblk, wlds, occ, stream);
                         if (he == hipSuccess) {
-                            hot_done = wave_done = true;
+                            hot_done = true;
                             if (!GRAD && hg.boxes && key)
                                 *key = cur;
                         } else if (he != hipErrorNotSupported || wide_wave)
                             e = he;
                     }
                 }
-                if (wide_wave && !wave_done && e == hipSuccess)
+                if (wide_wave && !hot_done && e == hipSuccess)
                     e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
-                if (hlds && !wave_done && !hot_done && e == hipSuccess) {
-                    const hipError_t he = k1z ? launch_k1z(hg, zg, ORDER, hlds, stream)
-                                          : (k1_new ? launch_k1_level1(hg, ORDER, nblk, hlds, stream)
-                                                    : launch_hot_level1(hg, ORDER, GRAD, nblk, hlds, stream));
+                if (hlds && !hot_done && e == hipSuccess) {
+                    // (forward, orders 4 / 5, when the one-wave kernels did not take the call: the general kernels below)
+                    hipError_t he = hipErrorNotSupported;
+                    if (k1z)
+                        he = launch_k1z(hg, zg, ORDER, hlds, stream);
+                    else if (kK1)
+                        he = launch_k1_level1(hg, ORDER, nblk, hlds, stream);
+                    else if (GRAD)
+                        he = launch_hot_grad_level1(hg, ORDER, nblk, hlds, stream);
                     if (he == hipSuccess) {
                         hot_done = true;
                         served_all = hg.self_serve != 0 || k1z;
@@ -2111,7 +1935,6 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                     } else if (he != hipErrorNotSupported || v.out16 || wide)
                         e = he;
                 }
-
             }
         }
         if (!tables_done) {

@@ -1,4 +1,4 @@
-// ed_zwalk.h -- what the z-walk kernels share (deform_k1z.hip: forward; deform_k2z.hip: gradient): the displacement from
+// ed_zwalk.h -- the arithmetic of the z-walk kernels (deform_k1z.hip), kept apart from their tiling: the displacement from
 // R[o_y][o_x][k_z][c] (contracted over y and x once per call by the geometry kernel) with lane-constant control planes and
 // scalar z weights, and the general coordinates of a voxel.
 #pragma once
