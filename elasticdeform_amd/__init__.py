@@ -26,6 +26,10 @@ the argmax of the order-1 deformed one-hot channels without the one-hot volumes.
 deformed frame into the source frame: the image-side counterpart of ``deform_points``.
 ``deform_grid_inverse_gradient`` / ``deform_grid_inverse_gradient_batch`` are their adjoints with respect to the image;
 a tensor that requires grad carries autograd through ``deform_grid_inverse``.
+``deform_grid_inverse_displacement_gradient`` / ``deform_grid_inverse_affine_gradient`` (and their ``_batch`` forms)
+differentiate ``deform_grid_inverse`` with respect to the control-point displacement and to affine, rotate and zoom:
+what a loss taken in the source (fixed) frame needs; ``displacement_grad=True`` / ``affine_grad=True`` carry them through
+autograd.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
@@ -38,7 +42,9 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_coordinates_gradient, deform_points_gradient,
                           deform_grid_coordinates_gradient_batch, deform_points_gradient_batch,
                           deform_grid_inverse, deform_grid_inverse_batch, deform_grid_inverse_gradient,
-                          deform_grid_inverse_gradient_batch)
+                          deform_grid_inverse_gradient_batch, deform_grid_inverse_displacement_gradient,
+                          deform_grid_inverse_displacement_gradient_batch, deform_grid_inverse_affine_gradient,
+                          deform_grid_inverse_affine_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

@@ -55,7 +55,8 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_profile_last_us', 'edhip_deform_displacement_gradient',
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
-           'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient')
+           'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient',
+           'edhip_deform_inverse_transform_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -205,6 +206,14 @@ def load():
             ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double,
             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_inverse_transform_gradient.restype = ctypes.c_int
+        L.edhip_deform_inverse_transform_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p,
+            ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -474,6 +483,24 @@ def deform_inverse_gradient(nbatch, cot_desc, cot_bstride, disp_desc, disp_bstri
           (int(nbatch), *_pairs(cot_desc, cot_bstride, disp_desc, disp_bstride), lens, off,
            *_pairs(din_desc, din_bstride), len(axis), ax, int(order), int(mode), aff, lin, int(max_iter),
            float(tol)), flags, stream)
+
+
+def deform_inverse_transform_gradient(nbatch, in_desc, in_bstride, cot_desc, cot_bstride, disp_desc, disp_bstride, in_len,
+                                      output_offset, ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride, axis, order,
+                                      mode, inverse_affine, forward_linear, max_iter, tol, flags, stream):
+    """edhip_deform_inverse_transform_gradient: the gradient of deform_inverse() with respect to the deformation --
+    `in_desc` (the deformed image, spline coefficients for order > 1) and `cot_desc` (dZ, deformed extents `in_len`),
+    float32 / float64 of one dtype; results (None = not wanted): the gradient of the PREFILTERED control grid into
+    `ddisp_desc` (the caller applies the transposed grid prefilter), of the inverse map into `dinv_desc` (float64,
+    naxis x naxis+1).  Sample 0's descriptors plus byte strides; `disp_desc` is the PREFILTERED control grid."""
+    lens, _lens = _ptr(in_len, numpy.int64)
+    ax, axis = _ptr(axis, numpy.int32)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    lin, _lin = _ptr(forward_linear, numpy.float64)
+    _call(load().edhip_deform_inverse_transform_gradient,
+          (int(nbatch), *_pairs(in_desc, in_bstride, cot_desc, cot_bstride, disp_desc, disp_bstride), lens, off,
+           *_pairs(ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride), len(axis), ax, int(order), int(mode), aff, lin,
+           int(max_iter), float(tol)), flags, stream)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):

@@ -14,6 +14,7 @@
 #include "ed_exact_coord.h"
 #include "ed_params.h"
 #include "ed_points.h"
+#include "ed_points_grad.h"
 
 namespace ed {
 
@@ -33,32 +34,6 @@ namespace {
 // change a bit of the sums): no cell can overflow, and integer addition is associative, so the sums depend neither on the
 // order in which the points arrive nor on how they are dealt to workgroups.  points_grad_clear zeroes heads and cells
 // in front of every call: nothing is carried from one call to the next.
-
-struct PointsGradArgs {
-    PointsArgs p;                             // p.pts: the positions q; p.g, p.scale: the geometry; the rest unused
-    int inverse;
-    const char* cot;                          // (npts, naxis) float32 / float64
-    int cot_f32;
-    int64_t cot_stride[2], cot_bstride;
-    const unsigned char* status;              // inverse: uint8 (npts) or nullptr
-    int64_t status_stride, status_bstride;
-    char* dpts;                               // (npts, naxis) float32 / float64, or nullptr
-    int dpts_f32;
-    int64_t dpts_stride[2], dpts_bstride;
-    char* ddisp;                              // the grid's shape, a floating dtype, or nullptr
-    int ddisp_dtype;
-    int64_t ddisp_stride[kMaxAxes + 1], ddisp_bstride;
-    char* dK;                                 // float64 (naxis, naxis + 1), or nullptr
-    int64_t dK_stride[2], dK_bstride;
-    unsigned long long* head;                 // per sample: bits of max|u|, of max|q|, the non-finite flag, the
-                                              // number of contributing points
-    unsigned long long* cells;                // per sample: naxis (naxis + 1) cells of dK, then `values` cells of dP
-    double* u;                                // per sample: (npts, naxis)
-    int values;                               // naxis prod ncp when the dP cells (and the grid) fit LDS, else 0
-    int64_t cells_per;                        // cells per sample: naxis (naxis + 1) + naxis prod ncp
-};
-
-constexpr int kGradHead = 4;                  // 64-bit words per sample in front of the cells
 
 // the exponent e of the smallest power of two >= bound (bound > 0 and finite)
 __device__ __forceinline__ int ceil_pow2_exponent(double bound)
@@ -82,28 +57,6 @@ __device__ __forceinline__ bool grad_quanta(const unsigned long long* head, int&
     eP = ceil_pow2_exponent(bP);
     eK = ceil_pow2_exponent(bK);
     return true;
-}
-
-// the control coordinate of eval_map and whether the taps around it are exact integers
-template <int N>
-__device__ __forceinline__ bool sane_position(const PointsArgs& a, const double (&q)[N])
-{
-    bool sane = true;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double cpq = (double)(a.g.ncp[k] - 1) * (q[k] + (double)a.g.off[k]) / (double)(a.g.in_len[k] - 1);
-        sane = sane && fabs(cpq) < kPointsMaxCoordinate;
-    }
-    return sane;
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-    for (int m = warpSize / 2; m > 0; m >>= 1) {
-        const double o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // heads and cells of every sample: zero (a kernel of the call's own, in stream order in front of the other three)
@@ -443,8 +396,9 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_finish(PointsGradA
     store_cast(ga.ddisp + b * ga.ddisp_bstride + off, ga.ddisp_dtype, v);
 }
 
+// prepare (unless the caller has written the u rows and the heads itself), scatter and finish
 template <int N>
-hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, hipStream_t stream)
+hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, bool prepare, hipStream_t stream)
 {
     const dim3 block(kPointsThreads);
     const int64_t npts = ga.p.npts;
@@ -452,13 +406,16 @@ hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, hi
         const int64_t want = (npts + kPointsThreads - 1) / kPointsThreads;
         const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
         const size_t grid_lds = lds ? (size_t)ga.values * sizeof(double) : 0;
-        if (lds)
-            hipLaunchKernelGGL((points_grad_prepare<N, true>), grid, block, grid_lds, stream, ga);
-        else
-            hipLaunchKernelGGL((points_grad_prepare<N, false>), grid, block, 0, stream, ga);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
+        hipError_t e = hipSuccess;
+        if (prepare) {
+            if (lds)
+                hipLaunchKernelGGL((points_grad_prepare<N, true>), grid, block, grid_lds, stream, ga);
+            else
+                hipLaunchKernelGGL((points_grad_prepare<N, false>), grid, block, 0, stream, ga);
+            e = hipGetLastError();
+            if (e != hipSuccess)
+                return e;
+        }
         if (ga.ddisp || ga.dK) {
             if (lds)
                 hipLaunchKernelGGL((points_grad_scatter<N, true>), grid, block,
@@ -478,29 +435,13 @@ hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, hi
     return hipSuccess;
 }
 
-}  // namespace
-
-size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts)
+// the call as the kernels take it; returns whether grid and cells fit LDS
+bool fill_points_grad_args(const PointsGradCall& c, PointsGradArgs& ga)
 {
-    int64_t values = g.naxis;
-    for (int k = 0; k < g.naxis; ++k)
-        values *= g.ncp[k];
-    const int64_t cells_per = values + g.naxis * (g.naxis + 1);
-    return (size_t)nbatch * (size_t)(kGradHead + cells_per + npts * g.naxis) * 8;
-}
-
-hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream)
-{
-    const GridGeom& g = c.g;
-    const int n = g.naxis;
-    if (n < 1 || n > kMaxAxes || c.nbatch > 65535)
-        return hipErrorNotSupported;
-    if (c.nbatch <= 0)
-        return hipSuccess;
-    PointsGradArgs ga;
+    const int n = c.g.naxis;
     memset(&ga, 0, sizeof(ga));
     PointsArgs& a = ga.p;
-    const int64_t values = fill_points_args(a, g, c.disp_bstride, nullptr, 0, 0.0);
+    const int64_t values = fill_points_args(a, c.g, c.disp_bstride, nullptr, 0, 0.0);
     unpack(c.pos, a.pts, a.pts_stride, a.pts_bstride);
     unpack(c.cot, ga.cot, ga.cot_stride, ga.cot_bstride);
     unpack(c.status, ga.status, ga.status_stride, ga.status_bstride);
@@ -518,27 +459,70 @@ hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t st
     ga.cells_per = values + n * (n + 1);
     const bool lds = values <= kPointsLdsValues;
     ga.values = lds ? (int)values : 0;
-    // scratch: [nbatch heads | nbatch x cells | nbatch x npts x naxis doubles]; heads and cells are cleared by every
-    // call itself, so that nothing is carried from an earlier call (a captured graph replays self-contained)
+    // scratch (ed_points_grad.h): [nbatch heads | nbatch x cells | nbatch x npts x naxis doubles]; heads and cells are
+    // cleared by every call itself, so that nothing is carried from an earlier call (a captured graph replays
+    // self-contained)
     ga.head = (unsigned long long*)c.scratch;
     ga.cells = ga.head + (size_t)c.nbatch * kGradHead;
     ga.u = (double*)(ga.cells + (size_t)c.nbatch * (size_t)ga.cells_per);
-    const int64_t words = (int64_t)c.nbatch * (kGradHead + ga.cells_per);
+    return lds;
+}
+
+bool points_grad_call_ok(const PointsGradCall& c)
+{
+    return c.g.naxis >= 1 && c.g.naxis <= kMaxAxes && c.nbatch <= 65535;
+}
+
+hipError_t launch_points_grad_kernels(const PointsGradCall& c, bool prepare, hipStream_t stream)
+{
+    PointsGradArgs ga;
+    const bool lds = fill_points_grad_args(c, ga);
+    switch (c.g.naxis) {
+    case 1: return launch_points_grad<1>(ga, c.nbatch, lds, prepare, stream);
+    case 2: return launch_points_grad<2>(ga, c.nbatch, lds, prepare, stream);
+    case 3: return launch_points_grad<3>(ga, c.nbatch, lds, prepare, stream);
+    case 4: return launch_points_grad<4>(ga, c.nbatch, lds, prepare, stream);
+    case 5: return launch_points_grad<5>(ga, c.nbatch, lds, prepare, stream);
+    case 6: return launch_points_grad<6>(ga, c.nbatch, lds, prepare, stream);
+    default: return launch_points_grad<7>(ga, c.nbatch, lds, prepare, stream);
+    }
+}
+
+}  // namespace
+
+size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts)
+{
+    return (size_t)nbatch * (size_t)(kGradHead + points_grad_cells_per(g) + npts * g.naxis) * 8;
+}
+
+hipError_t launch_points_grad_clear(const PointsGradCall& c, hipStream_t stream)
+{
+    if (!points_grad_call_ok(c))
+        return hipErrorNotSupported;
+    if (c.nbatch <= 0)
+        return hipSuccess;
+    const int64_t words = (int64_t)c.nbatch * (kGradHead + points_grad_cells_per(c.g));
     const int64_t blocks = (words + kPointsThreads - 1) / kPointsThreads;
     hipLaunchKernelGGL(points_grad_clear, dim3((unsigned)(blocks < kPointsMaxBlocks ? blocks : kPointsMaxBlocks)),
-                       dim3(kPointsThreads), 0, stream, ga.head, words);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
+                       dim3(kPointsThreads), 0, stream, (unsigned long long*)c.scratch, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_points_grad_reduce(const PointsGradCall& c, hipStream_t stream)
+{
+    if (!points_grad_call_ok(c))
+        return hipErrorNotSupported;
+    if (c.nbatch <= 0)
+        return hipSuccess;
+    return launch_points_grad_kernels(c, false, stream);
+}
+
+hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream)
+{
+    const hipError_t e = launch_points_grad_clear(c, stream);
+    if (e != hipSuccess || c.nbatch <= 0)
         return e;
-    switch (n) {
-    case 1: return launch_points_grad<1>(ga, c.nbatch, lds, stream);
-    case 2: return launch_points_grad<2>(ga, c.nbatch, lds, stream);
-    case 3: return launch_points_grad<3>(ga, c.nbatch, lds, stream);
-    case 4: return launch_points_grad<4>(ga, c.nbatch, lds, stream);
-    case 5: return launch_points_grad<5>(ga, c.nbatch, lds, stream);
-    case 6: return launch_points_grad<6>(ga, c.nbatch, lds, stream);
-    default: return launch_points_grad<7>(ga, c.nbatch, lds, stream);
-    }
+    return launch_points_grad_kernels(c, true, stream);
 }
 
 }  // namespace ed

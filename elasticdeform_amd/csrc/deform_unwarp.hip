@@ -24,7 +24,8 @@
 // arguments alone, so a sample of a batch and a repeated call give the same bits.
 //
 // The front of the kernel (staging, voxel index, Newton phase: solve_voxel) and the formation of the taps and weights
-// (form_taps) live in ed_unwarp.h: deform_unwarp_grad.hip, the adjoint, runs the same code.
+// (form_taps) and the tap sum (tap_sum) live in ed_unwarp.h: deform_unwarp_grad.hip, the adjoint in the image, and
+// deform_unwarp_tgrad.hip, the gradient with respect to the deformation, run the same code.
 #include <cstring>
 
 #include "ed_unwarp.h"
@@ -41,61 +42,6 @@ struct UnwarpView {
     int64_t valid_stride[3], valid_bstride;
     int64_t nsrc;                             // prod I_k: the work size
 };
-
-// The (order + 1)^N taps from deformed axis D on, added to t in the reference's order.  wo[k], k < D: the weight of
-// the current tap on the outer axes.  S: the element type (its conversion to double is the plain C one).
-template <typename S, int N, int D>
-__device__ __forceinline__ void tap_rows(const char* base, int order, const int64_t (&tap)[N][6],
-                                         const double (&w)[N][6], double (&wo)[N], double& t)
-{
-    // reference arithmetic (x86-64, no FMA): keep the products and sums separate
-#pragma clang fp contract(off)
-    if constexpr (D == N - 1) {
-        S val[6];
-#pragma unroll
-        for (int l = 0; l < 6; ++l)           // (taps past the order repeat tap 0: no branch around a load)
-            val[l] = *reinterpret_cast<const S*>(base + tap[D][l]);
-#pragma unroll
-        for (int l = 0; l < 6; ++l) {
-            if (l <= order) {
-                double coeff = (double)val[l];
-                if (order > 0) {
-#pragma unroll
-                    for (int k = 0; k < D; ++k)
-                        coeff *= wo[k];
-                    coeff *= w[D][l];
-                }
-                t += coeff;
-            }
-        }
-    } else {
-        // rolled: the turn's weight and offset rotate through scalars (deform_points.hip: grid_taps)
-        double w0 = w[D][0], w1 = w[D][1], w2 = w[D][2], w3 = w[D][3], w4 = w[D][4], w5 = w[D][5];
-        int64_t o0 = tap[D][0], o1 = tap[D][1], o2 = tap[D][2], o3 = tap[D][3], o4 = tap[D][4], o5 = tap[D][5];
-#pragma unroll 1
-        for (int l = 0; l <= order; ++l) {
-            wo[D] = w0;
-            tap_rows<S, N, D + 1>(base + o0, order, tap, w, wo, t);
-            const double wr = w0;
-            const int64_t orot = o0;
-            w0 = w1, w1 = w2, w2 = w3, w3 = w4, w4 = w5, w5 = wr;
-            o0 = o1, o1 = o2, o2 = o3, o3 = o4, o4 = o5, o5 = orot;
-        }
-    }
-}
-
-template <typename S, int N>
-__device__ __forceinline__ double tap_sum(const char* base, int order, const int64_t (&tap)[N][6],
-                                          const double (&w)[N][6])
-{
-    double t = 0.0;
-    double wo[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        wo[k] = 1.0;
-    tap_rows<S, N, 0>(base, order, tap, w, wo, t);
-    return t;
-}
 
 // The gather phase of source voxel o: S_Y(q) for every step, and valid.
 template <int N>

@@ -231,6 +231,12 @@ struct PointsGradCall {
 };
 size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts);
 hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream);
+// The two ends of that call for a caller whose own kernel writes the u rows and the sample heads into the scratch
+// (ed_points_grad.h has the layout): _clear zeroes heads and cells, in front of that kernel; _reduce runs the scatter
+// and the finish behind it, reading q from `pos` (no status: a row that contributes nothing is zero) and leaving
+// `ddisp` / `dK`.  `cot` and `dpts` play no part.
+hipError_t launch_points_grad_clear(const PointsGradCall& c, hipStream_t stream);
+hipError_t launch_points_grad_reduce(const PointsGradCall& c, hipStream_t stream);
 
 // Label-aware linear resampling of label maps (deform_vote.hip): per output voxel the order-1 weights are summed per
 // distinct label among the 2^naxis source voxels, the label with the largest sum is stored (ties: the smallest label).
@@ -270,6 +276,16 @@ hipError_t launch_deform_inverse(const InverseCall& c, hipStream_t stream);
 // v.out (dZ, read, extents I) times the tap weights ADDED into v.in (dY, extents O) with float atomics.  float32 /
 // float64 only, v.in_dtype == v.out_dtype; v.cval and `valid` play no part.  One launch, no scratch.
 hipError_t launch_deform_inverse_gradient(const InverseCall& c, hipStream_t stream);
+// Its gradient with respect to the deformation (deform_unwarp_tgrad.hip): the same solve and taps per source voxel,
+// v.in = the coefficients of Y (read, extents O), v.out = dZ (read, extents I), float32 / float64 of one dtype; per
+// voxel u = -J^-T dL/dq and q as fp64 rows of `scratch`, reduced by the points gradient's fixed-point kernels into
+// ddisp (the gradient of the PREFILTERED grid, the grid's shape, a floating dtype) and dK (float64 (naxis, naxis + 1));
+// one of the two may be empty.  v.cval and `valid` play no part.  Four launches (order 0: two);
+// inverse_tgrad_scratch_bytes() bytes of scratch from the caller: per sample 4 + naxis (naxis + 1) + naxis prod ncp
+// words and 2 * naxis * 8 bytes per source voxel.
+size_t inverse_tgrad_scratch_bytes(const GridGeom& g, int nbatch);
+hipError_t launch_deform_inverse_transform_gradient(const InverseCall& c, const BatchArray& ddisp, const BatchArray& dK,
+                                                    char* scratch, hipStream_t stream);
 
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;

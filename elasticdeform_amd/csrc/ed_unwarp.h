@@ -1,7 +1,9 @@
-// ed_unwarp.h -- what the kernels of deform_unwarp.hip (an image resampled back through the deformation) and of
-// deform_unwarp_grad.hip (its adjoint) share: the thread lattice with its Newton phase, and the formation of the tap
-// offsets and weights at the solved position.  Both kernels run this very code, so that the adjoint scatters to the
-// cells, and with the weights, the forward gathers from.  Notation: the head of deform_unwarp.hip.
+// ed_unwarp.h -- what the kernels of deform_unwarp.hip (an image resampled back through the deformation), of
+// deform_unwarp_grad.hip (its adjoint in the image) and of deform_unwarp_tgrad.hip (its gradient with respect to the
+// deformation) share: the thread lattice with its Newton phase, the formation of the tap offsets and weights at the
+// solved position, and the forward's tap sum.  All three run this very code, so that the adjoint scatters to the
+// cells, and with the weights, the forward gathers from, and the derivative is taken of the sum the forward forms.
+// Notation: the head of deform_unwarp.hip.
 #pragma once
 
 #include "ed_device.h"
@@ -87,7 +89,62 @@ __device__ __forceinline__ void form_taps(const GridGeom& g, const IOView& v, co
     }
 }
 
-// The front of both kernels: this sample's control grid (staged in s_grid with LDS), the source voxel o of the thread
+// The (order + 1)^N taps from deformed axis D on, added to t in the reference's order.  wo[k], k < D: the weight of
+// the current tap on the outer axes.  S: the element type (its conversion to double is the plain C one).
+template <typename S, int N, int D>
+__device__ __forceinline__ void tap_rows(const char* base, int order, const int64_t (&tap)[N][6],
+                                         const double (&w)[N][6], double (&wo)[N], double& t)
+{
+    // reference arithmetic (x86-64, no FMA): keep the products and sums separate
+#pragma clang fp contract(off)
+    if constexpr (D == N - 1) {
+        S val[6];
+#pragma unroll
+        for (int l = 0; l < 6; ++l)           // (taps past the order repeat tap 0: no branch around a load)
+            val[l] = *reinterpret_cast<const S*>(base + tap[D][l]);
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+            if (l <= order) {
+                double coeff = (double)val[l];
+                if (order > 0) {
+#pragma unroll
+                    for (int k = 0; k < D; ++k)
+                        coeff *= wo[k];
+                    coeff *= w[D][l];
+                }
+                t += coeff;
+            }
+        }
+    } else {
+        // rolled: the turn's weight and offset rotate through scalars (deform_points.hip: grid_taps)
+        double w0 = w[D][0], w1 = w[D][1], w2 = w[D][2], w3 = w[D][3], w4 = w[D][4], w5 = w[D][5];
+        int64_t o0 = tap[D][0], o1 = tap[D][1], o2 = tap[D][2], o3 = tap[D][3], o4 = tap[D][4], o5 = tap[D][5];
+#pragma unroll 1
+        for (int l = 0; l <= order; ++l) {
+            wo[D] = w0;
+            tap_rows<S, N, D + 1>(base + o0, order, tap, w, wo, t);
+            const double wr = w0;
+            const int64_t orot = o0;
+            w0 = w1, w1 = w2, w2 = w3, w3 = w4, w4 = w5, w5 = wr;
+            o0 = o1, o1 = o2, o2 = o3, o3 = o4, o4 = o5, o5 = orot;
+        }
+    }
+}
+
+template <typename S, int N>
+__device__ __forceinline__ double tap_sum(const char* base, int order, const int64_t (&tap)[N][6],
+                                          const double (&w)[N][6])
+{
+    double t = 0.0;
+    double wo[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        wo[k] = 1.0;
+    tap_rows<S, N, 0>(base, order, tap, w, wo, t);
+    return t;
+}
+
+// The front of the kernels: this sample's control grid (staged in s_grid with LDS), the source voxel o of the thread
 // (extents I, last deformed axis fastest) and the Newton phase, q with r(q) = o.  false: the thread is past the
 // lattice (it has taken part in the staging barrier) and returns.
 template <int N, bool LDS>

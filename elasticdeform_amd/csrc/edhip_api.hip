@@ -1710,4 +1710,55 @@ int edhip_deform_inverse_gradient(int nbatch, const edhip_array* cotangent0, int
     return EDHIP_OK;
 }
 
+int edhip_deform_inverse_transform_gradient(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                                            const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                            const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                            const int64_t* in_len, const int64_t* output_offset,
+                                            const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                            const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                            int naxis, const int32_t* axis, int32_t order, int32_t mode,
+                                            const double* affine, const double* forward_linear, int max_iter,
+                                            double tol, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    InverseCall c;
+    bool launch;
+    if (int st = fill_inverse_call("edhip_deform_inverse_transform_gradient", nbatch, input0, input_batch_stride,
+                                   displacement0, displacement_batch_stride, in_len, output_offset, cotangent0,
+                                   "cotangent", cotangent_batch_stride, nullptr, 0, naxis, axis, order, mode, 0.0,
+                                   affine, forward_linear, max_iter, tol, flags, true, c, &launch, err, errlen))
+        return st;
+    if (!ddisplacement0 && !dinverse_affine0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
+    if (ddisplacement0) {
+        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        const int dt = ddisplacement0->dtype;
+        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
+    }
+    if (dinverse_affine0) {
+        const int64_t map[2] = {naxis, naxis + 1};
+        if (!has_shape(dinverse_affine0, 2, map))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
+    if (!launch)
+        return EDHIP_OK;
+    // heads, cells and the per-voxel u and q rows: the stream's workspace, behind its grid head
+    StreamGuard guard(stream);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + inverse_tgrad_scratch_bytes(c.g, nbatch), &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    e = launch_deform_inverse_transform_gradient(c, batch_array(ddisplacement0, ddisplacement_batch_stride),
+                                                 batch_array(dinverse_affine0, dinverse_affine_batch_stride),
+                                                 ws + kWorkspaceGridBytes, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform inverse transform gradient launch");
+    return EDHIP_OK;
+}
+
 }  // extern "C"

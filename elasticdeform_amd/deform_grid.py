@@ -1649,12 +1649,12 @@ def _inverse_shapes(X_shape, Ys, batch):
     return shapes
 
 
-def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter,
-                  tol, return_valid, batch, gradient):
-    """The host path of deform_grid_inverse (A = Y) and of deform_grid_inverse_gradient (`gradient`: A = dZ, which has
-    the shape of X, so X_shape is not given; the result has the shape of Y), single call and batch.  Every argument
-    check runs before the device is touched; offsets, the inverse map K and the rotate / zoom centre are those of the
-    forward call on an array of shape X_shape (the same Plan)."""
+def _inverse_geometry(A, displacement, X_shape, order, mode, cval, crop, axis, affine, rotate, zoom, max_iter, tol, batch,
+                      gradient):
+    """The checks and the Plan every inverse call starts with, before the device is touched.  A: Y, or with `gradient`
+    the cotangent dZ (it has the shape of X, so X_shape is not given).  Returns (the arrays of A, the shapes of X, the
+    Plan of the forward call on arrays of those shapes, the shapes of Y that Plan gives, the leading batch extent as a
+    tuple, the deformed extents of X, whether one of them is 1)."""
     _check_iteration(max_iter, tol)
     if batch and (not _host.is_array(A) or A.ndim < 2):
         raise Exception('%s should be an array with a leading batch axis.' % ('dZ' if gradient else 'Y'))
@@ -1667,10 +1667,9 @@ def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, 
     if not gradient and y_shapes != a_shapes:
         raise ValueError("Y does not match X_shape and cropping. Expected shape of Y is %s, but %s given."
                          % (str(y_shapes), str(a_shapes)))
-    names = [_volume_dtype_name(a) for a in As]
     if gradient:
         _check_float_volumes(As)                          # cotangent and accumulator share a float32 / float64 dtype
-    elif any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in names):
+    elif any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in map(_volume_dtype_name, As)):
         raise RuntimeError('data type not supported')     # complex, 16-bit floats
     n = plan.naxis
     if n > 3:
@@ -1682,6 +1681,18 @@ def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, 
     if not degenerate and any(v < 2 for v in sampled):
         raise ValueError("deform_grid_inverse needs at least 2 elements along every deformed axis of Y, "
                          "but its deformed extents are %s." % str(sampled))
+    return As, X_shapes, plan, y_shapes, lead, deformed, degenerate
+
+
+def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter,
+                  tol, return_valid, batch, gradient):
+    """The host path of deform_grid_inverse (A = Y) and of deform_grid_inverse_gradient (`gradient`: A = dZ, which has
+    the shape of X, so X_shape is not given; the result has the shape of Y), single call and batch.  Every argument
+    check runs before the device is touched; offsets, the inverse map K and the rotate / zoom centre are those of the
+    forward call on an array of shape X_shape (the same Plan)."""
+    As, X_shapes, plan, y_shapes, lead, deformed, degenerate = _inverse_geometry(
+        A, displacement, X_shape, order, mode, cval, crop, axis, affine, rotate, zoom, max_iter, tol, batch, gradient)
+    n = plan.naxis
 
     if degenerate:
         # a deformed axis of X of length 1: the forward call maps every voxel to the constant and no position is
@@ -1729,23 +1740,28 @@ def _inverse_host(A, displacement, X_shape, order, mode, cval, crop, prefilter, 
 
 
 def _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom, max_iter, tol,
-                 return_valid, batch):
-    """Both forms of deform_grid_inverse.  With grad mode on and a floating-point tensor Y that requires grad, the call
-    goes through the autograd Function of elasticdeform_amd.torch, whose forward comes back here with grad mode off:
-    the plain path."""
+                 return_valid, batch, displacement_grad=False, affine_grad=False):
+    """Both forms of deform_grid_inverse.  With grad mode on the call goes through an autograd Function of
+    elasticdeform_amd.torch when a floating-point tensor Y requires grad, when `displacement_grad` is set and the
+    displacement tensor requires grad, or when `affine_grad` is set and a tensor affine / rotate / zoom requires grad;
+    the Function's forward comes back here with grad mode off: the plain path."""
     torch = sys.modules.get('torch')                      # (a tensor can only arrive with torch imported)
-    if torch is not None and torch.is_grad_enabled() and any(
-            torch.is_tensor(y) and y.is_floating_point() and y.requires_grad
-            for y in (Y if isinstance(Y, list) else [Y])):
-        from . import torch as _autograd
-        return _autograd._inverse_with_autograd(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine,
-                                                rotate, zoom, max_iter, tol, return_valid, batch)
+    if torch is not None and torch.is_grad_enabled():
+        def needs(v):
+            return torch.is_tensor(v) and v.is_floating_point() and v.requires_grad
+        if (any(needs(y) for y in (Y if isinstance(Y, list) else [Y])) or (displacement_grad and needs(displacement))
+                or (affine_grad and any(needs(v) for v in (affine, rotate, zoom)))):
+            from . import torch as _autograd
+            return _autograd._inverse_with_autograd(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis,
+                                                    affine, rotate, zoom, max_iter, tol, return_valid, batch,
+                                                    displacement_grad, affine_grad)
     return _inverse_host(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
                          max_iter, tol, return_valid, batch, False)
 
 
 def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
-                        axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9, return_valid=False):
+                        axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9, return_valid=False, *,
+                        displacement_grad=False, affine_grad=False):
     """
     Resample an image back through a deformation: the image-side counterpart of :func:`deform_points`.  With
     ``Y = deform_grid(X, displacement, crop=crop, axis=axis, affine=affine, rotate=rotate, zoom=zoom)`` a pull warp,
@@ -1778,23 +1794,29 @@ def deform_grid_inverse(Y, displacement, X_shape, order=3, mode='constant', cval
 
     Autograd: with grad mode on, a floating-point tensor ``Y`` that requires grad gives a ``Z`` with a ``grad_fn``; its
     backward is :func:`deform_grid_inverse_gradient`, the exact adjoint in ``Y`` (float atomics: the last bits of
-    ``Y.grad`` may differ between runs).  ``valid`` is not differentiable, and no gradient goes to ``displacement``,
-    ``affine``, ``rotate`` or ``zoom``.  In a list, each ``Y`` that requires grad gets its gradient.  Every other call
-    -- numpy arrays, integer tensors, tensors that do not require grad -- is untouched by this.
+    ``Y.grad`` may differ between runs).  ``valid`` is not differentiable.  In a list, each ``Y`` that requires grad
+    gets its gradient.  ``displacement_grad=True`` (keyword only, the switches of
+    ``elasticdeform_amd.torch.deform_grid``): a displacement tensor that requires grad gets its gradient too
+    (:func:`deform_grid_inverse_displacement_gradient`); ``affine_grad=True``: tensor ``affine`` / ``rotate`` /
+    ``zoom`` that require grad get theirs (:func:`deform_grid_inverse_affine_gradient`); one library call per float
+    input gives both, with reproducible bits.  With both switches off (the default) no gradient goes to them.  Every
+    other call -- numpy arrays, integer tensors, tensors that do not require grad -- is untouched by this.
     """
     return _inverse_run(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
-                        max_iter, tol, return_valid, False)
+                        max_iter, tol, return_valid, False, displacement_grad, affine_grad)
 
 
 def deform_grid_inverse_batch(Y, displacements, X_shape, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
                               axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9,
-                              return_valid=False):
+                              return_valid=False, *, displacement_grad=False, affine_grad=False):
     """:func:`deform_grid_inverse` over a batch with one control grid per sample (:func:`deform_grid_batch`): ``Y``
     ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample and ``axis`` counts
     the axes of one sample; everything else is shared.  One launch for the batch; sample b equals the single call on
-    sample b, bit for bit (``Z`` and ``valid``)."""
+    sample b, bit for bit (``Z`` and ``valid``).  ``displacement_grad`` / ``affine_grad`` as in
+    :func:`deform_grid_inverse`; the parameters are shared, so their gradients are summed over the samples in sample
+    order."""
     return _inverse_run(Y, displacements, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
-                        max_iter, tol, return_valid, True)
+                        max_iter, tol, return_valid, True, displacement_grad, affine_grad)
 
 
 def deform_grid_inverse_gradient(dZ, displacement, order=3, mode='constant', crop=None, prefilter=True, axis=None,
@@ -1811,8 +1833,9 @@ def deform_grid_inverse_gradient(dZ, displacement, order=3, mode='constant', cro
     ``mode='constant'`` and ``q(p)`` lies outside ``Y``.  The result is ``P^T A^T dZ``, ``P^T`` the transposed
     prefilter along the deformed axes (``order > 1`` and ``prefilter=True``): the exact adjoint, in the sense
     :func:`deform_grid_gradient` is for :func:`deform_grid`.  ``q(p)`` is solved again, exactly as the forward solves
-    it (``max_iter``, ``tol``).  ``cval`` plays no part, ``valid`` is not differentiable, and **no gradient goes to
-    the displacement or to affine / rotate / zoom** through this call.
+    it (``max_iter``, ``tol``).  ``cval`` plays no part and ``valid`` is not differentiable.  The displacement and
+    affine / rotate / zoom get their gradients from :func:`deform_grid_inverse_displacement_gradient` and
+    :func:`deform_grid_inverse_affine_gradient`.
 
     ``dZ``: a float32 or float64 array, or a list of them (per-input ``order`` / ``mode`` / ``axis`` lists as in
     :func:`deform_grid_inverse`); everything else raises ``RuntimeError('data type not supported')``.  The products
@@ -1835,3 +1858,144 @@ def deform_grid_inverse_gradient_batch(dZ, displacements, order=3, mode='constan
     sample b up to the order of the float adds."""
     return _inverse_host(dZ, displacements, None, order, mode, 0.0, crop, prefilter, axis, affine, rotate, zoom,
                          max_iter, tol, False, True, True)
+
+
+# ---- the gradient of deform_grid_inverse with respect to the deformation -----------------------------------------
+
+def _inverse_transform_gradient(Y, dZ, displacement, order, mode, crop, prefilter, axis, affine, rotate, zoom, max_iter,
+                                tol, batch, want_disp=True, want_map=False):
+    """The host path of the four deform_grid_inverse_*_gradient calls: ONE library call per input for whatever is
+    wanted.  Returns (plan, d displacement or None, dK or None): the first in the family of dZ, dK a float64 tensor
+    (naxis, naxis+1) -- (B, naxis, naxis+1) for a batch -- on the device.  dZ has the shape of X and takes the place of
+    X_shape; the Plan, the offsets and the inverse map K are the forward call's own (_inverse_geometry), and Y must
+    have the shape that call returns.  Every argument check runs before the device is touched."""
+    dZs, _, plan, y_shapes, lead, deformed, degenerate = _inverse_geometry(
+        dZ, displacement, None, order, mode, 0.0, crop, axis, affine, rotate, zoom, max_iter, tol, batch, True)
+    if batch and (not _host.is_array(Y) or Y.ndim < 2):
+        raise Exception('Y should be an array with a leading batch axis.')
+    Ys = [Y] if batch else _host.normalize_inputs(Y)
+    got = [tuple(int(v) for v in y.shape[1 if batch else 0:]) for y in Ys]
+    if len(Ys) != len(dZs) or got != y_shapes or (batch and int(Y.shape[0]) != lead[0]):
+        raise ValueError("Y does not match the shape of dZ and cropping. Expected shape of Y is %s, but %s given."
+                         % (str(y_shapes), str(got)))
+    _check_float_volumes(Ys)
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
+    n = plan.naxis
+    dk_shape = lead + (n, n + 1)
+    torch = _torch()
+    # order 0 is piecewise constant in q: such an input adds nothing
+    todo = [i for i in range(len(Ys)) if int(plan.order[i]) > 0]
+    if degenerate or not todo:
+        # (a deformed axis of X of length 1: no position is defined, nothing depends on the grid or the map)
+        dk = None
+        if want_map:
+            dk = torch.zeros(dk_shape, dtype=torch.float64, device=dZs[0].device if torch.is_tensor(dZs[0]) else 'cpu')
+        return plan, (_dgrad_zeros(displacement, dZs[0]) if want_disp else None), dk
+
+    K = plan.inverse_affine
+    M = _forward_linear(K, n)
+    device = _device_for(list(dZs) + list(Ys) + [displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        dd = _to_device(displacement, device)
+        df = _prefiltered_grid(dd, batch, device, stream)
+        nb = lead[0] if batch else 1
+        dp_sum = dk_sum = None
+        for i in todo:
+            yd, zd = _to_device(Ys[i], device), _to_device(dZs[i], device)
+            if yd.dtype != zd.dtype:                      # (the arithmetic is fp64 whatever the dtype)
+                yd, zd = yd.to(torch.float64), zd.to(torch.float64)
+            o = int(plan.order[i])
+            ax = plan.axis[i]
+            # Y is prepared as the forward prepares it: filtered along its deformed axes
+            filter_axes = ([d + 1 for d in ax] if batch else ax) if prefilter and o > 1 else []
+            yf = _filter_axes(yd, filter_axes, o, False, device, stream=stream)
+            dp = torch.empty(tuple(int(v) for v in dd.shape), dtype=torch.float64, device=device) if want_disp else None
+            dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
+            _lib.deform_inverse_transform_gradient(nb, *_sample(yf, batch), *_sample(zd, batch), *_sample(df, batch),
+                                                   deformed, plan.output_offset, *_sample(dp, batch),
+                                                   *_sample(dk, batch), ax, o, int(plan.mode[i]), K, M, int(max_iter),
+                                                   float(tol), 0, stream)
+            if dp is not None:
+                # dD = (order-3 mirror prefilter)^T dP in fp64; the inputs' results are added in input order
+                dp = _filter_axes(dp, _grid_axes(dd, batch), 3, True, device, overwrite=True, stream=stream)
+                dp_sum = dp if dp_sum is None else dp_sum + dp
+            if dk is not None:
+                dk_sum = dk if dk_sum is None else dk_sum + dk
+        out = None
+        if dp_sum is not None:
+            out = _from_device(dp_sum.to(_result_tensor_dtype(displacement)), dZs[0])
+    return plan, out, dk_sum
+
+
+def deform_grid_inverse_displacement_gradient(Y, dZ, displacement, order=3, mode='constant', crop=None, prefilter=True,
+                                              axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9):
+    """
+    Gradient of :func:`deform_grid_inverse` with respect to the control-point ``displacement``: for ``L`` with
+    ``dZ = dL / dZ`` and ``Z = deform_grid_inverse(Y, displacement, X_shape, ...)``, returns ``dL / d displacement``
+    (the order-3 prefilter of the grid included).  This is what a loss taken in the source (fixed) frame needs: a
+    registration similarity between ``deform_grid_inverse(moving, displacement, ...)`` and the fixed image, an
+    inverse-consistency term, an augmentation judged after un-warping.
+
+    ``Z[p] = S_Y(q(p))`` with ``r(q(p)) = p``.  The spatial derivative of the spline interpolant of ``Y`` at ``q``
+    (through the boundary ``mode``; ``Y`` prefiltered as the forward prefilters it) gives ``g = dL / dq`` per voxel;
+    the implicit function theorem at the solved ``q`` gives ``u = -J^-T g`` with ``J = dr / dq``, and
+    ``dL / dP[h, j] = sum_p u_h(p) beta(q(p), j)`` for the prefiltered grid ``P`` -- the sums of
+    :func:`deform_points_gradient`, with the positions and cotangents formed inside the kernel.  ``q(p)`` is solved
+    again, exactly as the forward solves it (``max_iter``, ``tol``).
+
+    ``Y`` and ``dZ``: float32 / float64 arrays or lists of them (``dZ[i]`` has the shape of ``X[i]``, channels included,
+    and takes the place of ``X_shape``; ``Y[i]`` the shape the forward call returns for the crop; per-input ``order`` /
+    ``mode`` / ``axis`` lists as in :func:`deform_grid_inverse`); everything else raises
+    ``RuntimeError('data type not supported')``.  All arithmetic is fp64.  A voxel contributes nothing where it is not
+    solved and where ``mode='constant'`` and ``q`` lies outside ``Y`` (``Z = cval`` there); where ``'nearest'`` clamps
+    an axis that axis has slope 0; ``order=0`` is piecewise constant and gives zeros, as does a deformed axis of ``X``
+    of length 1.  At order 1 the derivative at an integer ``q`` is the one-sided one of the window the forward picks;
+    orders 2 and above are continuously differentiable.
+
+    Returns an array of the displacement's shape, in its dtype when that is floating (float64 otherwise): numpy for a
+    numpy ``dZ``, otherwise a tensor on ``dZ``'s device.  The sums over the voxels are accumulated in 64-bit integer
+    fixed point: repeated calls return the same bits, and one non-finite ``dZ`` on a contributing voxel makes the
+    result NaN.  With several inputs there is one library call per input, and the results are added in fp64 in input
+    order.
+    """
+    return _inverse_transform_gradient(Y, dZ, displacement, order, mode, crop, prefilter, axis, affine, rotate, zoom,
+                                       max_iter, tol, False, True, False)[1]
+
+
+def deform_grid_inverse_displacement_gradient_batch(Y, dZ, displacements, order=3, mode='constant', crop=None,
+                                                    prefilter=True, axis=None, affine=None, rotate=None, zoom=None,
+                                                    max_iter=32, tol=1e-9):
+    """:func:`deform_grid_inverse_displacement_gradient` over a batch with one control grid per sample
+    (:func:`deform_grid_inverse_batch`): ``Y`` and ``dZ`` ``(B, ...)``, ``displacements`` ``(B, naxis, n_0, ...)``,
+    ``axis`` counts the axes of one sample; everything else is shared.  Returns ``(B, naxis, n_0, ...)``; sample b is
+    the same bits as the single call on sample b."""
+    return _inverse_transform_gradient(Y, dZ, displacements, order, mode, crop, prefilter, axis, affine, rotate, zoom,
+                                       max_iter, tol, True, True, False)[1]
+
+
+def deform_grid_inverse_affine_gradient(Y, dZ, displacement, order=3, mode='constant', crop=None, prefilter=True,
+                                        axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9):
+    """
+    Gradient of :func:`deform_grid_inverse` with respect to the affine part of the deformation: ``L`` with
+    ``dZ = dL / dZ`` differentiated with respect to ``affine``, ``rotate`` and ``zoom``.  Arguments, checks and
+    arithmetic as for :func:`deform_grid_inverse_displacement_gradient`; with ``u`` as there,
+    ``dL / dK[h, l] = sum_p u_h(p) q_l(p)`` and ``dL / dK[h, naxis] = sum_p u_h(p)`` for the inverse map ``K``.
+    Returns ``AffineGradient(affine, rotate, zoom, inverse_map)`` as :func:`deform_grid_affine_gradient` does
+    (``zoom=0`` raises ValueError): numpy (floats for rotate / zoom) for a numpy ``dZ``, otherwise float64 tensors on
+    ``dZ``'s device.  Repeated calls return the same bits.
+    """
+    plan, _, dk = _inverse_transform_gradient(Y, dZ, displacement, order, mode, crop, prefilter, axis, affine, rotate,
+                                              zoom, max_iter, tol, False, False, True)
+    return _affine_result(dk, plan, affine, rotate, zoom, isinstance(_host.normalize_inputs(dZ)[0], numpy.ndarray))
+
+
+def deform_grid_inverse_affine_gradient_batch(Y, dZ, displacements, order=3, mode='constant', crop=None, prefilter=True,
+                                              axis=None, affine=None, rotate=None, zoom=None, max_iter=32, tol=1e-9):
+    """:func:`deform_grid_inverse_affine_gradient` over a batch (:func:`deform_grid_inverse_batch`).  ``affine`` /
+    ``rotate`` / ``zoom`` are shared by the batch, so the result is the SUM over the samples: every field is each
+    sample's value (the single call on that sample, same bits) added in fp64 in sample order, b = 0, 1, ..., B-1."""
+    plan, _, dk = _inverse_transform_gradient(Y, dZ, displacements, order, mode, crop, prefilter, axis, affine, rotate,
+                                              zoom, max_iter, tol, True, False, True)
+    return _affine_result_batch(dk, plan, affine, rotate, zoom, isinstance(dZ, numpy.ndarray))

@@ -31,6 +31,10 @@ from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
 # device).  A Y that requires grad makes deform_grid_inverse itself go through DeformGridInverse below.
 from . import deform_grid_inverse, deform_grid_inverse_batch  # noqa: F401
 from . import deform_grid_inverse_gradient, deform_grid_inverse_gradient_batch  # noqa: F401
+# ... and its gradients with respect to the deformation; displacement_grad / affine_grad of deform_grid_inverse carry
+# them through DeformGridInverseExtended below
+from . import deform_grid_inverse_displacement_gradient, deform_grid_inverse_displacement_gradient_batch  # noqa: F401
+from . import deform_grid_inverse_affine_gradient, deform_grid_inverse_affine_gradient_batch  # noqa: F401
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)
@@ -461,14 +465,88 @@ class DeformGridInverse(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+class DeformGridInverseExtended(torch.autograd.Function):
+    """DeformGridInverse with a gradient for the displacement (displacement_grad=True) and / or for affine / rotate /
+    zoom (affine_grad=True, where they arrive as inputs of their own instead of inside the keywords), modelled on
+    ElasticDeformExtended: the forward keeps every Y.  Inputs: the displacement, affine, rotate, zoom, the call's other
+    keywords, the batch flag, whether Y came as a list, displacement_grad, then every Y; outputs: every Z, then every
+    valid.  backward: deform_grid_inverse_gradient(_batch) for the Y that need a gradient, and ONE call of
+    deform_grid.py _inverse_transform_gradient for the displacement's and the parameters' gradients."""
+
+    @staticmethod
+    def forward(ctx, displacement, affine, rotate, zoom, kw, batch, as_list, disp_grad, *ys):
+        ctx.params = (affine, rotate, zoom)
+        ctx.host = {k: _host_value(v) for k, v in zip(_AFFINE_ARGS, ctx.params)}
+        ctx.kw, ctx.batch, ctx.n, ctx.disp_grad = kw, batch, len(ys), disp_grad
+        ctx.save_for_backward(displacement, *ys)
+        res = _api._inverse_run([y.detach() for y in ys] if as_list else ys[0].detach(), displacement.detach(),
+                                batch=batch, **kw, **ctx.host)
+        res = res if as_list else [res]
+        zs, valids = (zip(*res) if kw['return_valid'] else (res, ()))
+        ctx.mark_non_differentiable(*valids, *[z for z in zs if not z.is_floating_point()])
+        return tuple(zs) + tuple(valids)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *douts):
+        n, kw, host = ctx.n, ctx.kw, ctx.host
+        displacement, *ys = (t.detach() for t in ctx.saved_tensors)
+        call = dict(crop=kw['crop'], prefilter=kw['prefilter'], max_iter=kw['max_iter'], tol=kw['tol'], **host)
+
+        def subset(idx):
+            return {k: _per_input_subset(kw[k], idx, n) for k in ('order', 'mode', 'axis')}
+        grads = [None] * n
+        idx = [i for i in range(n) if ctx.needs_input_grad[8 + i]]
+        if idx:
+            if ctx.batch:
+                grads[0] = deform_grid_inverse_gradient_batch(douts[0].detach(), displacement, **subset(idx), **call)
+            else:
+                for i, g in zip(idx, deform_grid_inverse_gradient([douts[i].detach() for i in idx], displacement,
+                                                                  **subset(idx), **call)):
+                    grads[i] = g
+        want_disp = ctx.disp_grad and ctx.needs_input_grad[0]
+        want_map = any(ctx.needs_input_grad[1:4])
+        ddisp = None
+        pgrads = [None, None, None]
+        idx = [i for i in range(n) if ys[i].is_floating_point()]
+        if (want_disp or want_map) and idx:
+            per = subset(idx)
+            plan, ddisp, dk = _api._inverse_transform_gradient(
+                ys[0] if ctx.batch else [ys[i] for i in idx], douts[0].detach() if ctx.batch else
+                [douts[i].detach() for i in idx], displacement, per['order'], per['mode'], kw['crop'], kw['prefilter'],
+                per['axis'], host['affine'], host['rotate'], host['zoom'], kw['max_iter'], kw['tol'], ctx.batch,
+                want_disp, want_map)
+            if ddisp is not None:
+                ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+            if dk is not None:
+                result = _api._affine_result_batch if ctx.batch else _api._affine_result
+                r = result(dk, plan, host['affine'], host['rotate'], host['zoom'], False)
+                pgrads = _param_grads(ctx.needs_input_grad[1:4], ctx.params, r[:3])
+        return (ddisp,) + tuple(pgrads) + (None, None, None, None) + tuple(grads)
+
+
 def _inverse_with_autograd(Y, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
-                           max_iter, tol, return_valid, batch):
-    """deform_grid_inverse(_batch) through DeformGridInverse (elasticdeform_amd.deform_grid._inverse_run sends a Y that
-    requires grad here); results in the plain call's form"""
+                           max_iter, tol, return_valid, batch, displacement_grad=False, affine_grad=False):
+    """deform_grid_inverse(_batch) through DeformGridInverse -- through DeformGridInverseExtended when the displacement
+    or affine / rotate / zoom get a gradient -- (elasticdeform_amd.deform_grid._inverse_run sends the calls that need a
+    gradient here); results in the plain call's form"""
+    def needs(v):
+        return torch.is_tensor(v) and v.requires_grad
     as_list = isinstance(Y, list)
     ys = Y if as_list else [Y]
     kw = dict(X_shape=X_shape, order=order, mode=mode, cval=cval, crop=crop, prefilter=prefilter, axis=axis,
-              affine=affine, rotate=rotate, zoom=zoom, max_iter=max_iter, tol=tol, return_valid=return_valid)
-    outs = DeformGridInverse.apply(displacement, kw, batch, as_list, *ys)
+              max_iter=max_iter, tol=tol, return_valid=return_valid)
+    params = (affine, rotate, zoom)
+    want_disp = bool(displacement_grad) and needs(displacement)
+    want_map = bool(affine_grad) and any(needs(v) for v in params)
+    if want_disp or want_map:
+        if not want_map:
+            params = tuple(_host_value(v) for v in params)
+        ys = [torch.as_tensor(y) for y in ys]
+        outs = DeformGridInverseExtended.apply(torch.as_tensor(displacement), *params, kw, batch, as_list, want_disp,
+                                               *ys)
+    else:
+        outs = DeformGridInverse.apply(displacement, dict(kw, affine=affine, rotate=rotate, zoom=zoom), batch, as_list,
+                                       *ys)
     res = list(zip(outs[:len(ys)], outs[len(ys):])) if return_valid else list(outs)
     return res if as_list else res[0]

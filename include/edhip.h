@@ -589,7 +589,7 @@ int edhip_deform_inverse(int nbatch,
  *   dinput0[j, step] += sum_p A[p, j] cotangent0[p, step].
  * The caller zeroes dinput0 beforehand and, for order > 1, applies the transposed prefilter along the deformed axes
  * afterwards (edhip_spline_filter_axes with transpose) -- as it prefilters Y before edhip_deform_inverse.  cval plays
- * no part; nothing flows to the control grid or to the affine map.  The solve (start, step, halvings, tol, max_iter)
+ * no part; the control grid and the affine map get theirs from edhip_deform_inverse_transform_gradient.  The solve (start, step, halvings, tol, max_iter)
  * and the taps and weights are those of edhip_deform_inverse: the same device code.
  * Arguments as for edhip_deform_inverse, except:
  *   cotangent0           dZ, read: float32 / float64 (anything else: EDHIP_ERR_DTYPE), deformed extents in_len
@@ -618,6 +618,60 @@ int edhip_deform_inverse_gradient(int nbatch,
                                   int max_iter, double tol,
                                   uint32_t flags, void* hip_stream,
                                   char* err, size_t errlen);
+
+/*
+ * The gradient of edhip_deform_inverse with respect to the deformation: the prefiltered control grid P and the inverse
+ * map K (no counterpart in the reference).  For L = sum_{p, step} cotangent0[p, step] Z[p, step] with
+ * Z = edhip_deform_inverse(Y), per source voxel p with solved q = q(p), r(q) = p:
+ *   g_h(p) = sum_step cotangent0[p, step] m'_h sum_k C[k, step] w'_h(m_h, k_h) prod_{e != h} w_e(m_e, k_e)
+ * (C = input0, the coefficients of Y with deformed extents O; m_h = the boundary map of q_h on O_h and m'_h its slope;
+ * w, w' the tap weights and their derivatives on the window edhip_deform_inverse samples: dL/dq), and by the implicit
+ * function theorem at the solved q
+ *   u(p) = -J(q)^-T g(p)                                     J = dr/dq
+ *   ddisplacement0[h, j]       = sum_p u_h(p) beta(q(p), j)  (beta: the folded cubic tap-weight products)
+ *   dinverse_affine0[h, l < n] = sum_p u_h(p) q_l(p)         dinverse_affine0[h, n] = sum_p u_h(p).
+ * ddisplacement0 is the gradient of the PREFILTERED grid: the caller applies the transposed order-3 grid prefilter
+ * (edhip_spline_filter_axes with transpose) for the gradient of the raw displacement.
+ * A voxel contributes nothing where it is not solved, where the mode is 'constant' and q lies outside Y (Z = cval
+ * there), and where J is singular.  Where 'nearest' clamps an axis that axis has slope 0.  At a window change (order 1
+ * at integer q_h; orders >= 2 are C^1) the derivative is the one-sided one of the window the forward picks.  Order 0
+ * is piecewise constant: both results are exact zeros.
+ * Arguments as for edhip_deform_inverse, except:
+ *   input0               the coefficients of Y, read: float32 / float64 (anything else: EDHIP_ERR_DTYPE), deformed
+ *                        extents O (>= 2 each: EDHIP_ERR_INVALID), any strides.
+ *   cotangent0           dZ, read: input0's dtype (EDHIP_ERR_DTYPE) and non-deformed axes, deformed extents in_len
+ *                        (EDHIP_ERR_INVALID), any strides.  Takes the place of output0.
+ *   ddisplacement0       NULL or displacement0's shape (EDHIP_ERR_INVALID), a floating dtype (EDHIP_ERR_DTYPE).
+ *   dinverse_affine0     NULL or float64 (EDHIP_ERR_DTYPE) of shape (naxis, naxis + 1) (EDHIP_ERR_INVALID).
+ *                        Both NULL: EDHIP_ERR_INVALID.
+ *   (no valid0, no cval; EDHIP_FLAG_RAW_DISPLACEMENT is refused: EDHIP_ERR_INVALID)
+ * All arithmetic is fp64 whatever the dtype (float32 is widened at the load).  The solve, the taps and the weights are
+ * those of edhip_deform_inverse: the same device code.  The sums over the voxels are those of
+ * edhip_deform_points_gradient -- 64-bit integer fixed point, one contribution resolved to 2^-61 of N max|u| -- and
+ * keep its contracts: a repeated call gives the same bits; a sample of a batch gives the bits of the single call on it;
+ * eager execution and the replay of a captured graph give the same bits; one non-finite cotangent (or coefficient) on
+ * a contributing voxel makes that sample's results NaN and no other sample's; max|u| = 0 gives exact zeros.
+ * Every shape, dtype and flag check answers before any launch.  Four launches (clear, the per-voxel kernel, scatter,
+ * finish; order 0: clear and finish).  Workspace, from the stream's cached scratch: per sample
+ * 4 + naxis (naxis + 1) + naxis prod ncp 64-bit words, plus 2 * naxis * 8 bytes per source voxel for the fp64 rows of u
+ * and q -- 48 bytes per voxel with three deformed axes, about 100 MB for 128^3.  The call enqueues on hip_stream and
+ * never synchronises; once a warm-up call has sized the workspace it can be captured into a HIP graph.
+ */
+int edhip_deform_inverse_transform_gradient(int nbatch,
+                                            const edhip_array* input0, int64_t input_batch_stride,
+                                            const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                            const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                            const int64_t* in_len,
+                                            const int64_t* output_offset,
+                                            const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                            const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                            int naxis, const int32_t* axis,
+                                            int32_t order, int32_t mode,
+                                            const double* affine,
+                                            const double* forward_linear,
+                                            int max_iter, double tol,
+                                            uint32_t flags, void* hip_stream,
+                                            char* err, size_t errlen);
 
 /*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
