@@ -99,8 +99,11 @@ __device__ __forceinline__ ZRecU zrec_load(crec_p p)
     return zrec_unpack(v);
 }
 
-// work-list counters (ZGeom::ctl): [parity][list: 0 = G, 1 = F][XCD]; entry k of XCD x's list sits at slot 8 k + x
-__host__ __device__ __forceinline__ int zctl(int parity, int list, int xcd) { return (parity * 2 + list) * 8 + xcd; }
+// work-list words (ZGeom::ctl): [parity][word][XCD]; words 0 / 1 / 2 = entries on list G's heavy part, on list F, on list
+// G's light part, word 3 = the general workgroups' cursor into list G.  Entry k of XCD x sits at slot 8 k + x of its list;
+// list G holds its heavy entries from the front and its light ones from the back (k counted down from total_strips - 1).
+enum : int { kZHeavy = 0, kZFix = 1, kZLight = 2, kZCursor = 3 };
+__host__ __device__ __forceinline__ int zctl(int parity, int word, int xcd) { return (parity * 4 + word) * 8 + xcd; }
 
 #define ED_RED6(CTRL)                                      \
     "v_min_i32_dpp %0, %0, %0 " CTRL "\n\t"                \
@@ -424,7 +427,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
     for (int tz = tid; tz < hg.tiles[0] && !ED_DBG(hg.dbg, 1 << 27); tz += kGeoBlock) {
         const int tile_id = sample * hg.ntiles + (tz * hg.tiles[1] + ty) * hg.tiles[2] + tx;
         int cls = 0;
-        bool hint0 = false, half_fit[2] = {false, false};
+        bool hint0 = false, slow0 = false, half_fit[2] = {false, false};
         // part 0: the whole tile; parts 1 / 2: its halves along z (the lane's first / second voxel), used when the whole
         // tile's box does not fit LDS
 #pragma unroll 1
@@ -488,6 +491,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
                                       (dma && zyin) ? blo[0] * hg.vol_sz + blo[1] * hg.vol_sy + blo[2] : 0, 0, 0);
             if (part == 0) {
                 hint0 = any && !(sane && pitch > 0 && nrows * pitch <= hg.small_cap);
+                slow0 = fits && !dma;
                 cls = (flags & kZUnfit) ? 3 : ((flags & kZFast) ? 1 : 2);
                 int4* dst = reinterpret_cast<int4*>(zg.recs + (size_t)tile_id * 8);
                 dst[0] = w0;
@@ -513,8 +517,9 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
         const bool split = cls == 3 && half_fit[0] && half_fit[1];
         ZSTAT(cls == 3 ? (split ? 6 : 5) : (cls == 1 ? 3 : 4), 1);
         // class of the tile for the strip summary: 1 class A, 2 general, 3 does not fit; + 4: does not fit but its halves
-        // do (taken by the general kernel half by half); + 8: beyond the standard box
-        sCls[tz] = cls | (split ? 4 : 0) | (hint0 ? 8 : 0);
+        // do (taken by the general kernel half by half); + 8: beyond the standard box; + 16 (not part of the summary): a
+        // general tile that is costly to stage -- not LDS-DMA as it stands, or taken half by half
+        sCls[tz] = cls | (split ? 4 : 0) | (hint0 ? 8 : 0) | ((cls == 2 && slow0) || split ? 16 : 0);
     }
     __syncthreads();
     ZTICK(7);
@@ -525,25 +530,34 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
     //      clears the next call's. -----------------------------------------------------------------------------------
     {
         const int zstrips = (hg.tiles[0] + zg.strip_tiles - 1) / zg.strip_tiles;
+        // List G comes in two parts, which the general workgroups take in this order (k1z_gen_body): HEAVY strips -- a
+        // tile that is costly to stage, or three and more general tiles (a column on a side face) -- and LIGHT ones (one
+        // or two general tiles: the top and bottom faces, partial tiles), so that no workgroup starts a long strip last.
+        int* sCntL = reinterpret_cast<int*>(sMax);      // [2]: the light part's count and base (the maxima were consumed above)
         if (tid < 4)
             sCnt[tid] = 0;
+        if (tid < 2)
+            sCntL[tid] = 0;
         __syncthreads();
-        int slotG = -1, slotF = -1, sidv = 0;
+        int slotG = -1, slotL = -1, slotF = -1, sidv = 0;
         if (tid < zstrips) {
-            int info = 0;
-            bool g = false, f = false;
+            int info = 0, ngen = 0;
+            bool slow = false, f = false;
             for (int k = 0; k < zg.strip_tiles && tid * zg.strip_tiles + k < hg.tiles[0]; ++k) {
                 const int c = sCls[tid * zg.strip_tiles + k];
-                info |= c << (4 * k);
-                g = g || (c & 3) == 2 || (c & 7) == 7;
+                info |= (c & 15) << (4 * k);
+                ngen += ((c & 3) == 2 || (c & 7) == 7) ? 1 : 0;
+                slow = slow || (c & 16) != 0;
                 f = f || (c & 7) == 3;
             }
             const size_t sid = (size_t)sample * zg.nstrips + ((size_t)tid * hg.tiles[1] + ty) * hg.tiles[2] + tx;
             sidv = (int)sid;
             zg.sinfo[sid] = info;
             zg.missed[sid] = f ? 2 : 0;            // (2: already on list F)
-            if (g)
+            if (ngen && (slow || ngen >= 3) && !ED_DBG(hg.dbg, 1 << 13))          // (profiling build, 1 << 13: one part, as the strips arrive)
                 slotG = atomicAdd(&sCnt[0], 1);
+            else if (ngen)
+                slotL = atomicAdd(&sCntL[0], 1);
             if (f)
                 slotF = atomicAdd(&sCnt[1], 1);
         }
@@ -553,14 +567,18 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
         // (skewed: a face of the volume -- tx = 0, or ty = 0 -- must not land on one XCD's list)
         const int xcd = (tx + ty + sample) & 7;
         if (tid == 0) {
-            sCnt[2] = sCnt[0] ? atomicAdd(&zg.ctl[zctl(zg.parity, 0, xcd)], sCnt[0]) : 0;
-            sCnt[3] = sCnt[1] ? atomicAdd(&zg.ctl[zctl(zg.parity, 1, xcd)], sCnt[1]) : 0;
+            sCnt[2] = sCnt[0] ? atomicAdd(&zg.ctl[zctl(zg.parity, kZHeavy, xcd)], sCnt[0]) : 0;
+            sCnt[3] = sCnt[1] ? atomicAdd(&zg.ctl[zctl(zg.parity, kZFix, xcd)], sCnt[1]) : 0;
+            sCntL[1] = sCntL[0] ? atomicAdd(&zg.ctl[zctl(zg.parity, kZLight, xcd)], sCntL[0]) : 0;
         }
-        if (blockIdx.x == 0 && sample == 0 && tid < 16)
+        // (the next call's counts and cursors)
+        if (blockIdx.x == 0 && sample == 0 && tid < 32)
             zg.ctl[zctl(1 - zg.parity, tid >> 3, tid & 7)] = 0;
         __syncthreads();
         if (slotG >= 0)
             zg.list_g[(size_t)(sCnt[2] + slotG) * 8 + xcd] = sidv;
+        if (slotL >= 0)
+            zg.list_g[(size_t)(zg.total_strips - 1 - (sCntL[1] + slotL)) * 8 + xcd] = sidv;
         if (slotF >= 0)
             zg.list_f[(size_t)(sCnt[3] + slotF) * 8 + xcd] = sidv;
     }
@@ -695,7 +713,16 @@ struct ZFast {
     int io16, nsteps, deal;
     int dbg;                  // profiling build: ablation bits (1 << 17 no gather, 1 << 18 no staging, 1 << 20 no stores)
     double aff[12];           // AFFINE: inverse map, the crop offset folded into column 3
+#ifdef EDHIP_EXPERIMENTS
+    unsigned long long* dbgbuf;      // EDHIP_DEBUG_PTR: clock records of the general rows' work items, from word kZDbgBase
+#endif
 };
+#ifdef EDHIP_EXPERIMENTS
+// [0] records written, [1] / [2] latest end of a class-A / of any workgroup, [3] start of workgroup 0; from word 8 a record
+// of 4 words per work item: strip id | general tiles << 32 | (a tile that is not LDS-DMA as it stands) << 40 | XCD << 48,
+// start, end, the item's index on its XCD's list (wall clock: 10 ns ticks, one clock for the chip)
+constexpr size_t kZDbgBase = (size_t)1 << 16;
+#endif
 
 template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
 __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
@@ -883,7 +910,7 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
 // whose boxes are staged element by element -- overlap with the class-A work instead of trailing it.  Same walk, same R
 // and z table, same sums as the fast kernel: the same bits.
 template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
-__device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const int vblock, const int ngen)
+__device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const int vblock)
 {
     constexpr int NT = ORDER + 1;
     constexpr int kPadX = NT & 1;
@@ -893,11 +920,24 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
     const int lane = tid & 63;
     const int wave = zuni(tid >> 6);
     const int io16 = OUT16 ? a.io16 : 0;
-    const int xcd = vblock & 7, nper = ngen >> 3;
-    const int nwork = ((cint_p)(const void*)a.ctl)[zctl(a.parity, 0, xcd)];      // (this XCD's share of list G)
-    if ((vblock >> 3) >= nwork)
+    const int xcd = vblock & 7;
+    // this XCD's share of list G: heavy entries first, then the light ones
+    const int nheavy = ((cint_p)(const void*)a.ctl)[zctl(a.parity, kZHeavy, xcd)];
+    const int nwork = nheavy + ((cint_p)(const void*)a.ctl)[zctl(a.parity, kZLight, xcd)];
+    if (ED_DBG(a.dbg, 1 << 15) || nwork == 0)         // (profiling build, 1 << 15: the general rows return at once)
         return;
     const int box_cap = a.box_cap;
+    // Items are dealt by a cursor per XCD: a workgroup takes the next entry when it is done with one, so a long strip
+    // delays nobody else and the workgroups that start first do most of the list.  The atomic for the NEXT item is
+    // issued before the work on this one, and its result is handed round through a word behind the boxes (two words,
+    // alternating: a wave may be one item ahead of the others where an item has no staged tile, hence no barrier).
+    int* cursor = a.ctl + zctl(a.parity, kZCursor, xcd);
+    volatile int* sNext = reinterpret_cast<volatile int*>(smem + 8 * (size_t)box_cap);
+    int fetched = 0, turn = 0;
+    if (tid == 0)
+        sNext[0] = atomicAdd(cursor, 1);
+    zlds_barrier();
+    int work = zuni(sNext[0]);
     const int odd_shift = (box_cap - 1) * 4;
     float* box0 = reinterpret_cast<float*>(smem);
     float* box1 = box0 + box_cap;
@@ -908,10 +948,13 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
     const int nsteps = STEPS ? a.nsteps : 1;
     const int yy = lane >> 3, xx = lane & 7;
 
-    for (int work = vblock >> 3; work < nwork; work += nper) {
+    while (work < nwork) {
+        if (tid == 0)
+            fetched = atomicAdd(cursor, 1);
         ZStrip sp;
         {
-            int sid = ((cint_p)(const void*)a.list_g)[(size_t)work * 8 + xcd];
+            const int slot = work < nheavy ? work : a.total_strips - 1 - (work - nheavy);
+            int sid = ((cint_p)(const void*)a.list_g)[(size_t)slot * 8 + xcd];
             sp.id = sid;
             sp.sample = sid / a.nstrips;
             sid -= sp.sample * a.nstrips;
@@ -927,8 +970,10 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
         crec_p rech0 = (crec_p)(const void*)a.recs_half + ((size_t)sp.sample * a.ntiles + ((size_t)sp.tz0 * a.tiles_y + sp.ty) * a.tiles_x + sp.tx) * 2;
         if (tid == 0)
             ZSTAT(7, 1);
-        if (work != (vblock >> 3))
-            zlds_barrier();                        // (the previous strip's gathers are done with the box)
+#ifdef EDHIP_EXPERIMENTS
+        const unsigned long long dbg_t0 = a.dbgbuf ? wall_clock64() : 0;
+        int dbg_kind = 0;           // general tiles | (a tile that is not LDS-DMA as it stands) << 8
+#endif
         const int oy = sp.ty * kT + yy, ox = sp.tx * kT + xx;
         const int obase = oy * a.img_sy + ox;
         const float* __restrict__ vol = a.vol + sp.sample * a.vol_bstride;
@@ -941,6 +986,49 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
             Pyx[h] = AFFINE ? fma(zn->aff[h * 4 + 2], (double)ox, fma(zn->aff[h * 4 + 1], (double)oy, zn->aff[h * 4 + 3] + zn->offd[h])) : 0.0;
         ZTaps tp;
         tp.key[0] = tp.key[1] = tp.key[2] = tp.key[3] = -1;
+        // ---- boxes that are not LDS-DMA as they stand, by rows ---------------------------------------------------
+        // Box position xi of a row holds X[mirror_i32(b0x + xi)].  Chunk q of copy c (floats 4 q .. 4 q + 3 of the row in
+        // that copy, box positions 4 q + c ...) is loaded from s' = clamp(b0x + 4 q + c, 0, W - 4): the chunks of copy 0
+        // hold, between them, every element of [lo, hi) = [clamp(b0x, 0, W - 4), min(max(b0x + pitch, 4), W)), and
+        // element m of that range sits in chunk qs = clamp(floor((m - b0x) / 4), 0, pitch / 4 - 1) at m - s'(qs).  The
+        // row form serves a box when every element its rows need lies in that range (always, when the box covers the
+        // row: arrays narrower than a box row, however often the map folds).
+        auto row_form = [&](const ZRecU& rc) {
+            const int W = zn->in_len[2];
+            const int m = mirror_i32(rc.b0x + min(lane, rc.ex - 1), W);
+            const int mlo = wave_min(m), mhi = wave_max(m);
+            return W >= 4 && mlo >= min(max(rc.b0x, 0), W - 4) && mhi < min(max(rc.b0x + rc.pitch, 4), W);
+        };
+        // The misplaced chunks of both copies, rewritten from copy 0 of their own row: 2 pitch / 4 lanes per row, a lane
+        // reads its chunk's four elements where the clamped loads left them and writes the chunk.  A wave does the rows
+        // it loaded itself, behind its own vmcnt(0) and ahead of the tile's barrier; it reads before it writes and LDS
+        // keeps a wave's accesses in order, so no chunk is read after it was rewritten, and no barrier is added.
+        bool rowf = false;
+        auto stage_fix = [&](const ZRecU& rc) {
+            const int W = zn->in_len[2], pitch = rc.pitch, by = rc.ey;
+            const int cpr = pitch >> 2, lpr = 2 * cpr, RW = 64 / lpr;
+            const int lr = (lane * (65536 / lpr + 1)) >> 16, rem = lane - lr * lpr;
+            const int c = rem >= cpr ? 1 : 0, q = rem - c * cpr;
+            const int s = rc.b0x + 4 * q + c;
+            const bool moved = (s < 0 || s + 4 > W) && lr < RW;
+            int loc[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int m = mirror_i32(rc.b0x + min(4 * q + c + j, rc.ex - 1), W);
+                const int qs = min(max((m - rc.b0x) >> 2, 0), cpr - 1);
+                loc[j] = 4 * qs + min(max(m - min(max(rc.b0x + 4 * qs, 0), W - 4), 0), 3);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            for (int zrow = wave; zrow < rc.ez; zrow += 4) {
+                for (int y0 = 0; y0 < by; y0 += RW) {
+                    if (moved && y0 + lr < by) {
+                        float* row = box0 + (zrow * by + y0 + lr) * pitch;
+                        const float4 v = make_float4(row[loc[0]], row[loc[1]], row[loc[2]], row[loc[3]]);
+                        *reinterpret_cast<float4*>(row + c * box_cap + 4 * q) = v;
+                    }
+                }
+            }
+        };
         // ---- staging: the source box of a tile into LDS, two copies, the second shifted by one element ----------
         auto stage = [&](const ZRecU& rc, const float* src) {
             const int flags = rc.flags;
@@ -964,9 +1052,31 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                         }
                     }
                 }
+            } else if ((rowf = row_form(rc))) {
+                // The box sticks out along x, or ends within a chunk of the array's end (the tiles on the x faces): rows by
+                // LDS-DMA all the same.  Every 16-byte chunk's source is clamped into ITS OWN ROW, [0, in_len[2]) -- never
+                // a byte before the row's first element or behind its last, whatever lies there --, which leaves the
+                // chunks at the row's ends misplaced; stage_fix() puts their elements, and the mirrored ones, in place.
+                const int W = zn->in_len[2];
+                const int cpr = pitch >> 2, RW = 64 / cpr;
+                const int lr = (lane * (65536 / cpr + 1)) >> 16, q = lane - lr * cpr;
+                const int s0 = min(max(rc.b0x + 4 * q, 0), W - 4), s1 = min(max(rc.b0x + 4 * q + 1, 0), W - 4);
+                for (int zrow = wave; zrow < rc.ez; zrow += 4) {
+                    const float* gp = src + (long long)mirror_i32(rc.b0z + zrow, zn->in_len[0]) * vol_sz;
+                    const int lrow0 = zrow * by;
+                    for (int y0 = 0; y0 < by; y0 += RW) {
+                        if (lr < RW && y0 + lr < by) {
+                            const float* g = gp + (long long)mirror_i32(rc.b0y + y0 + lr, zn->in_len[1]) * vol_sy;
+                            zglds16(g + s0, box0 + (lrow0 + y0) * pitch);
+                            zglds16(g + s1, box1 + (lrow0 + y0) * pitch);
+                        }
+                    }
+                }
             } else {
-                // the box sticks out along x: every box index goes through the mirror map, as the reference does with
-                // the taps of a window that sticks out (deform.c:791-813)
+                // What the row form cannot serve -- arrays of fewer than 4 elements along x, and boxes that reach so far
+                // beyond an end of the array that a mirrored element lies outside the part of the row the chunks cover
+                // (row_form) --, element by element: every box index goes through the mirror map, as the reference does
+                // with the taps of a window that sticks out (deform.c:791-813)
                 const int nrows = rc.ez * rc.ey;
                 const float inv_by = __frcp_rn((float)by);
                 const int sub = tid & 7;
@@ -1070,6 +1180,9 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
             if (it < 2 * ntile)
                 tile_coords(it >> 1, item_mask(it), rc, cur);
             while (it < 2 * ntile) {
+#ifdef EDHIP_EXPERIMENTS
+                dbg_kind = (dbg_kind + 1) | ((rc.flags & (kZStaged | kZDma)) == kZStaged ? 256 : 0);
+#endif
                 stage(rc, vol + (STEPS ? steps[0] : 0));
                 const int in = next_item(it);
                 if (in < 2 * ntile) {
@@ -1081,6 +1194,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                 for (int ss = 0; ss < nsteps; ++ss) {
                     if (STEPS && ss > 0)
                         stage(rc, vol + steps[2 * ss]);
+                    if (staged && !(rc.flags & kZDma) && rowf)
+                        stage_fix(rc);
                     if (staged)
                         zdma_barrier();
 #pragma unroll
@@ -1103,10 +1218,26 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
         if (__any(bad < 0) && lane == 0) {
             // the fix-up kernel redoes the voxels of this strip whose window is not inside the box
             if (atomicOr(a.missed + sp.id, 1) == 0) {
-                const int xcd = vblock & 7;
-                a.list_f[(size_t)atomicAdd(a.ctl + zctl(a.parity, 1, xcd), 1) * 8 + xcd] = sp.id;
+                a.list_f[(size_t)atomicAdd(a.ctl + zctl(a.parity, kZFix, xcd), 1) * 8 + xcd] = sp.id;
             }
         }
+#ifdef EDHIP_EXPERIMENTS
+        if (a.dbgbuf && tid == 0) {
+            const unsigned long long nrec = atomicAdd(a.dbgbuf + kZDbgBase, 1ull);
+            unsigned long long* rec = a.dbgbuf + kZDbgBase + 8 + 4 * (nrec < 40000 ? nrec : 40000);      // (the tool's buffer)
+            rec[0] = (unsigned long long)(unsigned)sp.id | ((unsigned long long)(dbg_kind & 255) << 32) |
+                     ((unsigned long long)(dbg_kind >> 8) << 40) | ((unsigned long long)xcd << 48);
+            rec[1] = dbg_t0;
+            rec[2] = wall_clock64();
+            rec[3] = (unsigned long long)work;
+        }
+#endif
+        // the next item; the barrier also tells that this strip's gathers are done with the box
+        turn ^= 1;
+        if (tid == 0)
+            sNext[turn] = fetched;
+        zlds_barrier();
+        work = zuni(sNext[turn]);
     }
 }
 
@@ -1123,10 +1254,23 @@ __global__ __launch_bounds__(kBlock, 4) void k1z_tile_kernel(const ZFast a, czge
     // rows every - 1, 2 every - 1, ... are general rows while they last
     const int gens_before = min((row + 1) / every, gen_rows);         // general rows among rows 0 .. row (inclusive)
     const bool is_gen = gens_before > 0 && (row + 1) % every == 0 && (row + 1) / every <= gen_rows;
+#ifdef EDHIP_EXPERIMENTS
+    if (a.dbgbuf && blockIdx.x == 0 && threadIdx.x == 0)
+        a.dbgbuf[kZDbgBase + 3] = wall_clock64();
+#endif
     if (is_gen)
-        k1z_gen_body<ORDER, AFFINE, OUT16, STEPS>(a, zn, (gens_before - 1) * 8 + xcd, ngen);
-    else
+        k1z_gen_body<ORDER, AFFINE, OUT16, STEPS>(a, zn, (gens_before - 1) * 8 + xcd);
+    else if (!ED_DBG(a.dbg, 1 << 14))                 // (profiling build, 1 << 14: the class-A rows return at once)
         k1z_fast_body<ORDER, AFFINE, OUT16, STEPS>(a, (row - gens_before) * 8 + xcd);
+#ifdef EDHIP_EXPERIMENTS
+    // EDHIP_DEBUG_PTR (tools/k1z_gen_items.py): the latest end of a class-A workgroup [1] and of any workgroup [2]
+    if (a.dbgbuf && threadIdx.x == 0) {
+        const unsigned long long now = wall_clock64();
+        if (!is_gen)
+            atomicMax(a.dbgbuf + kZDbgBase + 1, now);
+        atomicMax(a.dbgbuf + kZDbgBase + 2, now);
+    }
+#endif
 }
 
 // What the tile kernels could not serve, straight from global memory: every voxel of a tile whose box does not fit LDS,
@@ -1280,9 +1424,15 @@ template <int ORDER, bool AFFINE, bool OUT16, bool STEPS>
 hipError_t launch_k1z_kernels(const ZFast& zf, const void* znp, unsigned ngen, unsigned nfix, size_t lds, hipStream_t stream)
 {
     const unsigned nfast = k1z_grid(zf.total_strips, zf.deal);
-    // general rows interleaved with the fast rows in proportion, all of them within the first fast rows' reach
+    // general rows interleaved with the fast rows in proportion, all of them within the first fast rows' reach.
+    // (profiles/k1z_general_rows.txt: the launch ends on class-A workgroups whatever the general rows do -- the last
+    // general item ends at 60 % of the launch --, and general rows bunched at the launch's start cost it dearly:
+    // every second / fourth row until they are placed, whole forward call 205 -> 250 / 307 us in the profiling
+    // build.  So the placement stayed; what the general rows save is slot time.)
     const unsigned fast_rows = nfast >> 3, gen_rows = ngen >> 3;
     unsigned every = gen_rows ? fast_rows / gen_rows + 1 : 2;
+    if (const char* ev = ed_env("EDHIP_ZEVERY"))
+        every = (unsigned)atoi(ev);
     if (every < 2)
         every = 2;
     hipLaunchKernelGGL((k1z_tile_kernel<ORDER, AFFINE, OUT16, STEPS>), dim3(nfast + ngen), dim3(kBlock), lds, stream, zf, (czgen_p)znp,
@@ -1326,7 +1476,7 @@ size_t k1z_lds_bytes(int* box_cap, bool large)
     size_t cap = budget / 8;
     cap = ((cap - 56) / 64) * 64 + 56;        // cap = 56 (mod 64): the copies sit on disjoint banks
     *box_cap = (int)cap;
-    return 2 * 4 * cap;
+    return 2 * 4 * cap + 16;                  // (+ the general rows' hand-over words, k1z_gen_body)
 }
 
 size_t k1z_geo_lds_bytes(const GridGeom& g, const HotGeom& hg)
@@ -1399,6 +1549,9 @@ hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds,
     zf.io16 = hg.io16;
     zf.nsteps = (int)hg.nsteps;
     zf.dbg = hg.dbg;
+#ifdef EDHIP_EXPERIMENTS
+    zf.dbgbuf = hg.dbgbuf;
+#endif
     // chunks of a few rows of strips; small launches: smaller chunks, so that every XCD gets some
     zf.deal = 4 * hg.tiles[2];
     while (zf.deal > 1 && zg.total_strips < 16 * zf.deal)
@@ -1411,7 +1564,8 @@ hipError_t launch_k1z(const HotGeom& hg, const ZGeom& zg, int order, size_t lds,
         zf.aff[h * 4 + 3] = hg.affine[h * 4 + 3] + (double)hg.off[h];
     }
     const void* zn = zg.zgen;
-    // persistent grids: the general tiles' list is worked off by up to 5 workgroups per CU; the fix-up list is empty on
+    // persistent grids: the general tiles' list is worked off by up to 5 workgroups per CU, which take its entries from
+    // a cursor and leave when it is dealt (those that find nothing leave at once); the fix-up list is empty on
     // a mild field (a launch of idle workgroups: ~2 us)
     unsigned ngen = (unsigned)(zg.total_strips < 1280 ? ((zg.total_strips + 7) / 8) * 8 : 1280);
     if (const char* ng = ed_env("EDHIP_ZNGEN"))

@@ -447,9 +447,10 @@ struct ZGeom {
     long long* steps;         // [nsteps][2]: element offsets (volume, image) of every index of the step axes
     int* sinfo;               // [sample * nstrips + strip]: 3 bits per tile of the strip (class, beyond the standard box)
     // work lists of strips: G = general tiles (geometry kernel), F = tiles that do not fit (geometry kernel) or a window
-    // outside its sampled box (tile kernels).  ctl[parity] / ctl[2 + parity] = their counts for this call; the geometry
-    // kernel clears the other parity's for the next call on the stream (the head of the geometry buffer, ed::GeoBuffer,
-    // is cleared when allocated)
+    // outside its sampled box (tile kernels).  List G is kept in two parts per XCD, heavy strips from the front and light
+    // ones from the back.  ctl[parity][word][XCD] (zctl, deform_k1z.hip) = the counts of this call and the cursor the
+    // general workgroups deal list G with; the geometry kernel clears the other parity's words for the next call on the
+    // stream (the head of the geometry buffer, ed::GeoBuffer, is cleared when allocated)
     int* list_g;
     int* list_f;
     int* ctl;

@@ -12,12 +12,12 @@ d = torch.from_numpy(np.random.default_rng(22).standard_normal((3, 5, 5, 5)) * s
 for _ in range(3):
     ed.deform_grid(X, d, order=3, mode="mirror", prefilter=False)
 torch.cuda.synchronize()
-buf = torch.zeros((1 << 12, 16), dtype=torch.int64, device=dev)
+buf = torch.zeros((1 << 14, 16), dtype=torch.int64, device=dev)      # (rows from 1 << 12: the tile kernel's records, tools/k1z_gen_items.py)
 os.environ["EDHIP_DEBUG_PTR"] = "%x" % buf.data_ptr()
 ed.deform_grid(X, d, order=3, mode="mirror", prefilter=False)
 torch.cuda.synchronize()
 del os.environ["EDHIP_DEBUG_PTR"]
-b = buf.cpu().numpy().astype(np.float64)
+b = buf.cpu().numpy()[:1 << 12].astype(np.float64)
 b = b[b[:, 0] > 0]
 t0 = b[:, 0].min()
 names = ["grid -> LDS (+ prefilter)", "hint", "slack max", "axis entries, z table, sZ", "slack fold", "R", "boxes", "records", "summaries + lists"]
