@@ -447,7 +447,8 @@ __global__ __launch_bounds__(kBlock) void deform_fast_kernel(const GridGeom g, c
 }
 
 // B-spline basis weights from the fractional offset in the data's width (closed forms of
-// deform.c:160-268, last weight = 1 - sum of the others) -- same as the tile kernels use.
+// deform.c:160-268, last weight = 1 - sum of the others).  Not weights_from_frac of ed_tile.h: that one
+// writes its fused multiply-adds out and takes the cubic pieces in another form, so the two round differently.
 template <typename T, int ORDER>
 __device__ __forceinline__ void weights_from_frac2(T x, T* w)
 {
@@ -505,23 +506,6 @@ __device__ __forceinline__ void weights_from_frac2(T x, T* w)
 // ================================================================================================
 constexpr int kRows2 = 16;          // output rows per block: 4 per wave, state kept in registers
 constexpr int kBoxCap2 = 6144;      // accumulator cells
-
-template <typename T>
-struct Fixed;
-template <>
-struct Fixed<float> {
-    typedef int acc_t;
-    typedef unsigned int uacc_t;
-    static constexpr double kRange = 2147483648.0 - 1024.0;
-    __device__ static acc_t round(float x) { return __float2int_rn(x); }
-};
-template <>
-struct Fixed<double> {
-    typedef long long acc_t;
-    typedef unsigned long long uacc_t;
-    static constexpr double kRange = 4611686018427387904.0;       // 2^62
-    __device__ static acc_t round(double x) { return __double2ll_rn(x); }
-};
 
 template <typename T, int ORDER>
 __global__ __launch_bounds__(kBlock) void deform_fast2_grad_kernel(const GridGeom g, const IOView v,

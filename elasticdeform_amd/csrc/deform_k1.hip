@@ -86,71 +86,8 @@ enum : int {
     kTGen = 128,        // general tile (array faces, partial tiles): boundary map, constant / valid flags
 };
 
-#define ED_RED6(CTRL)                                      \
-    "v_min_i32_dpp %0, %0, %0 " CTRL "\n\t"                \
-    "v_min_i32_dpp %1, %1, %1 " CTRL "\n\t"                \
-    "v_min_i32_dpp %2, %2, %2 " CTRL "\n\t"                \
-    "v_max_i32_dpp %3, %3, %3 " CTRL "\n\t"                \
-    "v_max_i32_dpp %4, %4, %4 " CTRL "\n\t"                \
-    "v_max_i32_dpp %5, %5, %5 " CTRL "\n\t"
-// min of lo[3] / max of hi[3] over the wave's 64 lanes (all active), result in lane 63: six interleaved DPP
-// chains (hand-written: the compiler turns every update_dpp step into four instructions)
-__device__ __forceinline__ void wave_box63(int (&lo)[3], int (&hi)[3])
-{
-    asm volatile("s_nop 1\n\t"
-                 ED_RED6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_mirror row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 ED_RED6("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
-}
-#undef ED_RED6
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ void lds_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// workgroup barrier that orders LDS traffic only (the output stores in flight need no draining)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// barrier that also retires this wave's LDS-DMA copies
-__device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void glds16(const float* g, float* lds)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-template <bool OUT16>
-__device__ __forceinline__ void store_out(float* img, long long off, float val, int io16)
-{
-    if constexpr (OUT16)      // (cached 2-byte stores: streamed past the L2 their half sectors cost 17 us)
-        reinterpret_cast<unsigned short*>(img)[off] = (unsigned short)narrow16(val, io16);
-    else
-        __builtin_nontemporal_store(val, img + off);
-}
-
-struct K1Strip {
-    int tz, ty, tx0, ntile, sample;
-};
-// strips are dealt to the 8 XCDs in contiguous chunks (block b runs on XCD b % 8): neighbouring strips, whose
-// source boxes overlap, share an L2
-__device__ __forceinline__ bool k1_strip(const HotGeom& hg, K1Strip& sp, int b)
-{
-    const int per = (hg.total_strips + 7) >> 3;
-    int s = (b & 7) * per + (b >> 3);
-    if ((b >> 3) >= per || s >= hg.total_strips)
-        return false;
-    sp.sample = s / hg.nstrips;
-    s -= sp.sample * hg.nstrips;
-    const int sx = s % hg.strips_x;
-    s /= hg.strips_x;
-    sp.ty = s % hg.tiles[1];
-    sp.tz = s / hg.tiles[1];
-    sp.tx0 = sx * hg.strip_tiles;
-    sp.ntile = min(hg.strip_tiles, hg.tiles[2] - sp.tx0);
-    return true;
-}
-
 // ---- strip prologue: x table, Q rows, uniform parameters -> LDS; ends with a barrier -------------------------
-__device__ __forceinline__ void k1_prologue(const HotGeom& hg, const K1Strip& sp, char* smem, int tid)
+__device__ __forceinline__ void k1_prologue(const HotGeom& hg, const Strip& sp, char* smem, int tid)
 {
     {   // x table: 12 dwords per output column; the control-column indices (dwords 8..11, counted in doubles of a
         // Q row [ncpx][4]) become byte offsets of the column in the LDS layout
@@ -178,39 +115,11 @@ __device__ __forceinline__ void k1_prologue(const HotGeom& hg, const K1Strip& sp
     if (tid >= 128 && tid < 128 + 12) {
         HotParams* hp = reinterpret_cast<HotParams*>(smem + kK1Hot);
         const int k = tid - 128;
-        hp->affine[k] = hg.affine[k];
-        if (k < 3) {
-            hp->offd[k] = (double)hg.off[k];
-            hp->last[k] = (double)(hg.in_len[k] - 1);
-            hp->period[k] = hg.period[k];
-            hp->inv_period[k] = hg.inv_period[k];
+        fill_hot_params(hp, hg, k);
+        if (k < 3)
             hp->slack[k] = hg.slack[sp.sample * 4 + k];
-        }
-        if (k < 8) {
-            hp->step_len[k] = hg.step_len[k];
-            hp->in_step_stride[k] = hg.vol_step[k];
-            hp->out_step_stride[k] = hg.img_step[k];
-        }
-        if (k == 0)
-            hp->nstep = hg.nstep;
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ void k1_step_offsets(const HotParams* hp, long long ss, long long& vol_off, long long& img_off)
-{
-    vol_off = 0;
-    img_off = 0;
-    long long r = ss;
-    const int nstep = hp->nstep;
-    for (int l = 0; l < nstep; ++l) {
-        const long long len = hp->step_len[l];
-        const long long q = r / len;
-        const long long c = r - q * len;
-        vol_off += hp->in_step_stride[l] * c;
-        img_off += hp->out_step_stride[l] * c;
-        r = q;
-    }
 }
 
 // x table entry of one output column of the strip: cubic weights + LDS addresses of the lane's Q row in the four
@@ -228,68 +137,18 @@ __device__ __forceinline__ void k1_xent(const char* smem, int col, int row, XEnt
         xe.qa[l] = t.idx[l] + (kK1Q + row);
     }
 }
-// displacement of one voxel (deform.c:693-758 after the contraction over z and y): 4 control columns x 3
-// components, ds_read_b128 (components 0, 1) + ds_read_b64 (2) per column; ROFF = immediate row offset
+// displacement of one voxel of the lane's column; ROFF = immediate row offset
 template <int ROFF>
 __device__ __forceinline__ void k1_disp(const char* smem, const XEnt& xe, double (&d)[3])
 {
-    double2 q01[4];
-    double q2[4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        q01[l] = *reinterpret_cast<const double2*>(smem + xe.qa[l] + ROFF);
-        q2[l] = *reinterpret_cast<const double*>(smem + xe.qa[l] + ROFF + 16);
-    }
-    d[0] = xe.w[0] * q01[0].x;
-    d[1] = xe.w[0] * q01[0].y;
-    d[2] = xe.w[0] * q2[0];
-#pragma unroll
-    for (int l = 1; l < 4; ++l) {
-        d[0] = fma(xe.w[l], q01[l].x, d[0]);
-        d[1] = fma(xe.w[l], q01[l].y, d[1]);
-        d[2] = fma(xe.w[l], q2[l], d[2]);
-    }
-}
-
-// general coordinates of one voxel (deform.c:771-824): window start and fractions with the boundary map for the
-// axes along which the source point left the array -- coord_axis_fast / coord_axis_mapped of ed_tile.h, the
-// arithmetic every tile kernel shares.  `b[h]` = output index + crop offset (no affine) or 0 (affine: the real
-// base is in `P`).  Returns true when the voxel maps to the constant.
-template <int ORDER, bool AFFINE>
-__device__ __forceinline__ bool k1_coords(const HotGeom& hg, const HotParams* hp, const double (&d)[3], const int (&b)[3],
-                                          const double (&P)[3], int* start, float* frac, int* raw_start = nullptr)
-{
-    int ci[3];
-    bool inr[3];
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        inr[h] = coord_axis_fast<ORDER, float>(AFFINE ? P[h] + d[h] : d[h], AFFINE ? 0 : b[h], hg.in_len[h], ci[h], frac[h]);
-    if (raw_start) {         // the window start a fast tile's voxel works with: no range test, no boundary map
-#pragma unroll
-        for (int h = 0; h < 3; ++h)
-            raw_start[h] = ci[h] - ORDER / 2;
-    }
-    bool cst = false;
-    if (!(inr[0] && inr[1] && inr[2])) {
-        // one divergent region: the axes along which the source point left the array
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-            if (!inr[h])
-                cst = coord_axis_mapped<ORDER, float>(AFFINE ? P[h] + d[h] : (double)b[h] + d[h], hg.in_len[h], hg.mode,
-                                                      hp->period[h], hp->inv_period[h], ci[h], frac[h]) || cst;
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        start[h] = cst ? 0 : ci[h] - ORDER / 2;
-    return cst;
+    qrow_disp<ROFF>(smem, xe.qa, xe.w, d);
 }
 
 // ---- tile records ------------------------------------------------------------------------------------------------
 // One lane per tile: everything the tile loop needs, from the box [lo, hi] in window-start space (hi: last tap,
 // along x the padding tap of even orders included), plus the tile's side effects -- spill feedback, spill list,
 // the box for the gradient call (EDHIP_FLAG_KEEP_BOXES).
-__device__ __forceinline__ void k1_derive(const HotGeom& hg, const K1Strip& sp, TileRec* rec, int t, const int (&lo)[3],
+__device__ __forceinline__ void k1_derive(const HotGeom& hg, const Strip& sp, TileRec* rec, int t, const int (&lo)[3],
                                           const int (&hi)[3], int kpad, bool fast)
 {
     const bool any = hi[0] >= lo[0] && hi[1] >= lo[1] && hi[2] >= lo[2];
@@ -384,7 +243,7 @@ __device__ __forceinline__ float k1_gather(const float* bp, int plane, const flo
 // zero: the bits every other level gives.  Per wave, no barriers.  (Inlined on purpose: as a real call the kernel's
 // argument block is copied to scratch for it, and every pointer loaded back from there is a flat pointer.)
 template <int ORDER, bool AFFINE, bool OUT16>
-__device__ __forceinline__ void k1_fix(const HotGeom& hg, const K1Strip& sp, char* smem, bool missed, int io16)
+__device__ __forceinline__ void k1_fix(const HotGeom& hg, const Strip& sp, char* smem, bool missed, int io16)
 {
     constexpr int NT = ORDER + 1;
     constexpr int kPadX = NT & 1;
@@ -428,7 +287,8 @@ __device__ __forceinline__ void k1_fix(const HotGeom& hg, const K1Strip& sp, cha
             }
             int st[3], raw[3];
             float fr[3];
-            const bool cst = k1_coords<ORDER, AFFINE>(hg, hp, d, b, P, st, fr, raw);
+            const bool cst = tile_coords<ORDER, AFFINE, float>(hg.in_len, &hg.mode, hp->period, hp->inv_period, d, b, P, st, fr,
+                                                               raw);
             if (!whole) {
                 // A fast tile's voxels worked with the RAW window start (no range test), a general tile's with the
                 // mapped one; the loop served the voxel iff that window lay inside the box (a constant voxel of a
@@ -461,7 +321,7 @@ __device__ __forceinline__ void k1_fix(const HotGeom& hg, const K1Strip& sp, cha
             for (long long ss = 0; ss < hg.nsteps; ++ss) {
                 long long vol_off = 0, img_off = 0;
                 if (hg.nstep)
-                    k1_step_offsets(hp, ss, vol_off, img_off);
+                    hot_step_offsets(hp, ss, vol_off, img_off);
                 float val = hg.cval;
                 if (!cst) {
                     const float* src = vol + vol_off;
@@ -508,8 +368,8 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
     constexpr int ROW1 = 4 * kT * 32;      // Q row of the lane's second voxel (z + 4): an immediate
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int io16 = OUT16 ? hg.io16 : 0;
-    K1Strip sp;
-    if (!k1_strip(hg, sp, blockIdx.x))
+    Strip sp;
+    if (!strip_of_block(hg, sp, blockIdx.x))
         return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -574,7 +434,7 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
             lo[h] = (int)floor(cr - hp->slack[h]);
             hi[h] = (int)floor(cr + hp->slack[h]);
         }
-        wave_box63(lo, hi);
+        box_reduce<6>(lo, hi);
         // fast: a full tile whose every coordinate, margin included, is one coord_axis_fast accepts
         int rlo[3], rhi[3];
         bool fast = nz == kT && ny == kT && nx == kT && !ED_DBG(hg.dbg, 1 << 16);
@@ -607,7 +467,7 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
                     hi[h] = (int)0x80000000;
                 }
             }
-            wave_box63(lo, hi);
+            box_reduce<6>(lo, hi);
         }
         if (lane == 63) {
             int blo[3], bhi[3];
@@ -733,7 +593,7 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
     // coordinates (deform.c:771-824), constant and valid flags.  Either way a window that is not inside the box
     // raises the lane's flag.
     int bad = 0;
-    auto tile_coords = [&](auto gen_tag, int ti, VoxState& vs) {
+    auto coords_of_tile = [&](auto gen_tag, int ti, VoxState& vs) {
         constexpr bool GEN = decltype(gen_tag)::value;
         const int4 r0 = *reinterpret_cast<const int4*>(rec + ti);
         const int4 r1 = *(reinterpret_cast<const int4*>(rec + ti) + 1);
@@ -775,7 +635,8 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
                         P[h] = fma(hp->affine[h * 4 + 2], (double)ox, Pzy[h][i]);
                 }
                 int start[3];
-                const bool cst = k1_coords<ORDER, AFFINE>(hg, hp, d, b, P, start, vs.frac[i]);
+                const bool cst = tile_coords<ORDER, AFFINE, float>(hg.in_len, &hg.mode, hp->period, hp->inv_period, d, b, P,
+                                                                   start, vs.frac[i]);
                 const bool valid = oz0 + 4 * i < hg.out_len[0] && oy < hg.out_len[1] && ox < hg.out_len[2];
                 rz = start[0] - b0z;
                 ry = start[1] - b0y;
@@ -824,23 +685,23 @@ __global__ __launch_bounds__(kBlock, 4) void k1_fwd_kernel(const HotGeom hg)
         VoxState cur, nxt;
         int ti = next_tile(-1);
         if (ti < ntile)
-            tile_coords(gen_tag, ti, cur);
+            coords_of_tile(gen_tag, ti, cur);
         ED_TICK(GEN ? 6 : 1);
         while (ti < ntile) {
             long long vol_off = 0, img_off = 0;
             if (hg.nstep)
-                k1_step_offsets(hp, 0, vol_off, img_off);
+                hot_step_offsets(hp, 0, vol_off, img_off);
             stage(ti, vol + vol_off);
             ED_TICK(GEN ? 6 : 2);
             const int tn = next_tile(ti);
             if (tn < ntile)
-                tile_coords(gen_tag, tn, nxt);
+                coords_of_tile(gen_tag, tn, nxt);
             ED_TICK(GEN ? 6 : 3);
             const bool staged = !GEN || (uni(rec[ti].flags) & kTStaged);
             const int pitch = uni(rec[ti].pitch), plane = uni(rec[ti].plane);
             for (long long ss = 0; ss < hg.nsteps; ++ss) {
                 if (ss > 0) {
-                    k1_step_offsets(hp, ss, vol_off, img_off);
+                    hot_step_offsets(hp, ss, vol_off, img_off);
                     stage(ti, vol + vol_off);
                 }
                 if (staged)

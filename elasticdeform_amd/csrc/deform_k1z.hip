@@ -105,41 +105,6 @@ __device__ __forceinline__ ZRecU zrec_load(crec_p p)
 enum : int { kZHeavy = 0, kZFix = 1, kZLight = 2, kZCursor = 3 };
 __host__ __device__ __forceinline__ int zctl(int parity, int word, int xcd) { return (parity * 4 + word) * 8 + xcd; }
 
-#define ED_RED6(CTRL)                                      \
-    "v_min_i32_dpp %0, %0, %0 " CTRL "\n\t"                \
-    "v_min_i32_dpp %1, %1, %1 " CTRL "\n\t"                \
-    "v_min_i32_dpp %2, %2, %2 " CTRL "\n\t"                \
-    "v_max_i32_dpp %3, %3, %3 " CTRL "\n\t"                \
-    "v_max_i32_dpp %4, %4, %4 " CTRL "\n\t"                \
-    "v_max_i32_dpp %5, %5, %5 " CTRL "\n\t"
-// min of lo[3] / max of hi[3] over each ROW of 16 lanes (all 64 active): afterwards every lane holds its row's result
-__device__ __forceinline__ void zrow_box(int (&lo)[3], int (&hi)[3])
-{
-    asm volatile("s_nop 1\n\t"
-                 ED_RED6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_mirror row_mask:0xf bank_mask:0xf")
-                 : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
-}
-#undef ED_RED6
-__device__ __forceinline__ int zuni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ void zlds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void zdma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void zglds16(const float* g, float* lds)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-template <bool OUT16>
-__device__ __forceinline__ void zstore_out(float* img, long long off, float val, int io16)
-{
-    if constexpr (OUT16)
-        reinterpret_cast<unsigned short*>(img)[off] = (unsigned short)narrow16(val, io16);
-    else
-        __builtin_nontemporal_store(val, img + off);
-}
-
 // one entry of the z table / one control-axis entry (deform.c:639-647,655-690): cubic weights of the control
 // coordinate + mirror-mapped control indices
 __device__ __forceinline__ void zaxis_entry(const GridGeom& g, int a, int oi, double* w, int* idx)
@@ -166,7 +131,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = zuni(tid >> 6);
+    const int wave = uni(tid >> 6);
     const int sample = blockIdx.y;
     const int ncpz = (int)g.ncp[0], ncpy = (int)g.ncp[1], ncpx = (int)g.ncp[2];
     const int nyx = ncpy * ncpx;
@@ -378,7 +343,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
         const bool fast = nz == kT && ny == kT && nx == kT && !__any(out_of_fast);
         // every lane of a row of 16 holds the row's range = the range of one sampled z slice; the thread that derives
         // the tile's record combines the slices (whole tile, low half, high half)
-        zrow_box(lo, hi);
+        box_reduce<4>(lo, hi);
         int* dst = sBox + (tz * 8 + (lane >> 4)) * 8;
         if ((lane & 15) == 0) {
 #pragma unroll
@@ -410,7 +375,7 @@ __global__ __launch_bounds__(kGeoBlock) void k1z_geo_kernel(const GridGeom g, co
                     hi[h] = (int)0x80000000;
                 }
             }
-            zrow_box(lo, hi);
+            box_reduce<4>(lo, hi);
             if ((lane & 15) == 0) {
 #pragma unroll
                 for (int h = 0; h < 3; ++h) {
@@ -736,7 +701,7 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
         return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = zuni(tid >> 6);
+    const int wave = uni(tid >> 6);
     const int io16 = OUT16 ? a.io16 : 0;
     const int ntile = sp.ntile;
     const size_t tile_step = (size_t)a.tiles_y * a.tiles_x;      // records between tz and tz + 1
@@ -798,8 +763,8 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
                 for (int y0 = 0; y0 < rc.ey; y0 += 16) {
                     if (y0 + lr16 < rc.ey) {
                         const float* g = gp + y0 * vol_sy;
-                        zglds16(g, box0 + (lrow0 + y0) * 16);
-                        zglds16(g + 1, box1 + (lrow0 + y0) * 16);
+                        glds16(g, box0 + (lrow0 + y0) * 16);
+                        glds16(g + 1, box1 + (lrow0 + y0) * 16);
                     }
                 }
             }
@@ -814,8 +779,8 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
                 for (int y0 = 0; y0 < rc.ey; y0 += RW) {
                     if (lr < RW && y0 + lr < rc.ey) {
                         const float* g = gp + y0 * vol_sy;
-                        zglds16(g, box0 + (lrow0 + y0) * rc.pitch);
-                        zglds16(g + 1, box1 + (lrow0 + y0) * rc.pitch);
+                        glds16(g, box0 + (lrow0 + y0) * rc.pitch);
+                        glds16(g + 1, box1 + (lrow0 + y0) * rc.pitch);
                     }
                 }
             }
@@ -824,7 +789,7 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
     // coordinates of the lane's two voxels of a tile, as LDS addresses relative to the tile's box; a window that is not
     // inside the box raises the lane's flag
     int bad = 0;
-    auto tile_coords = [&](int t, const ZRecU& rc, const ZEnt (&ze)[2], ZVox& vs) {
+    auto coords_of_tile = [&](int t, const ZRecU& rc, const ZEnt (&ze)[2], ZVox& vs) {
         const int ez = rc.ez - NT, ey = rc.ey - NT, ex = rc.ex - NTX;
         const int dy = ky - rc.b0y, dx = kx - rc.b0x;
 #pragma unroll
@@ -860,7 +825,7 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
     ZRecU rc = zrec_load(rec0 + (size_t)ti * tile_step), rn = rc;
     {
         const ZEnt ze[2] = {k1z_entry(zt, (sp.tz0 + ti) * kT + wave), k1z_entry(zt, (sp.tz0 + ti) * kT + wave + 4)};
-        tile_coords(ti, rc, ze, cur);
+        coords_of_tile(ti, rc, ze, cur);
     }
     while (ti < ntile) {
         // the next tile's record and z-table entries: scalar loads issued here, ahead of the staging loop, used behind it
@@ -872,23 +837,23 @@ __device__ __forceinline__ void k1z_fast_body(const ZFast& a, const int vblock)
             stage(rc, vol + (STEPS ? steps[0] : 0));
         if (tn < ntile) {
             rn = zrec_unpack(rnv);
-            tile_coords(tn, rn, zn, nxt);
+            coords_of_tile(tn, rn, zn, nxt);
         }
         const long long ozoff = (long long)((sp.tz0 + ti) * kT + wave) * img_sz + obase;
         const int nsteps = STEPS ? a.nsteps : 1;
         for (int ss = 0; ss < nsteps; ++ss) {
             if (STEPS && ss > 0)
                 stage(rc, vol + steps[2 * ss]);
-            zdma_barrier();       // B2: retires this wave's copies (vmcnt) and everyone's
+            dma_barrier();       // B2: retires this wave's copies (vmcnt) and everyone's
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const float val = ED_DBG(a.dbg, 1 << 17) ? cur.frac[i][0] + cur.frac[i][1] + cur.frac[i][2] + __int_as_float(cur.addr[i])
                                                          : k1z_voxel<ORDER>(smem, cur.addr[i], cur.frac[i], rc.pitch, rc.plane);
                 // streaming store (a tile writes 32-byte row segments)
                 if (!ED_DBG(a.dbg, 1 << 20) || val == 123.456f)
-                    zstore_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ozoff + (long long)(4 * i) * img_sz, val, io16);
+                    store_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ozoff + (long long)(4 * i) * img_sz, val, io16);
             }
-            zlds_barrier();       // B1: every gather of this tile is done with the box
+            lds_barrier();       // B1: every gather of this tile is done with the box
         }
         cur = nxt;
         rc = rn;
@@ -918,7 +883,7 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = zuni(tid >> 6);
+    const int wave = uni(tid >> 6);
     const int io16 = OUT16 ? a.io16 : 0;
     const int xcd = vblock & 7;
     // this XCD's share of list G: heavy entries first, then the light ones
@@ -936,8 +901,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
     int fetched = 0, turn = 0;
     if (tid == 0)
         sNext[0] = atomicAdd(cursor, 1);
-    zlds_barrier();
-    int work = zuni(sNext[0]);
+    lds_barrier();
+    int work = uni(sNext[0]);
     const int odd_shift = (box_cap - 1) * 4;
     float* box0 = reinterpret_cast<float*>(smem);
     float* box1 = box0 + box_cap;
@@ -1047,8 +1012,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                     for (int y0 = 0; y0 < by; y0 += RW) {
                         if (lr < RW && y0 + lr < by) {
                             const float* g = gp + (long long)mirror_i32(rc.b0y + y0 + lr, zn->in_len[1]) * vol_sy;
-                            zglds16(g, box0 + (lrow0 + y0) * pitch);
-                            zglds16(g + 1, box1 + (lrow0 + y0) * pitch);
+                            glds16(g, box0 + (lrow0 + y0) * pitch);
+                            glds16(g + 1, box1 + (lrow0 + y0) * pitch);
                         }
                     }
                 }
@@ -1067,8 +1032,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                     for (int y0 = 0; y0 < by; y0 += RW) {
                         if (lr < RW && y0 + lr < by) {
                             const float* g = gp + (long long)mirror_i32(rc.b0y + y0 + lr, zn->in_len[1]) * vol_sy;
-                            zglds16(g + s0, box0 + (lrow0 + y0) * pitch);
-                            zglds16(g + s1, box1 + (lrow0 + y0) * pitch);
+                            glds16(g + s0, box0 + (lrow0 + y0) * pitch);
+                            glds16(g + s1, box1 + (lrow0 + y0) * pitch);
                         }
                     }
                 }
@@ -1120,7 +1085,7 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
         };
         // ---- general coordinates of the lane's two voxels of a tile, constant and valid flags -------------------
         int bad = 0;
-        auto tile_coords = [&](int t, int mask, const ZRecU& rc, ZVox& vs) {
+        auto coords_of_tile = [&](int t, int mask, const ZRecU& rc, ZVox& vs) {
             const int ez = rc.ez - NT, ey = rc.ey - NT, ex = rc.ex - NTX;
             const bool staged = (rc.flags & kZStaged) != 0;
             vs.flg = 0;
@@ -1141,7 +1106,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                         P[h] = fma(zn->aff[h * 4 + 0], (double)oz, Pyx[h]);
                 }
                 int start[3];
-                const bool cst = k1z_coords<ORDER, AFFINE>(zn, d, b, P, start, vs.frac[i]);
+                const bool cst = tile_coords<ORDER, AFFINE, float>(zn->in_len, &zn->mode, zn->period, zn->inv_period, d, b, P,
+                                                                   start, vs.frac[i]);
                 const bool valid = oz < zn->out_len[0] && oy < zn->out_len[1] && ox < zn->out_len[2];
                 const int rz = start[0] - rc.b0z, ry = start[1] - rc.b0y, rx = start[2] - rc.b0x;
                 // (a general tile without a box -- every sample maps to the constant: a voxel that does not is redone)
@@ -1178,7 +1144,7 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
             int it = next_item(-2);
             ZRecU rc = item_rec(it < 2 * ntile ? it : 0), rn = rc;
             if (it < 2 * ntile)
-                tile_coords(it >> 1, item_mask(it), rc, cur);
+                coords_of_tile(it >> 1, item_mask(it), rc, cur);
             while (it < 2 * ntile) {
 #ifdef EDHIP_EXPERIMENTS
                 dbg_kind = (dbg_kind + 1) | ((rc.flags & (kZStaged | kZDma)) == kZStaged ? 256 : 0);
@@ -1187,7 +1153,7 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                 const int in = next_item(it);
                 if (in < 2 * ntile) {
                     rn = item_rec(in);
-                    tile_coords(in >> 1, item_mask(in), rn, nxt);
+                    coords_of_tile(in >> 1, item_mask(in), rn, nxt);
                 }
                 const bool staged = (rc.flags & kZStaged) != 0;
                 const long long ozoff = (long long)((sp.tz0 + (it >> 1)) * kT + wave) * img_sz + obase;
@@ -1197,7 +1163,7 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                     if (staged && !(rc.flags & kZDma) && rowf)
                         stage_fix(rc);
                     if (staged)
-                        zdma_barrier();
+                        dma_barrier();
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         if (!(cur.flg & (4 << i)))
@@ -1205,10 +1171,10 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
                         float val = zn->cval;
                         if (cur.flg & (1 << i))
                             val = k1z_voxel<ORDER>(smem, cur.addr[i], cur.frac[i], rc.pitch, rc.plane);
-                        zstore_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ozoff + (long long)(4 * i) * img_sz, val, io16);
+                        store_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ozoff + (long long)(4 * i) * img_sz, val, io16);
                     }
                     if (staged)
-                        zlds_barrier();
+                        lds_barrier();
                 }
                 cur = nxt;
                 rc = rn;
@@ -1236,8 +1202,8 @@ __device__ __forceinline__ void k1z_gen_body(const ZFast& a, czgen_p zn, const i
         turn ^= 1;
         if (tid == 0)
             sNext[turn] = fetched;
-        zlds_barrier();
-        work = zuni(sNext[turn]);
+        lds_barrier();
+        work = uni(sNext[turn]);
     }
 }
 
@@ -1285,7 +1251,7 @@ __global__ __launch_bounds__(kBlock) void k1z_fix_kernel(const ZFast a, czgen_p 
     constexpr int kPadX = NT & 1;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = zuni(tid >> 6);
+    const int wave = uni(tid >> 6);
     const int io16 = OUT16 ? a.io16 : 0;
     const int xcd = (int)(blockIdx.x & 7), nper = (int)(gridDim.x >> 3);
     const int nwork = ((cint_p)(const void*)a.ctl)[zctl(a.parity, 1, xcd)];      // (this XCD's share of list F)
@@ -1364,7 +1330,8 @@ __global__ __launch_bounds__(kBlock) void k1z_fix_kernel(const ZFast a, czgen_p 
                     }
                     int st[3], raw[3];
                     float fr[3];
-                    const bool cst = k1z_coords<ORDER, AFFINE>(zn, d, b, P, st, fr, raw);
+                    const bool cst = tile_coords<ORDER, AFFINE, float>(zn->in_len, &zn->mode, zn->period, zn->inv_period, d, b,
+                                                                       P, st, fr, raw);
                     if (!whole) {
                         // A class-A tile's voxels worked with the RAW window start (no range test), a general tile's
                         // with the mapped one; the loop served the voxel iff that window lay inside the box (a constant
@@ -1412,7 +1379,7 @@ __global__ __launch_bounds__(kBlock) void k1z_fix_kernel(const ZFast a, czgen_p 
                             }
                             val = a0;
                         }
-                        zstore_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ooff, val, io16);
+                        store_out<OUT16>(img, (STEPS ? steps[2 * ss + 1] : 0) + ooff, val, io16);
                     }
                 }
             }

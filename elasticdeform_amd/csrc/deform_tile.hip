@@ -278,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void tile_tables_kernel(const GridGeom g, c
 // Strip prologue: the strip's 64 x-table entries and its 64 rows of Q come from the per-call
 // tables into LDS; hot uniform parameters are parked in LDS.  Ends with a barrier.
 __device__ __forceinline__ void strip_prologue(const GridGeom& g, const IOView& vstep,
-                                               const TileGeom& tg, const StripPos& sp, char* smem)
+                                               const TileGeom& tg, const Strip& sp, char* smem)
 {
     int* sred = reinterpret_cast<int*>(smem + kOffRed);
     double* sQ = reinterpret_cast<double*>(smem + kOffQ);
@@ -309,7 +309,7 @@ __device__ __forceinline__ void strip_prologue(const GridGeom& g, const IOView& 
         const int k = tid & 7;
         sred[tid] = k < 3 ? 0x7fffffff : (int)0x80000000;
     }
-    if (tid >= 128 && tid < 128 + 12) {
+    if (tid >= 128 && tid < 128 + 12) {       // (fill_hot_params of ed_tile.h, from TileGeom / IOView instead of HotGeom)
         HotParams* hp = reinterpret_cast<HotParams*>(smem + kOffHot);
         const int k = tid - 128;
         hp->affine[k] = tg.affine[k];
@@ -331,6 +331,7 @@ __device__ __forceinline__ void strip_prologue(const GridGeom& g, const IOView& 
 }
 
 // Phase A for one voxel: displacement from Q, affine, boundary map, window start, fraction.
+// (not tile_coords of ed_tile.h: has_affine is a run-time value here and the mapped axis takes its length from LDS)
 template <typename T, int ORDER>
 __device__ __forceinline__ bool voxel_coords(const TileGeom& tg, const HotParams* hp, const double* sQ,
                                              const AxTab& tx_, int zi, int yy, const int* o,
@@ -373,23 +374,6 @@ __device__ __forceinline__ bool voxel_coords(const TileGeom& tg, const HotParams
     for (int h = 0; h < 3; ++h)
         start[h] = cst ? 0 : ci[h] - ORDER / 2;
     return cst;
-}
-
-__device__ __forceinline__ void step_offsets(const HotParams* hp, int64_t ss, int64_t& in_off,
-                                             int64_t& out_off)
-{
-    in_off = 0;
-    out_off = 0;
-    int64_t r = ss;
-    const int nstep = hp->nstep;
-    for (int l = 0; l < nstep; ++l) {
-        const int64_t len = hp->step_len[l];
-        const int64_t q = r / len;
-        const int64_t c = r - q * len;
-        in_off += hp->in_step_stride[l] * c;
-        out_off += hp->out_step_stride[l] * c;
-        r = q;
-    }
 }
 
 __device__ __forceinline__ void step_offsets(const IOView& v, int64_t ss, int64_t& in_off,
@@ -443,7 +427,7 @@ __global__ __launch_bounds__(kBlock, 4) void deform_tile3_fwd_kernel(const GridG
     constexpr int NTX = NT + kPadX;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     for (int work = blockIdx.x;; work += gridDim.x) {
-    StripPos sp;
+    Strip sp;
     if (!strip_position(tg, work, sp))
         return;
     if (work != (int)blockIdx.x)
@@ -547,7 +531,7 @@ __global__ __launch_bounds__(kBlock, 4) void deform_tile3_fwd_kernel(const GridG
 
         for (int64_t ss = 0; ss < v.nsteps; ++ss) {
             int64_t in_off, out_off;
-            step_offsets(hp, ss, in_off, out_off);
+            hot_step_offsets(hp, ss, in_off, out_off);
             const T* src = in + in_off;
 
             if (any && !(ABL & 32)) {
@@ -677,29 +661,6 @@ __global__ __launch_bounds__(kBlock, 4) void deform_tile3_fwd_kernel(const GridG
 // ================================================================================================
 // K2: gradient (float32 / float64): integer LDS accumulation per tile, float atomics to flush
 // ================================================================================================
-// fixed-point accumulator of the data type: float32 -> int32, float64 -> int64 (ds_add_u64)
-template <typename T>
-struct GradFixed;
-template <>
-struct GradFixed<float> {
-    typedef int acc_t;
-    typedef unsigned int uacc_t;
-    static constexpr double kRange = 2147483648.0 - 1024.0;
-    __device__ static acc_t round(float x) { return __float2int_rn(x); }
-    __device__ static bool finite(float x) { return (__float_as_int(x) & 0x7f800000) != 0x7f800000; }
-};
-template <>
-struct GradFixed<double> {
-    typedef long long acc_t;
-    typedef unsigned long long uacc_t;
-    static constexpr double kRange = 4611686018427387904.0;      // 2^62
-    __device__ static acc_t round(double x) { return __double2ll_rn(x); }
-    __device__ static bool finite(double x)
-    {
-        return ((unsigned long long)__double_as_longlong(x) & 0x7ff0000000000000ULL) != 0x7ff0000000000000ULL;
-    }
-};
-
 __device__ __forceinline__ double wave_sum(double f)
 {
     for (int m = 32; m >= 1; m >>= 1)
@@ -713,12 +674,12 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? 2 : 3) void deform_tile3_g
                                                                       const TileGeom tg)
 {
     constexpr int NT = ORDER + 1;
-    typedef typename GradFixed<T>::acc_t acc_t;
-    typedef typename GradFixed<T>::uacc_t uacc_t;
+    typedef typename Fixed<T>::acc_t acc_t;
+    typedef typename Fixed<T>::uacc_t uacc_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int phase = 0;      // parity of the per-wave |dY| sum slots
     for (int work = blockIdx.x;; work += gridDim.x) {
-    StripPos sp;
+    Strip sp;
     if (!strip_position(tg, work, sp))
         return;
     if (work != (int)blockIdx.x)
@@ -805,7 +766,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? 2 : 3) void deform_tile3_g
 
         for (int64_t ss = 0; ss < v.nsteps; ++ss, ++phase) {
             int64_t in_off, out_off;
-            step_offsets(hp, ss, in_off, out_off);
+            hot_step_offsets(hp, ss, in_off, out_off);
             if (ss > 0)
                 __syncthreads();         // previous step's flush is done with the box
             // zero the accumulators; tile maximum of |dY|
@@ -821,7 +782,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? 2 : 3) void deform_tile3_g
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 gval[i] = active[i] ? dy[out_off + ooff[i]] : (T)0;
-                if (!GradFixed<T>::finite(gval[i])) {
+                if (!Fixed<T>::finite(gval[i])) {
                     // inf / NaN gradient: no fixed-point scale exists -- this voxel scatters its
                     // taps with float atomics straight to global memory (rare, rolled loops)
                     T w0[NT], w1[NT], w2[NT];
@@ -868,7 +829,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? 2 : 3) void deform_tile3_g
             // float32 rounding in the reference's own `+=` (deform.c:309-312).
             constexpr double kWmax = ORDER == 1 ? 1.0 : ORDER == 2 ? 0.4219 : (ORDER == 3 ? 0.2963
                                     : (ORDER == 4 ? 0.2150 : 0.1664));
-            const T scale = (T)(GradFixed<T>::kRange / (kWmax * 1.001 * (double)gtot));
+            const T scale = (T)(Fixed<T>::kRange / (kWmax * 1.001 * (double)gtot));
             const T inv_scale = (T)1 / scale;
 
             // two voxels per trip (four unrolled 64-tap scatters do not fit the register budget: fully
@@ -909,7 +870,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? 2 : 3) void deform_tile3_g
                         acc_t* rp = bp + (l0 * by + l1) * pitch;
 #pragma unroll
                         for (int l2 = 0; l2 < NT; ++l2)
-                            atomicAdd(reinterpret_cast<uacc_t*>(rp + l2), (uacc_t)GradFixed<T>::round(g1 * w2[l2]));
+                            atomicAdd(reinterpret_cast<uacc_t*>(rp + l2), (uacc_t)Fixed<T>::round(g1 * w2[l2]));
                     }
                 }
             }

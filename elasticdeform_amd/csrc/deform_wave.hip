@@ -56,67 +56,17 @@ namespace {
 typedef int int8v __attribute__((ext_vector_type(8)));
 typedef int int4v __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// min of lo[3] / max of hi[3] over the wave, result wave-uniform (six interleaved DPP chains ending
-// in lane 63, see deform_hot.hip's box_reduce_to_lds for why this is hand-written)
-#define ED_RED6(CTRL)                                      \
-    "v_min_i32_dpp %0, %0, %0 " CTRL "\n\t"                \
-    "v_min_i32_dpp %1, %1, %1 " CTRL "\n\t"                \
-    "v_min_i32_dpp %2, %2, %2 " CTRL "\n\t"                \
-    "v_max_i32_dpp %3, %3, %3 " CTRL "\n\t"                \
-    "v_max_i32_dpp %4, %4, %4 " CTRL "\n\t"                \
-    "v_max_i32_dpp %5, %5, %5 " CTRL "\n\t"
+// min of lo[3] / max of hi[3] over the wave, result wave-uniform
 __device__ __forceinline__ void wave_box(int (&lo)[3], int (&hi)[3])
 {
-    asm volatile("s_nop 1\n\t"
-                 ED_RED6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_mirror row_mask:0xf bank_mask:0xf")
-                 ED_RED6("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 ED_RED6("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
+    box_reduce<6>(lo, hi);
 #pragma unroll
     for (int h = 0; h < 3; ++h) {
         lo[h] = __builtin_amdgcn_readlane(lo[h], 63);
         hi[h] = __builtin_amdgcn_readlane(hi[h], 63);
     }
 }
-#undef ED_RED6
 
-__device__ __forceinline__ void glds16(const float* g, float* lds)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-struct WaveStrip {
-    int tz, ty, tx0, ntile, sample;
-};
-
-// strips are dealt to the 8 XCDs in contiguous chunks (block b runs on XCD b % 8): neighbouring
-// strips, whose source boxes overlap, share an L2
-__device__ __forceinline__ void strip_decode(const HotGeom& hg, WaveStrip& sp, int s)
-{
-    sp.sample = s / hg.nstrips;
-    s -= sp.sample * hg.nstrips;
-    const int sx = s % hg.strips_x;
-    s /= hg.strips_x;
-    sp.ty = s % hg.tiles[1];
-    sp.tz = s / hg.tiles[1];
-    sp.tx0 = sx * hg.strip_tiles;
-    sp.ntile = min(hg.strip_tiles, hg.tiles[2] - sp.tx0);
-}
-__device__ __forceinline__ bool wave_strip(const HotGeom& hg, WaveStrip& sp, int b)
-{
-    const int per = (hg.total_strips + 7) >> 3;
-    const int s = (b & 7) * per + (b >> 3);
-    if ((b >> 3) >= per || s >= hg.total_strips)
-        return false;
-    strip_decode(hg, sp, s);
-    return true;
-}
 // The lane's control columns of its Q row: 4 columns x 3 components (fp64), reloaded when the
 // wave-uniform index tuple of the x table changes (once per control interval).
 struct QCols {
@@ -141,11 +91,9 @@ __device__ __forceinline__ void qcols_load(QCols& qc, const double* __restrict__
 }
 
 // Phase A for one voxel (deform.c:649-824): displacement from the lane's control columns with the
-// wave-uniform cubic weights `tw`, (affine), + offset, window start and fractional offsets.  Same
-// operations in the same order as hot_coords (deform_hot.hip) and voxel_coords (deform_tile.hip): a
-// voxel gets bit-identical (start, frac) whichever kernel serves its tile.  `b[h]` = output index +
-// crop offset along axis h (no affine) or 0 (affine: the real base is in `P`).  Returns true when the
-// voxel maps to the constant.
+// wave-uniform cubic weights `tw`, (affine), + offset, window start and fractional offsets.  `b[h]` =
+// output index + crop offset along axis h (no affine) or 0 (affine: the real base is in `P`).  Returns
+// true when the voxel maps to the constant.
 template <int ORDER, bool AFFINE>
 __device__ __forceinline__ bool wave_coords(const HotGeom& hg, const HotParams* hp, const QCols& qc,
                                             const double (&tw)[4], const int (&b)[3], const double (&P)[3],
@@ -160,44 +108,7 @@ __device__ __forceinline__ bool wave_coords(const HotGeom& hg, const HotParams* 
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             d[c] = fma(tw[l], qc.v[l][c], d[c]);
-    int ci[3];
-    bool inr[3];
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        inr[h] = coord_axis_fast<ORDER, float>(AFFINE ? P[h] + d[h] : d[h], AFFINE ? 0 : b[h], hg.in_len[h],
-                                               ci[h], frac[h]);
-    bool cst = false;
-    if (!(inr[0] && inr[1] && inr[2])) {
-        // one divergent region: the axes along which the source point left the array
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-            if (!inr[h])
-                cst = coord_axis_mapped<ORDER, float>(AFFINE ? P[h] + d[h] : (double)b[h] + d[h], hg.in_len[h],
-                                                      hg.mode, hp->period[h], hp->inv_period[h], ci[h],
-                                                      frac[h]) || cst;
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        start[h] = cst ? 0 : ci[h] - ORDER / 2;
-    return cst;
-}
-
-__device__ __forceinline__ void wave_step_offsets(const HotParams* hp, long long ss, long long& vol_off,
-                                                  long long& img_off)
-{
-    vol_off = 0;
-    img_off = 0;
-    long long r = ss;
-    const int nstep = hp->nstep;
-    for (int l = 0; l < nstep; ++l) {
-        const long long len = hp->step_len[l];
-        const long long q = r / len;
-        const long long c = r - q * len;
-        vol_off += hp->in_step_stride[l] * c;
-        img_off += hp->out_step_stride[l] * c;
-        r = q;
-    }
+    return tile_coords<ORDER, AFFINE, float>(hg.in_len, &hg.mode, hp->period, hp->inv_period, d, b, P, start, frac);
 }
 
 // Rarely used wave-uniform values (boundary-map periods, the affine map, step-axis strides) are parked
@@ -207,23 +118,8 @@ constexpr int kWaveHead = 416;
 static_assert(sizeof(HotParams) <= kWaveHead, "HotParams must fit the head of the wave's LDS");
 __device__ __forceinline__ void wave_prologue(const HotGeom& hg, char* smem, int lane)
 {
-    HotParams* hp = reinterpret_cast<HotParams*>(smem);
-    if (lane < 12) {
-        hp->affine[lane] = hg.affine[lane];
-        if (lane < 3) {
-            hp->offd[lane] = (double)hg.off[lane];
-            hp->last[lane] = (double)(hg.in_len[lane] - 1);
-            hp->period[lane] = hg.period[lane];
-            hp->inv_period[lane] = hg.inv_period[lane];
-        }
-        if (lane < 8) {
-            hp->step_len[lane] = hg.step_len[lane];
-            hp->in_step_stride[lane] = hg.vol_step[lane];
-            hp->out_step_stride[lane] = hg.img_step[lane];
-        }
-        if (lane == 0)
-            hp->nstep = hg.nstep;
-    }
+    if (lane < 12)
+        fill_hot_params(reinterpret_cast<HotParams*>(smem), hg, lane);
     __builtin_amdgcn_s_waitcnt(0xC07F);       // lgkmcnt(0): one wave, DS operations are ordered
     asm volatile("" ::: "memory");
 }
@@ -475,11 +371,11 @@ __global__ __launch_bounds__(64, OCC) void wave_fwd_kernel(const HotGeom hg, con
     const HotParams* hp = reinterpret_cast<const HotParams*>(smem);
     float* box = reinterpret_cast<float*>(smem + kWaveHead);
     const int lane = threadIdx.x;
-    WaveStrip sp;
+    Strip sp;
 #ifdef EDHIP_EXPERIMENTS
     const unsigned long long t_begin = __builtin_readcyclecounter();
 #endif
-    if (!wave_strip(hg, sp, blockIdx.x))
+    if (!strip_of_block(hg, sp, blockIdx.x))
         return;
     wave_prologue(hg, smem, lane);
     const int yy = lane >> 3, zz = lane & 7;
@@ -544,7 +440,7 @@ __global__ __launch_bounds__(64, OCC) void wave_fwd_kernel(const HotGeom hg, con
             for (long long ss = 0; ss < hg.nsteps; ++ss) {
                 long long vol_off = 0, img_off = 0;
                 if (hg.nstep)
-                    wave_step_offsets(hp, ss, vol_off, img_off);
+                    hot_step_offsets(hp, ss, vol_off, img_off);
 #ifdef EDHIP_EXPERIMENTS
                 if (!ED_DBG(hg.dbg, 2))             // ablation: no staging
 #endif
@@ -646,13 +542,6 @@ __global__ __launch_bounds__(64, OCC) void wave_fwd_kernel(const HotGeom hg, con
 // in a per-tile scale derived from the tile's sum of |dY|, flushed by its own wave with one float
 // atomic per touched source element (deform.c:926-997; see deform_tile.hip for the no-overflow bound).
 // ================================================================================================
-__device__ __forceinline__ int round_half_up_i32(float x)
-{
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));      // (int)floor(x + 0.5) in one instruction
-    return r;
-}
-
 struct CellLayout {
     int b0[3], ext[3];
     int px, ps;           // cells per row / per plane
@@ -684,8 +573,8 @@ __global__ __launch_bounds__(64, OCC) void wave_grad_kernel(const HotGeom hg, co
     const HotParams* hp = reinterpret_cast<const HotParams*>(smem);
     int* cells = reinterpret_cast<int*>(smem + kWaveHead);
     const int lane = threadIdx.x;
-    WaveStrip sp;
-    if (!wave_strip(hg, sp, blockIdx.x))
+    Strip sp;
+    if (!strip_of_block(hg, sp, blockIdx.x))
         return;
     // the accumulator cells start at zero and every flush leaves the cells it read at zero again
     for (int e = lane * 4; e < hg.box_cap; e += 256)
@@ -801,7 +690,7 @@ __global__ __launch_bounds__(64, OCC) void wave_grad_kernel(const HotGeom hg, co
             for (long long ss = 0; ss < hg.nsteps; ++ss) {
                 long long vol_off = 0, img_off = 0;
                 if (hg.nstep)
-                    wave_step_offsets(hp, ss, vol_off, img_off);
+                    hot_step_offsets(hp, ss, vol_off, img_off);
                 float* dst = dx + vol_off;
                 // dY of the lane's row
                 float g[kT];
@@ -950,6 +839,7 @@ constexpr double kIntTieBand = 1e-4;
 constexpr double kCoordEps = 1e-6;
 
 // coordinates with the fraction in fp64; `near` is set when the voxel has to be re-evaluated exactly
+// (not tile_coords of ed_tile.h: the outermost cells take the mapped region too, which also looks for near-ties)
 template <int ORDER, bool AFFINE>
 __device__ __forceinline__ bool int_coords(const HotGeom& hg, const HotParams* hp, const QCols& qc,
                                            const double (&tw)[4], const int (&b)[3], const double (&P)[3],
@@ -1085,8 +975,8 @@ __global__ __launch_bounds__(64, 3) void wave_int_fwd_kernel(const HotGeom hg, c
     const HotParams* hp = reinterpret_cast<const HotParams*>(smem);
     float* box = reinterpret_cast<float*>(smem + kWaveHead);
     const int lane = threadIdx.x;
-    WaveStrip sp;
-    if (!wave_strip(hg, sp, blockIdx.x))
+    Strip sp;
+    if (!strip_of_block(hg, sp, blockIdx.x))
         return;
     wave_prologue(hg, smem, lane);
     const int yy = lane >> 3, zz = lane & 7;
@@ -1147,7 +1037,7 @@ __global__ __launch_bounds__(64, 3) void wave_int_fwd_kernel(const HotGeom hg, c
             for (long long ss = 0; ss < hg.nsteps; ++ss) {
                 long long vol_off = 0, img_off = 0;
                 if (hg.nstep)
-                    wave_step_offsets(hp, ss, vol_off, img_off);
+                    hot_step_offsets(hp, ss, vol_off, img_off);
                 const TIN* __restrict__ src = vol + vol_off;
                 if (bl.any && !direct) {
                     // stage the box as float32, every index through the mirror map (deform.c:791-813)

@@ -426,6 +426,75 @@ __device__ __forceinline__ unsigned narrow16(float x, int kind)
     return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x);
 }
 
+// ---------------------------------------------------------------------------------------------
+// one-instruction helpers of the hand-scheduled kernels (GCN builtins and inline assembly: HIP
+// compilations only -- the sanitizer tests compile the rest of this header as plain host C++)
+// ---------------------------------------------------------------------------------------------
+#ifdef __HIP__
+namespace ed {
+
+// a value the caller knows to be wave-uniform, moved to a scalar register
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float unif(float v) { return __int_as_float(uni(__float_as_int(v))); }
+// (int)floor(x + 0.5) in one instruction; __float2int_rn is v_rndne_f32 + v_cvt_i32_f32 (64 more VALU
+// instructions per voxel in the scatter).  Ties go up instead of to even: exact halves of a
+// fixed-point unit, no bias that matters.
+__device__ __forceinline__ int round_half_up_i32(float x)
+{
+    int r;
+    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+__device__ __forceinline__ void lds_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt: every wave
+// would sit out the round trip of the global stores / atomics it has just issued (about 2-4 us per
+// tile) although nothing in the workgroup reads those addresses back.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// barrier that also retires this wave's LDS-DMA copies
+__device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// LDS-DMA: 16 bytes per lane from global memory straight into LDS
+__device__ __forceinline__ void glds16(const float* g, float* lds)
+{
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                     (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+}
+// one output voxel of a float32 pass; OUT16: stored as a 16-bit float of kind `io16` (widen16 / narrow16)
+template <bool OUT16>
+__device__ __forceinline__ void store_out(float* img, long long off, float val, int io16)
+{
+    if constexpr (OUT16)      // (cached 2-byte stores: streamed past the L2 their half sectors cost 17 us)
+        reinterpret_cast<unsigned short*>(img)[off] = (unsigned short)narrow16(val, io16);
+    else
+        __builtin_nontemporal_store(val, img + off);
+}
+
+// fixed-point accumulator cells of the gradient kernels that scatter into LDS with integer atomics:
+// float32 -> int32, float64 -> int64 (ds_add_u64)
+template <typename T>
+struct Fixed;
+template <>
+struct Fixed<float> {
+    typedef int acc_t;
+    typedef unsigned int uacc_t;
+    static constexpr double kRange = 2147483648.0 - 1024.0;
+    __device__ static acc_t round(float x) { return __float2int_rn(x); }
+    __device__ static bool finite(float x) { return (__float_as_int(x) & 0x7f800000) != 0x7f800000; }
+};
+template <>
+struct Fixed<double> {
+    typedef long long acc_t;
+    typedef unsigned long long uacc_t;
+    static constexpr double kRange = 4611686018427387904.0;      // 2^62
+    __device__ static acc_t round(double x) { return __double2ll_rn(x); }
+    __device__ static bool finite(double x)
+    {
+        return ((unsigned long long)__double_as_longlong(x) & 0x7ff0000000000000ULL) != 0x7ff0000000000000ULL;
+    }
+};
+
+}  // namespace ed
+#endif  // __HIP__
+
 
 // Experiment switches of the kernels (EDHIP_TILE_DBG bits, timestamp buffers): live in the profiling build
 // (make EXPERIMENTS=1) only -- in the shipped library the tests below are the constant `false` and the code

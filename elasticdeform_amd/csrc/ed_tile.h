@@ -1,5 +1,6 @@
 // ed_tile.h -- definitions shared by the LDS-tiled deform kernels: deform_tile.hip (general tile
-// kernels, tables, spill levels, label kernel) and deform_hot.hip (the float32 benchmark kernels).
+// kernels, tables, spill levels, label kernel) and the float32 level-1 kernels (deform_hot.hip, deform_k1.hip,
+// deform_k1z.hip, deform_wave.hip): argument blocks, the coordinate arithmetic, strips, the wave-level box reduction.
 #pragma once
 
 #include "ed_device.h"
@@ -273,6 +274,103 @@ __device__ __forceinline__ bool coord_axis_mapped(double c, int in_len, int mode
     frac = (T)(cc - fl);
     return !(cc > -1.0);
 }
+// General coordinates of one voxel (deform.c:771-824), the tail every level-1 kernel ends its displacement
+// with: window start and fractions, with the boundary map for the axes along which the source point left the
+// array.  `d` = the displacement, `b[h]` = output index + crop offset along axis h (no affine) or 0 (affine:
+// the real base is in `P`).  in_len / mode / period / inv_period: pointers into whatever the kernel keeps them
+// in (kernel arguments, LDS, constant memory), read where a branch needs them.  raw_start: the window start before range test and boundary map, which
+// the fast tiles of the sampled-box kernels work with.  Returns true when the voxel maps to the constant.
+template <int ORDER, bool AFFINE, typename T, typename IntP, typename DblP>
+__device__ __forceinline__ bool tile_coords(IntP in_len, IntP mode, DblP period, DblP inv_period, const double (&d)[3],
+                                            const int (&b)[3], const double (&P)[3], int* start, T* frac,
+                                            int* raw_start = nullptr)
+{
+    int ci[3];
+    bool inr[3];
+#pragma unroll
+    for (int h = 0; h < 3; ++h)
+        inr[h] = coord_axis_fast<ORDER, T>(AFFINE ? P[h] + d[h] : d[h], AFFINE ? 0 : b[h], in_len[h], ci[h], frac[h]);
+    if (raw_start) {
+#pragma unroll
+        for (int h = 0; h < 3; ++h)
+            raw_start[h] = ci[h] - ORDER / 2;
+    }
+    bool cst = false;
+    if (!(inr[0] && inr[1] && inr[2])) {
+        // one divergent region: the axes along which the source point left the array
+#pragma unroll
+        for (int h = 0; h < 3; ++h) {
+            if (!inr[h])
+                cst = coord_axis_mapped<ORDER, T>(AFFINE ? P[h] + d[h] : (double)b[h] + d[h], in_len[h], *mode, period[h],
+                                                  inv_period[h], ci[h], frac[h]) || cst;
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 3; ++h)
+        start[h] = cst ? 0 : ci[h] - ORDER / 2;
+    return cst;
+}
+
+// Displacement of one voxel (deform.c:693-758 after the contraction over z and y) from a row of Q laid out
+// [control column][component padded to 4]: `off` = byte offsets of the four control columns, `w` = the cubic
+// weights along x; ds_read_b128 (components 0, 1) + ds_read_b64 (2) per column.  ROFF: immediate byte offset.
+template <int ROFF = 0>
+__device__ __forceinline__ void qrow_disp(const char* qrow, const int (&off)[4], const double (&w)[4], double (&d)[3])
+{
+    double2 q01[4];
+    double q2[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        q01[l] = *reinterpret_cast<const double2*>(qrow + off[l] + ROFF);
+        q2[l] = *reinterpret_cast<const double*>(qrow + off[l] + ROFF + 16);
+    }
+    d[0] = w[0] * q01[0].x;
+    d[1] = w[0] * q01[0].y;
+    d[2] = w[0] * q2[0];
+#pragma unroll
+    for (int l = 1; l < 4; ++l) {
+        d[0] = fma(w[l], q01[l].x, d[0]);
+        d[1] = fma(w[l], q01[l].y, d[1]);
+        d[2] = fma(w[l], q2[l], d[2]);
+    }
+}
+
+// Bounding box of a wave's tap windows: min of lo[3], max of hi[3] with DPP only -- four row steps
+// (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror) leave every lane with the result of
+// its row of 16 (STEPS 4); row_bcast:15 / row_bcast:31 then carry the row results upwards so that lane 63
+// holds the wave's (STEPS 6).  Hand-written: the compiler turns every __builtin_amdgcn_update_dpp step into
+// copy + s_nop + v_mov_dpp + v_min (4 instructions instead of 1) and wraps single-lane atomics behind it in a
+// wave-reduction loop -- together ~200 instructions per wave and tile, a quarter of K2's VALU work.  The six
+// chains are interleaved, which also covers the DPP read-after-write hazard (2 wait states) without s_nop.
+// All 64 lanes must be active.
+#define ED_RED6(CTRL)                                      \
+    "v_min_i32_dpp %0, %0, %0 " CTRL "\n\t"                \
+    "v_min_i32_dpp %1, %1, %1 " CTRL "\n\t"                \
+    "v_min_i32_dpp %2, %2, %2 " CTRL "\n\t"                \
+    "v_max_i32_dpp %3, %3, %3 " CTRL "\n\t"                \
+    "v_max_i32_dpp %4, %4, %4 " CTRL "\n\t"                \
+    "v_max_i32_dpp %5, %5, %5 " CTRL "\n\t"
+#define ED_RED6_ROWS                                                  \
+    "s_nop 1\n\t"                                                     \
+    ED_RED6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")         \
+    ED_RED6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")         \
+    ED_RED6("row_half_mirror row_mask:0xf bank_mask:0xf")             \
+    ED_RED6("row_mirror row_mask:0xf bank_mask:0xf")
+template <int STEPS>
+__device__ __forceinline__ void box_reduce(int (&lo)[3], int (&hi)[3])
+{
+    static_assert(STEPS == 4 || STEPS == 6, "rows of 16 lanes, or the wave to lane 63");
+    if constexpr (STEPS == 4)
+        asm volatile(ED_RED6_ROWS
+                     : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
+    else
+        asm volatile(ED_RED6_ROWS
+                     ED_RED6("row_bcast:15 row_mask:0xa bank_mask:0xf")
+                     ED_RED6("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                     : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
+}
+#undef ED_RED6_ROWS
+#undef ED_RED6
 
 struct TileGeom {
     int in_len[3];        // I_k (the tile kernels require extents < 2^30)
@@ -329,12 +427,13 @@ struct TileGeom {
     long long in_bstride, out_bstride, q_bstride, disp_bstride;
 };
 
-struct StripPos {
+// a run of at most strip_tiles tiles along x: what one workgroup of a level-1 kernel takes
+struct Strip {
     int tz, ty, tx0, ntile;   // tile coordinates of the strip and number of tiles in it
     int sample;               // which volume of the batch
 };
 
-__device__ __forceinline__ bool strip_position(const TileGeom& tg, int work, StripPos& sp)
+__device__ __forceinline__ bool strip_position(const TileGeom& tg, int work, Strip& sp)
 {
     if (tg.worklist) {
         // second-level pass: one 8^3 tile per work item, taken from the first level's spill list
@@ -423,6 +522,83 @@ struct HotGeom {
     long long step_len[8], vol_step[8], img_step[8];    // element strides of the step axes
     double period[3], inv_period[3], affine[12];
 };
+
+// One lane's share of filling HotParams in LDS, k = 0 .. 11.  The caller picks the twelve threads and places the
+// barrier; HotParams::slack is K1's own.
+__device__ __forceinline__ void fill_hot_params(HotParams* hp, const HotGeom& hg, int k)
+{
+    hp->affine[k] = hg.affine[k];
+    if (k < 3) {
+        hp->offd[k] = (double)hg.off[k];
+        hp->last[k] = (double)(hg.in_len[k] - 1);
+        hp->period[k] = hg.period[k];
+        hp->inv_period[k] = hg.inv_period[k];
+    }
+    if (k < 8) {
+        hp->step_len[k] = hg.step_len[k];
+        hp->in_step_stride[k] = hg.vol_step[k];
+        hp->out_step_stride[k] = hg.img_step[k];
+    }
+    if (k == 0)
+        hp->nstep = hg.nstep;
+}
+
+// element offsets of step `ss` of the step axes (the axes that are not deformed) on the input and output side;
+// I: long long or int64_t
+template <typename I>
+__device__ __forceinline__ void hot_step_offsets(const HotParams* hp, long long ss, I& vol_off, I& img_off)
+{
+    vol_off = 0;
+    img_off = 0;
+    I r = ss;
+    const int nstep = hp->nstep;
+    for (int l = 0; l < nstep; ++l) {
+        const I len = hp->step_len[l];
+        const I q = r / len;
+        const I c = r - q * len;
+        vol_off += hp->in_step_stride[l] * c;
+        img_off += hp->out_step_stride[l] * c;
+        r = q;
+    }
+}
+
+// ---- block -> strip of the level-1 kernels ---------------------------------------------------------------------------
+// Strips are dealt to the 8 XCDs in contiguous chunks (block b runs on XCD b % 8): neighbouring strips, whose
+// source boxes overlap, share an L2.  `s` = the strip of block `b` out of `total`; false: no strip.  A grid of
+// 8 * ceil(total / 8) blocks covers every strip once, and no block of a larger grid takes a second turn at one.
+__host__ __device__ __forceinline__ bool strip_of_block(int b, int total, int& s)
+{
+    const int per = (total + 7) >> 3;
+    s = (b & 7) * per + (b >> 3);
+    if ((b >> 3) >= per || s >= total)
+        return false;
+    return true;
+}
+// strip id -> sample and tile coordinates; nstrips = strips per sample, strips_x = strips per tile row
+__host__ __device__ __forceinline__ void strip_decode(Strip& sp, int s, int nstrips, int strips_x, int tiles_y, int tiles_x,
+                                                      int strip_tiles)
+{
+    sp.sample = s / nstrips;
+    s -= sp.sample * nstrips;
+    const int sx = s % strips_x;
+    s /= strips_x;
+    sp.ty = s % tiles_y;
+    sp.tz = s / tiles_y;
+    sp.tx0 = sx * strip_tiles;
+    sp.ntile = strip_tiles < tiles_x - sp.tx0 ? strip_tiles : tiles_x - sp.tx0;
+}
+__device__ __forceinline__ void strip_decode(const HotGeom& hg, Strip& sp, int s)
+{
+    strip_decode(sp, s, hg.nstrips, hg.strips_x, hg.tiles[1], hg.tiles[2], hg.strip_tiles);
+}
+__device__ __forceinline__ bool strip_of_block(const HotGeom& hg, Strip& sp, int b)
+{
+    int s;
+    if (!strip_of_block(b, hg.total_strips, s))
+        return false;
+    strip_decode(hg, sp, s);
+    return true;
+}
 
 // level-1 launch of K2 (deform_hot.hip: the gradient, orders 1-5); hipErrorNotSupported when (order, ...) has no
 // instantiation

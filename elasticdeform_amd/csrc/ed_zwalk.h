@@ -1,6 +1,6 @@
 // ed_zwalk.h -- the arithmetic of the z-walk kernels (deform_k1z.hip), kept apart from their tiling: the displacement from
 // R[o_y][o_x][k_z][c] (contracted over y and x once per call by the geometry kernel) with lane-constant control planes and
-// scalar z weights, and the general coordinates of a voxel.
+// scalar z weights, and what the general coordinates of a voxel (tile_coords, ed_tile.h) read on this route.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -83,37 +83,6 @@ __device__ __forceinline__ void k1z_disp(const ZTaps& tp, const double (&zw)[4],
         for (int l = 1; l < 4; ++l)
             d[h] = fma(zw[l], tp.r[l][h], d[h]);
     }
-}
-
-// general coordinates of one voxel (deform.c:771-824): the arithmetic every tile kernel shares (ed_tile.h)
-template <int ORDER, bool AFFINE>
-__device__ __forceinline__ bool k1z_coords(czgen_p zn, const double (&d)[3], const int (&b)[3], const double (&P)[3], int* start,
-                                           float* frac, int* raw_start = nullptr)
-{
-    int ci[3];
-    bool inr[3];
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        inr[h] = coord_axis_fast<ORDER, float>(AFFINE ? P[h] + d[h] : d[h], AFFINE ? 0 : b[h], zn->in_len[h], ci[h], frac[h]);
-    if (raw_start) {
-#pragma unroll
-        for (int h = 0; h < 3; ++h)
-            raw_start[h] = ci[h] - ORDER / 2;
-    }
-    bool cst = false;
-    if (!(inr[0] && inr[1] && inr[2])) {
-        // one divergent region: the axes along which the source point left the array
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-            if (!inr[h])
-                cst = coord_axis_mapped<ORDER, float>(AFFINE ? P[h] + d[h] : (double)b[h] + d[h], zn->in_len[h], zn->mode,
-                                                      zn->period[h], zn->inv_period[h], ci[h], frac[h]) || cst;
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 3; ++h)
-        start[h] = cst ? 0 : ci[h] - ORDER / 2;
-    return cst;
 }
 
 }  // namespace

@@ -306,7 +306,7 @@ __device__ __forceinline__ TileGeo tile_geometry(const LineTile& p)
         g.olen[d] = d < p.nouter ? (uint32_t)p.outer_len[d] : 1u;
     if (!p.win)
         return g;
-    auto w = [&](int dim, int k) { return __builtin_amdgcn_readfirstlane(p.win[2 * dim + k]); };
+    auto w = [&](int dim, int k) { return uni(p.win[2 * dim + k]); };
     const int a0 = w(p.win_axis, 0), a1 = w(p.win_axis, 1);
     g.in_off = (int64_t)a0 * p.in_axis_stride;
     g.out_off = (int64_t)a0 * p.out_axis_stride;
@@ -473,13 +473,9 @@ struct VecOf<double> {
     static constexpr int N = 2;
 };
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. it would
+// Barriers here are lds_barrier() (ed_device.h): __syncthreads() also drains vmcnt, i.e. it would
 // wait for the next tile's prefetch loads (and this tile's global stores) at every barrier.  The tile
 // kernels never communicate through global memory inside a launch, so LDS ordering is all they need.
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // ---- strided axis ----------------------------------------------------------------------------------
 // Persistent workgroups; with VEC the next tile's rows are already in flight (in registers) while

@@ -316,3 +316,21 @@ def test_a_deformed_axis_of_length_one_gives_the_reference_result():
         assert isinstance(both, list) and both[1].dtype == np.float32 and not both[0].any()
     with pytest.raises(RuntimeError):
         ed.deform_grid(np.zeros((1, 5), dtype=np.complex64), np.zeros((2, 2, 2)))
+
+
+def test_strip_deal_covers_every_strip_once(tmp_path):
+    """strip_of_block / strip_decode (csrc/ed_tile.h), the one block -> strip map of the level-1 tile kernels, driven
+    from a host-only C++ program (no GPU, no HIP call): over a grid of 8 * ceil(total / 8) blocks every strip is dealt
+    exactly once, no block of a larger grid takes a strip again, and the decoded strips enumerate every tile once."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    exe = str(tmp_path / "strip_deal_test")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-w",
+                    "-I" + os.path.join(root, "elasticdeform_amd", "csrc"), "-I" + os.path.join(root, "include"),
+                    os.path.join(root, "tests", "cxx", "strip_deal_test.cpp"), "-o", exe], check=True, timeout=300)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
