@@ -30,6 +30,10 @@ a tensor that requires grad carries autograd through ``deform_grid_inverse``.
 differentiate ``deform_grid_inverse`` with respect to the control-point displacement and to affine, rotate and zoom:
 what a loss taken in the source (fixed) frame needs; ``displacement_grad=True`` / ``affine_grad=True`` carry them through
 autograd.
+``deform_grid_jacobian`` / ``deform_grid_jacobian_batch`` give det J of the coordinate map at every output voxel (the
+folding check of a fitted field, without a coordinate volume), ``deform_grid_jacobian_gradient`` /
+``deform_grid_jacobian_gradient_batch`` its adjoint with respect to the displacement and to affine, rotate and zoom:
+what a folding penalty, a log det or a volume-preservation term differentiates.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
@@ -44,7 +48,9 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_inverse, deform_grid_inverse_batch, deform_grid_inverse_gradient,
                           deform_grid_inverse_gradient_batch, deform_grid_inverse_displacement_gradient,
                           deform_grid_inverse_displacement_gradient_batch, deform_grid_inverse_affine_gradient,
-                          deform_grid_inverse_affine_gradient_batch)
+                          deform_grid_inverse_affine_gradient_batch, JacobianGradient, deform_grid_jacobian,
+                          deform_grid_jacobian_gradient, deform_grid_jacobian_batch,
+                          deform_grid_jacobian_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

@@ -56,7 +56,7 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
            'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient',
-           'edhip_deform_inverse_transform_gradient')
+           'edhip_deform_inverse_transform_gradient', 'edhip_deform_jacobian', 'edhip_deform_jacobian_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -214,6 +214,17 @@ def load():
             ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
             ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_uint32, ctypes.c_void_p,
             ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_jacobian.restype = ctypes.c_int
+        L.edhip_deform_jacobian.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+            ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_jacobian_gradient.restype = ctypes.c_int
+        L.edhip_deform_jacobian_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -433,6 +444,30 @@ def deform_points_gradient(inverse, nbatch, pos_desc, pos_bstride, cot_desc, cot
           (int(bool(inverse)), int(nbatch), *_pairs(pos_desc, pos_bstride, cot_desc, cot_bstride, status_desc,
                                                     status_bstride, disp_desc, disp_bstride), lens, off, len(in_len),
            aff, *_pairs(dpts_desc, dpts_bstride, ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride)), flags, stream)
+
+
+def deform_jacobian(nbatch, disp_desc, disp_bstride, in_len, output_offset, inverse_affine, det_desc, det_bstride, flags,
+                    stream):
+    """edhip_deform_jacobian: det J of the coordinate map at every voxel of the crop box into `det_desc` (float32 /
+    float64, one dimension per deformed axis).  Sample 0's descriptors plus byte strides; `disp_desc` is the
+    PREFILTERED control grid."""
+    lens, in_len = _ptr(in_len, numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_jacobian,
+          (int(nbatch), *_pairs(disp_desc, disp_bstride), lens, off, len(in_len), aff, *_pairs(det_desc, det_bstride)),
+          flags, stream)
+
+
+def deform_jacobian_gradient(nbatch, ddet_desc, ddet_bstride, disp_desc, disp_bstride, in_len, output_offset,
+                             inverse_affine, ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride, flags, stream):
+    """edhip_deform_jacobian_gradient: the adjoint of deform_jacobian() for the cotangent `ddet_desc`.  Results (None =
+    not wanted): the gradient with respect to the PREFILTERED grid into `ddisp_desc`, with respect to the inverse map
+    into `dinv_desc` (float64, naxis x naxis+1)."""
+    lens, in_len = _ptr(in_len, numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_jacobian_gradient,
+          (int(nbatch), *_pairs(ddet_desc, ddet_bstride, disp_desc, disp_bstride), lens, off, len(in_len), aff,
+           *_pairs(ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride)), flags, stream)
 
 
 def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, out_desc, out_bstride,

@@ -287,6 +287,25 @@ size_t inverse_tgrad_scratch_bytes(const GridGeom& g, int nbatch);
 hipError_t launch_deform_inverse_transform_gradient(const InverseCall& c, const BatchArray& ddisp, const BatchArray& dK,
                                                     char* scratch, hipStream_t stream);
 
+// det J of the coordinate map on the voxel lattice and its adjoint (deform_jacobian.hip): rows along the last deformed
+// axis, the other axes contracted once per row; blockIdx.y = sample, fp64, no atomics.  1 to 3 deformed axes;
+// hipErrorNotSupported (nothing launched) otherwise.
+struct JacobianCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len = I (>= 2 each), out_len = the crop
+    int nbatch;
+    int64_t disp_bstride;
+    BatchArray det;               // deformed extents g.out_len, float32 / float64: det (written) / dL/d det (read)
+    BatchArray ddisp;             // gradient: of the PREFILTERED grid, the grid's shape, float32 / float64; may be empty
+    BatchArray dK;                // gradient: float64 (naxis, naxis + 1); may be empty
+    char* scratch;                // gradient: jacobian_grad_scratch_bytes() bytes
+};
+hipError_t launch_deform_jacobian(const JacobianCall& c, hipStream_t stream);
+// per sample rows * nch * (naxis^2 w + naxis^2) doubles -- a row is served in nch units of xc <= 256 voxels, each
+// reaching at most w control points of the last axis (w <= min(ncp_last, ceil((xc - 1) s_last) + 6); xc as large as
+// naxis^2 w <= 512 and xc w <= 1280 allow) --; 3 axes: plus O_0 * (2 naxis ncp_1 ncp_2 + naxis^2) doubles
+size_t jacobian_grad_scratch_bytes(const GridGeom& g, int nbatch);
+hipError_t launch_deform_jacobian_gradient(const JacobianCall& c, hipStream_t stream);
+
 // first bytes of every per-stream workspace are reserved for the prefiltered control grid
 constexpr size_t kWorkspaceGridBytes = 64 * 1024;
 

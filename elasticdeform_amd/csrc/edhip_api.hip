@@ -1761,4 +1761,104 @@ int edhip_deform_inverse_transform_gradient(int nbatch, const edhip_array* input
     return EDHIP_OK;
 }
 
+// ---- det J of the coordinate map on the voxel lattice and its adjoint (deform_jacobian.hip) -------------------------
+// What edhip_deform_jacobian and edhip_deform_jacobian_gradient check and fill alike.  lattice0: det (written) or ddet
+// (read), called `name` in the messages; its own dimensions are the deformed axes.
+static int fill_jacobian_call(const char* entry, int nbatch, const edhip_array* lattice0, const char* name,
+                              int64_t lattice_batch_stride, const edhip_array* displacement0,
+                              int64_t displacement_batch_stride, const int64_t* in_len, const int64_t* output_offset,
+                              int naxis, const double* affine, const edhip_array* ddisplacement0,
+                              const edhip_array* dinverse_affine0, bool gradient, uint32_t flags, ed::JacobianCall& c,
+                              char* err, size_t errlen)
+{
+    static const int32_t lattice_axes[3] = {0, 1, 2};
+    if (int st = check_batch_call(nbatch, lattice0 && displacement0 && in_len, err, errlen))
+        return st;
+    if (int st = check_axes_1_to_3(entry, lattice_axes, naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered(entry, flags, err, errlen))
+        return st;
+    if (gradient && !ddisplacement0 && !dinverse_affine0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "none of ddisplacement and dinverse_affine is requested");
+    if (lattice0->ndim != naxis)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "%s must have one dimension per deformed axis", name);
+    if (!f32_or_f64(lattice0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "%s must be float32 or float64", name);
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (ddisplacement0) {
+        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        if (!f32_or_f64(ddisplacement0))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must be float32 or float64");
+    }
+    if (dinverse_affine0) {
+        const int64_t map[2] = {naxis, naxis + 1};
+        if (!has_shape(dinverse_affine0, 2, map))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
+    if (int st = check_batch_limit(entry, nbatch, err, errlen))
+        return st;
+    memset(&c, 0, sizeof(c));
+    if (int st = fill_geometry(displacement0, in_len, lattice0->shape, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    c.nbatch = nbatch;
+    c.disp_bstride = displacement_batch_stride;
+    c.det = batch_array(lattice0, lattice_batch_stride);
+    return EDHIP_OK;
+}
+
+int edhip_deform_jacobian(int nbatch, const edhip_array* displacement0, int64_t displacement_batch_stride,
+                          const int64_t* in_len, const int64_t* output_offset, int naxis, const double* affine,
+                          const edhip_array* det0, int64_t det_batch_stride, uint32_t flags, void* hip_stream,
+                          char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    JacobianCall c;
+    if (int st = fill_jacobian_call("edhip_deform_jacobian", nbatch, det0, "det", det_batch_stride, displacement0,
+                                    displacement_batch_stride, in_len, output_offset, naxis, affine, nullptr, nullptr,
+                                    false, flags, c, err, errlen))
+        return st;
+    if (nbatch == 0 || c.g.nvox <= 0)
+        return EDHIP_OK;
+    const hipError_t e = launch_deform_jacobian(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform jacobian launch");
+    return EDHIP_OK;
+}
+
+int edhip_deform_jacobian_gradient(int nbatch, const edhip_array* ddet0, int64_t ddet_batch_stride,
+                                   const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                   const int64_t* in_len, const int64_t* output_offset, int naxis, const double* affine,
+                                   const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                   const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                   uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    JacobianCall c;
+    if (int st = fill_jacobian_call("edhip_deform_jacobian_gradient", nbatch, ddet0, "ddet", ddet_batch_stride,
+                                    displacement0, displacement_batch_stride, in_len, output_offset, naxis, affine,
+                                    ddisplacement0, dinverse_affine0, true, flags, c, err, errlen))
+        return st;
+    if (nbatch == 0)
+        return EDHIP_OK;
+    c.ddisp = batch_array(ddisplacement0, ddisplacement_batch_stride);
+    c.dK = batch_array(dinverse_affine0, dinverse_affine_batch_stride);
+    // the per-unit and per-plane partial sums: the stream's workspace, behind its grid head
+    StreamGuard guard(stream);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + jacobian_grad_scratch_bytes(c.g, nbatch), &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    c.scratch = ws + kWorkspaceGridBytes;
+    e = launch_deform_jacobian_gradient(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform jacobian gradient launch");
+    return EDHIP_OK;
+}
+
 }  // extern "C"

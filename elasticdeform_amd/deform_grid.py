@@ -1531,6 +1531,170 @@ def deform_points_gradient_batch(points, d_positions, displacements, X_shape, cr
                                    True)
 
 
+# ---- det J of the coordinate map on the voxel lattice, with gradients (no counterpart in the reference) ----------
+
+JacobianGradient = collections.namedtuple('JacobianGradient',
+                                          ['displacement', 'affine', 'rotate', 'zoom', 'inverse_map'])
+
+_DET_DTYPES = ('float32', 'float64')
+
+
+def _jacobian_plan(displacement, X_shape, crop, axis, affine, rotate, zoom, batch):
+    """(Plan of the image call on an array of X_shape, naxis, the shape of det: the deformed axes of the output --
+    behind the batch axis for a batch)"""
+    if X_shape is None:
+        raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
+    X_shape = tuple(int(v) for v in X_shape)
+    nbatch = None
+    if batch:
+        nbatch = int(displacement.shape[0]) if _host.is_array(displacement) and displacement.ndim >= 1 else 0
+    plan = _plan_of(_shape_only(X_shape, nbatch), batch, displacement, 3, 'constant', 0.0, crop, axis, affine, rotate,
+                    zoom)
+    n = plan.naxis
+    if n > 3:
+        raise ValueError("deform_grid_jacobian takes 1 to 3 deformed axes, not %d." % n)
+    lattice = tuple(int(plan.output_shapes[0][d]) for d in plan.axis[0])
+    return plan, n, ((nbatch,) if batch else ()) + lattice
+
+
+def _jacobian_run(displacement, X_shape, crop, axis, affine, rotate, zoom, dtype, batch):
+    """deform_grid_jacobian, single call and batch.  Every argument check runs before the device is touched."""
+    if dtype is None:
+        name = 'float64'
+    elif isinstance(dtype, str):
+        name = dtype
+    else:
+        try:
+            name = numpy.dtype(dtype).name
+        except TypeError:
+            name = str(dtype).replace('torch.', '')      # a torch dtype: torch.float32 -> 'float32'
+    if name not in _DET_DTYPES:
+        raise ValueError("dtype should be 'float32' or 'float64' (or None: float64).")
+    plan, n, shape = _jacobian_plan(displacement, X_shape, crop, axis, affine, rotate, zoom, batch)
+    if any(int(d) == 1 for d in plan.deform_shape):
+        # a deformed axis of length 1: no coordinate is defined there (deform_grid_coordinates gives NaN)
+        return _fill(displacement, shape, float('nan'), name)
+    torch = _torch()
+    device = _device_for([displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
+        det = torch.empty(shape, dtype=getattr(torch, name), device=device)
+        if det.numel():
+            _lib.deform_jacobian(shape[0] if batch else 1, *_sample(df, batch), plan.deform_shape, plan.output_offset,
+                                 plan.inverse_affine, *_sample(det, batch), 0, stream)
+        return _from_device(det, displacement)
+
+
+def deform_grid_jacobian(displacement, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None, dtype=None):
+    """
+    The Jacobian determinant of the coordinate map of :func:`deform_grid` at every output voxel: ``det[o] = det J(o)``
+    for the ``J`` that ``deform_grid_coordinates(o, displacement, X_shape, ..., jacobian=True)`` returns at the integer
+    crop-local position ``o``.  ``det <= 0`` somewhere means the field folds there; ``det`` is the local volume
+    change of the map from the output to the source.  ``X_shape`` is the shape of the array ``deform_grid`` deforms;
+    the other arguments are deform_grid's own, checked the same way.  1 to 3 deformed axes.
+
+    The result has the shape of the deformed axes of what ``deform_grid`` returns for that call (crop applied), dtype
+    float64 -- or float32 with ``dtype='float32'``: the arithmetic is fp64 and a float32 result is rounded once.  No
+    positions are read and no coordinates formed: on the lattice the tap weights of an axis depend on that axis'
+    index only, so the axes other than the last are contracted once per row.  A voxel's value depends on its
+    position in the uncropped output and the call's arguments only: without affine / rotate / zoom a crop gives the
+    bits of the whole lattice at those voxels.
+
+    numpy in gives numpy out, otherwise a tensor on the displacement's device.  A deformed axis of length 1 gives
+    NaN.  No autograd flows through this call itself: :func:`deform_grid_jacobian_gradient` is its adjoint and
+    ``elasticdeform_amd.torch.deform_grid_jacobian`` the differentiable wrapper.
+    """
+    return _jacobian_run(displacement, X_shape, crop, axis, affine, rotate, zoom, dtype, False)
+
+
+def deform_grid_jacobian_batch(displacements, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None,
+                               dtype=None):
+    """:func:`deform_grid_jacobian` over a batch with one control grid per sample: ``displacements``
+    ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample; everything else is shared.  The result is
+    ``(B, ...)``.  One launch for the batch; sample b equals the single call, bit for bit."""
+    return _jacobian_run(displacements, X_shape, crop, axis, affine, rotate, zoom, dtype, True)
+
+
+def _jacobian_gradient(d_det, displacement, X_shape, crop, axis, affine, rotate, zoom, batch, want_disp=True,
+                       want_map=True):
+    """The adjoint of _jacobian_run: ONE library call for whatever is wanted.  Returns (plan, d displacement or None
+    in the family of `d_det`, dK or None: a float64 tensor (naxis, naxis+1) -- (B, naxis, naxis+1) for a batch).
+    Every argument check runs before the device or the library is touched."""
+    plan, n, shape = _jacobian_plan(displacement, X_shape, crop, axis, affine, rotate, zoom, batch)
+    if not _host.is_array(d_det):
+        d_det = numpy.asarray(d_det)
+    if _volume_dtype_name(d_det) not in _DET_DTYPES:
+        raise ValueError("d_det should be float32 or float64, not %s." % _volume_dtype_name(d_det))
+    if tuple(int(v) for v in d_det.shape) != shape:
+        raise ValueError("d_det should have the shape of det, %s, but its shape is %s."
+                         % (str(shape), str(tuple(d_det.shape))))
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
+    dk_shape = ((shape[0],) if batch else ()) + (n, n + 1)
+    torch = _torch()
+    if not isinstance(d_det, numpy.ndarray):
+        d_det = d_det.detach()
+
+    if any(int(d) == 1 for d in plan.deform_shape):
+        # a deformed axis of length 1: det is NaN whatever the arguments, nothing depends on anything
+        dk = None
+        if want_map:
+            dk = torch.zeros(dk_shape, dtype=torch.float64, device=d_det.device if torch.is_tensor(d_det) else 'cpu')
+        return plan, _dgrad_zeros(displacement, d_det) if want_disp else None, dk
+
+    device = _device_for([d_det, displacement])
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        gd = _to_device(d_det, device)
+        dd = _to_device(displacement, device)
+        df = _prefiltered_grid(dd, batch, device, stream)
+        dp = torch.empty(tuple(int(v) for v in dd.shape), dtype=torch.float64, device=device) if want_disp else None
+        dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
+        if want_disp or want_map:
+            _lib.deform_jacobian_gradient(shape[0] if batch else 1, *_sample(gd, batch), *_sample(df, batch),
+                                          plan.deform_shape, plan.output_offset, plan.inverse_affine,
+                                          *_sample(dp, batch), *_sample(dk, batch), 0, stream)
+        out = None
+        if dp is not None:
+            # dD = (order-3 mirror prefilter)^T dP in fp64, rounded once to the result's dtype
+            dp = _filter_axes(dp, _grid_axes(dd, batch), 3, True, device, overwrite=True, stream=stream)
+            out = _from_device(dp.to(_result_tensor_dtype(displacement)), d_det)
+    return plan, out, dk
+
+
+def deform_grid_jacobian_gradient(d_det, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                                  zoom=None):
+    """
+    Gradient through :func:`deform_grid_jacobian`: for ``L`` with ``d_det = dL / d det`` (the shape of ``det``,
+    float32 / float64) returns ``JacobianGradient(displacement, affine, rotate, zoom, inverse_map)``:
+
+    * ``displacement``: dL / d displacement (the order-3 prefilter of the grid included), as
+      :func:`deform_grid_displacement_gradient` returns it;
+    * ``affine`` / ``rotate`` / ``zoom`` / ``inverse_map``: as in :class:`AffineGradient` (``zoom=0`` raises).  The
+      translation column of ``inverse_map`` is zero: det does not depend on it.
+
+    With ``C(o)`` the cofactor matrix of ``J(o)`` (so that the derivative is right where ``det = 0`` too) this is
+    ``dP[h, j] = sum_o d_det(o) sum_l C[h, l](o) d_l beta_j(o)`` and ``dK[h, l] = sum_o d_det(o) C[h, l](o)``, summed
+    in fp64 as a chain of small contractions -- over x per row, over the rows, over the planes -- in an order that
+    depends on the shapes only: no atomics, the same bits on every call.  A float32 ``d_det`` is widened at the load.
+    numpy in gives numpy out, otherwise tensors on ``d_det``'s device.  A deformed axis of length 1 gives zeros.
+    """
+    plan, ddisp, dk = _jacobian_gradient(d_det, displacement, X_shape, crop, axis, affine, rotate, zoom, False)
+    return JacobianGradient(ddisp, *_affine_result(dk, plan, affine, rotate, zoom, isinstance(ddisp, numpy.ndarray)))
+
+
+def deform_grid_jacobian_gradient_batch(d_det, displacements, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                                        zoom=None):
+    """:func:`deform_grid_jacobian_gradient` over a batch with one control grid per sample: ``d_det`` ``(B, ...)``,
+    ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample.  ``displacement`` is per sample,
+    the same bits as the single call on that sample; the map's fields are the sum over the samples in sample order
+    (:func:`deform_grid_affine_gradient_batch`).  One set of launches for the batch."""
+    plan, ddisp, dk = _jacobian_gradient(d_det, displacements, X_shape, crop, axis, affine, rotate, zoom, True)
+    return JacobianGradient(ddisp, *_affine_result_batch(dk, plan, affine, rotate, zoom,
+                                                         isinstance(ddisp, numpy.ndarray)))
+
+
 # ---- label-aware linear resampling of label maps (no counterpart in the reference) -------------------------------
 
 _LABEL_RANGE = {'bool': (0, 1), 'uint8': (0, 2 ** 8 - 1), 'int8': (-2 ** 7, 2 ** 7 - 1), 'uint16': (0, 2 ** 16 - 1),

@@ -35,6 +35,11 @@ from . import deform_grid_inverse_gradient, deform_grid_inverse_gradient_batch  
 # them through DeformGridInverseExtended below
 from . import deform_grid_inverse_displacement_gradient, deform_grid_inverse_displacement_gradient_batch  # noqa: F401
 from . import deform_grid_inverse_affine_gradient, deform_grid_inverse_affine_gradient_batch  # noqa: F401
+# det J on the voxel lattice: the batch forms and the explicit gradient are the package's own (no autograd);
+# deform_grid_jacobian below is the differentiable wrapper of the single call
+from . import deform_grid_jacobian_batch, deform_grid_jacobian_gradient_batch  # noqa: F401
+from . import deform_grid_jacobian_gradient  # noqa: F401
+from . import deform_grid_jacobian as _deform_grid_jacobian_fn
 import importlib  # noqa: E402
 
 _api = importlib.import_module("elasticdeform_amd.deform_grid")      # (the module, not the function)
@@ -418,6 +423,60 @@ def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=No
                                dict(X_shape=X_shape, crop=crop, axis=axis, max_iter=max_iter, tol=tol),
                                bool(displacement_grad))
     return (q, ok) if return_converged else q
+
+
+# ---- det J on the voxel lattice, with autograd ------------------------------------------------------------------------
+
+class DeformGridJacobian(torch.autograd.Function):
+    """forward: deform_grid_jacobian; backward: ONE call of deform_grid_jacobian_gradient's kernels for whatever needs
+    a gradient (inputs: displacement, affine, rotate, zoom, two non-tensors)"""
+
+    @staticmethod
+    def forward(ctx, displacement, affine, rotate, zoom, kw, disp_grad):
+        call = _points_forward(ctx, None, displacement, affine, rotate, zoom, kw, disp_grad)
+        ctx.save_for_backward(displacement)
+        return _deform_grid_jacobian_fn(displacement.detach(), kw['X_shape'], dtype=kw['dtype'], **call)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_det):
+        displacement = ctx.saved_tensors[0].detach()
+        want_disp = ctx.disp_grad and ctx.needs_input_grad[0]
+        want_map = any(ctx.needs_input_grad[1:4])
+        ddisp = None
+        grads = [None, None, None]
+        if want_disp or want_map:
+            host = ctx.host
+            plan, ddisp, dk = _api._jacobian_gradient(
+                d_det.detach(), displacement, ctx.x_shape, ctx.kw.get('crop'), ctx.kw.get('axis'), host.get('affine'),
+                host.get('rotate'), host.get('zoom'), False, want_disp=want_disp, want_map=want_map)
+            if ddisp is not None:
+                ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
+            if dk is not None:
+                r = _api._affine_result(dk, plan, host.get('affine'), host.get('rotate'), host.get('zoom'), False)
+                grads = _param_grads(ctx.needs_input_grad[1:4], ctx.params, r[:3])
+        return (ddisp,) + tuple(grads) + (None, None)
+
+
+def deform_grid_jacobian(displacement, X_shape, crop=None, axis=None, affine=None, rotate=None, zoom=None, dtype=None, *,
+                         displacement_grad=False, affine_grad=False):
+    """
+    ``elasticdeform_amd.deform_grid_jacobian`` with autograd: det J of the coordinate map at every output voxel, the
+    gradient flowing to ``displacement`` with ``displacement_grad=True`` and to tensor ``affine`` / ``rotate`` /
+    ``zoom`` with ``affine_grad=True`` (keyword-only, the switches of :func:`deform_grid_coordinates`), in their dtype
+    and on their device; the backward is ONE call of ``elasticdeform_amd.deform_grid_jacobian_gradient``'s kernels.
+    This is what a folding penalty (``relu(-det)``), a ``log det`` term or a volume-preservation term differentiates.
+    With nothing requiring a gradient the call is the package's own: no graph is built, numpy stays numpy.
+    """
+    params = (affine, rotate, zoom)
+    if not _points_need_autograd(None, displacement, params, displacement_grad, affine_grad):
+        host = [_host_value(v) for v in params]
+        return _deform_grid_jacobian_fn(displacement, X_shape, crop, axis, *host, dtype=dtype)
+    displacement = torch.as_tensor(displacement)
+    if not affine_grad:
+        params = tuple(_host_value(v) for v in params)
+    return DeformGridJacobian.apply(displacement, *params, dict(X_shape=X_shape, crop=crop, axis=axis, dtype=dtype),
+                                    bool(displacement_grad))
 
 
 # ---- an image carried back through the deformation, with autograd -----------------------------------------------------

@@ -674,6 +674,63 @@ int edhip_deform_inverse_transform_gradient(int nbatch,
                                             char* err, size_t errlen);
 
 /*
+ * det J of the coordinate map on the voxel lattice (deform_jacobian.hip): for every integer crop-local output
+ * position o of a strided batch, det0[o] = det J(o) with J the Jacobian edhip_deform_points returns at q = o,
+ *   J[h,l](o) = K[h,l] + (ncp_l - 1) / (I_l - 1) sum_t P[h, m(t)] w'_l prod_{k != l} w_k.
+ * No positions are read and no coordinates formed: the axes other than the last are contracted once per row of the
+ * last deformed axis, every voxel then does 4 taps per entry of J.
+ *   nbatch, displacement0, displacement_batch_stride, in_len, output_offset, naxis, affine
+ *                        as for edhip_deform_points (the PREFILTERED grid; EDHIP_FLAG_RAW_DISPLACEMENT is refused);
+ *                        naxis 1..3 (more: EDHIP_ERR_UNSUPPORTED); in_len >= 2 on every axis (EDHIP_ERR_INVALID).
+ *   det0                 written: one dimension per deformed axis (EDHIP_ERR_INVALID) -- its extents are the crop
+ *                        box's --, float32 / float64 (EDHIP_ERR_DTYPE), any strides.  fp64 arithmetic, a float32
+ *                        value is rounded once.
+ * det0[o] depends on o + output_offset and the call's arguments only: a crop gives the bits of the whole lattice at
+ * those voxels, a sample of a batch the bits of the single call, a repeated call and a graph replay the same bits.
+ * One launch, no workspace, no synchronisation; can be captured into a HIP graph.
+ */
+int edhip_deform_jacobian(int nbatch,
+                          const edhip_array* displacement0, int64_t displacement_batch_stride,
+                          const int64_t* in_len,
+                          const int64_t* output_offset,
+                          int naxis,
+                          const double* affine,
+                          const edhip_array* det0, int64_t det_batch_stride,
+                          uint32_t flags, void* hip_stream,
+                          char* err, size_t errlen);
+
+/*
+ * The adjoint of edhip_deform_jacobian: for L with ddet0 = dL / d det (the shape of det0, float32 / float64), and C(o)
+ * the cofactor matrix of J(o) (d det / dJ = C, also where det = 0),
+ *   ddisplacement0[h, j]     = sum_o ddet0[o] sum_l C[h,l](o) d_l beta_j(o)     (the gradient of the PREFILTERED grid)
+ *   dinverse_affine0[h, l<n] = sum_o ddet0[o] C[h,l](o),    dinverse_affine0[h, n] = 0.
+ *   ddisplacement0       NULL or displacement0's shape (EDHIP_ERR_INVALID), float32 / float64 (EDHIP_ERR_DTYPE).
+ *   dinverse_affine0     NULL or float64 (EDHIP_ERR_DTYPE) of shape (naxis, naxis + 1) (EDHIP_ERR_INVALID).
+ *                        Both NULL: EDHIP_ERR_INVALID.
+ * Grids of any size are served: a row is cut into units of at most 256 voxels, each reaching a window of the last
+ * axis' control points only, and a fine last axis takes more units a row.
+ * Every sum runs in fp64 in an order fixed by the shapes, without atomics: per piece of a row over x, then over the
+ * rows of a plane, then over the planes.  A repeated call, a graph replay and a sample of a batch give the bits of
+ * the single call.  Two to three launches.  Workspace, from the stream's cached scratch: per sample
+ * rows * nch * (naxis^2 w + naxis^2) doubles for nch units a row that reach at most w control points each (about
+ * naxis^2 (ncp_last + 7 nch) doubles a row), with three axes plus O_0 * (2 naxis ncp_1 ncp_2 + naxis^2) doubles: for
+ * 256^3, 27 MiB on a 5^3 grid, about 180 MB with 16 points along the last axis, 300 MB with 32, 520 MB with 64.  It
+ * stays cached with the stream until edhip_release_scratch.  The call enqueues on hip_stream
+ * and never synchronises; once a warm-up call has sized the workspace it can be captured into a HIP graph.
+ */
+int edhip_deform_jacobian_gradient(int nbatch,
+                                   const edhip_array* ddet0, int64_t ddet_batch_stride,
+                                   const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                   const int64_t* in_len,
+                                   const int64_t* output_offset,
+                                   int naxis,
+                                   const double* affine,
+                                   const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                   const edhip_array* dinverse_affine0, int64_t dinverse_affine_batch_stride,
+                                   uint32_t flags, void* hip_stream,
+                                   char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
