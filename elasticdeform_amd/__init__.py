@@ -34,6 +34,12 @@ autograd.
 folding check of a fitted field, without a coordinate volume), ``deform_grid_jacobian_gradient`` /
 ``deform_grid_jacobian_gradient_batch`` its adjoint with respect to the displacement and to affine, rotate and zoom:
 what a folding penalty, a log det or a volume-preservation term differentiates.
+``deform_grid_sample`` / ``deform_grid_sample_batch`` give the deformed image at arbitrary real output positions,
+``V_i = X(r(q_i))``, without deforming the volume: what a sampled registration metric, a read-out at landmarks or mesh
+vertices and any sparse loss on a deformed image need.  ``deform_grid_sample_gradient`` (the adjoint in the image),
+``deform_grid_sample_coordinate_gradient`` (``dL/dr`` per point) and ``deform_grid_sample_points_gradient`` (the
+positions, the displacement and affine / rotate / zoom), with their ``_batch`` forms, are its gradients;
+``elasticdeform_amd.torch.deform_grid_sample`` carries them through autograd.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
@@ -50,7 +56,10 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_inverse_displacement_gradient_batch, deform_grid_inverse_affine_gradient,
                           deform_grid_inverse_affine_gradient_batch, JacobianGradient, deform_grid_jacobian,
                           deform_grid_jacobian_gradient, deform_grid_jacobian_batch,
-                          deform_grid_jacobian_gradient_batch)
+                          deform_grid_jacobian_gradient_batch, deform_grid_sample, deform_grid_sample_batch,
+                          deform_grid_sample_gradient, deform_grid_sample_gradient_batch,
+                          deform_grid_sample_coordinate_gradient, deform_grid_sample_coordinate_gradient_batch,
+                          deform_grid_sample_points_gradient, deform_grid_sample_points_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

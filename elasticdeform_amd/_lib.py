@@ -56,7 +56,8 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_deform_displacement_gradient_batch_strided', 'edhip_deform_transform_gradient',
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
            'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient',
-           'edhip_deform_inverse_transform_gradient', 'edhip_deform_jacobian', 'edhip_deform_jacobian_gradient')
+           'edhip_deform_inverse_transform_gradient', 'edhip_deform_jacobian', 'edhip_deform_jacobian_gradient',
+           'edhip_deform_sample', 'edhip_deform_sample_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -225,6 +226,21 @@ def load():
             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_sample.restype = ctypes.c_int
+        L.edhip_deform_sample.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+            ctypes.POINTER(ctypes.c_double), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_sample_gradient.restype = ctypes.c_int
+        L.edhip_deform_sample_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+            ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p,
+            ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -536,6 +552,39 @@ def deform_inverse_transform_gradient(nbatch, in_desc, in_bstride, cot_desc, cot
           (int(nbatch), *_pairs(in_desc, in_bstride, cot_desc, cot_bstride, disp_desc, disp_bstride), lens, off,
            *_pairs(ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride), len(axis), ax, int(order), int(mode), aff, lin,
            int(max_iter), float(tol)), flags, stream)
+
+
+def deform_sample(nbatch, in_desc, in_bstride, pts_desc, pts_bstride, disp_desc, disp_bstride, in_len, output_offset,
+                  out_desc, out_bstride, inside_desc, inside_bstride, axis, order, mode, cval, inverse_affine, flags,
+                  stream):
+    """edhip_deform_sample: `in_desc` (the image, spline coefficients for order > 1; deformed extents `in_len`) gathered
+    at r(q) for the positions q of `pts_desc` (N, naxis) into `out_desc` (the input's non-deformed axes, one axis of N
+    points in the place of the first deformed axis); `inside_desc` (uint8 (N); None = not wanted): 1 where r lies inside
+    the input.  Sample 0's descriptors plus byte strides; `disp_desc` is the PREFILTERED control grid."""
+    lens, _lens = _ptr(in_len, numpy.int64)
+    ax, axis = _ptr(axis, numpy.int32)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_sample,
+          (int(nbatch), *_pairs(in_desc, in_bstride, pts_desc, pts_bstride, disp_desc, disp_bstride), lens, off,
+           *_pairs(out_desc, out_bstride, inside_desc, inside_bstride), len(axis), ax, int(order), int(mode),
+           float(cval), aff), flags, stream)
+
+
+def deform_sample_gradient(nbatch, in_desc, in_bstride, cot_desc, cot_bstride, pts_desc, pts_bstride, disp_desc,
+                           disp_bstride, in_len, output_offset, din_desc, din_bstride, dcoord_desc, dcoord_bstride, axis,
+                           order, mode, inverse_affine, flags, stream):
+    """edhip_deform_sample_gradient: for the cotangent `cot_desc` (the shape of deform_sample()'s output, float32 /
+    float64) the adjoint in the image ADDED into `din_desc` (the accumulator, the image's shape, the cotangent's dtype;
+    the caller zeroes it and applies the transposed prefilter afterwards) and / or dL/dr per point into `dcoord_desc`
+    (float64 (N, naxis); needs `in_desc`, the image's coefficients in the cotangent's dtype).  None = not given / not
+    wanted.  Sample 0's descriptors plus byte strides; `disp_desc` is the PREFILTERED control grid."""
+    lens, _lens = _ptr(in_len, numpy.int64)
+    ax, axis = _ptr(axis, numpy.int32)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_sample_gradient,
+          (int(nbatch), *_pairs(in_desc, in_bstride, cot_desc, cot_bstride, pts_desc, pts_bstride, disp_desc,
+                                disp_bstride), lens, off, *_pairs(din_desc, din_bstride, dcoord_desc, dcoord_bstride),
+           len(axis), ax, int(order), int(mode), aff), flags, stream)
 
 
 def source_box(disp_desc, in_len, out_len, output_offset, inverse_affine, flags, stream):

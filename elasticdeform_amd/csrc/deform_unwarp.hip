@@ -51,11 +51,10 @@ __device__ __forceinline__ void resample(const GridGeom& g, const UnwarpView& u,
     // reference arithmetic (x86-64, no FMA): keep the products and sums separate
 #pragma clang fp contract(off)
     const IOView& v = u.v;
-    const int order = v.order;
     double w[N][6];
     int64_t tap[N][6];                        // byte offsets of the taps on each deformed axis of Y
     bool constant, inside;
-    form_taps<N>(g, v, q, solved, w, tap, constant, inside);
+    form_taps<N>(g.out_len, v, q, solved, w, tap, constant, inside);
 
     int64_t out_vox = 0;
 #pragma unroll
@@ -70,40 +69,7 @@ __device__ __forceinline__ void resample(const GridGeom& g, const UnwarpView& u,
     }
 
     // every step (channel) of the voxel reuses q, the taps and the weights
-    const char* in_b = v.in + b * u.in_bstride;
-    char* out_b = v.out + b * u.out_bstride + out_vox;
-    for (int64_t ss = 0; ss < v.nsteps; ++ss) {
-        // step (non-deformed axes) offsets, first step axis fastest, deform.c:828-838 (the same for every thread)
-        int64_t in_off = 0, out_off = 0;
-        {
-            int64_t r = ss;
-            for (int l = 0; l < v.nstep; ++l) {
-                const int64_t d = r / v.step_len[l];
-                const int64_t c = r - d * v.step_len[l];
-                in_off += v.in_step_stride[l] * c;
-                out_off += v.out_step_stride[l] * c;
-                r = d;
-            }
-        }
-        double t = v.cval;
-        if (!constant) {
-            const char* base = in_b + in_off;
-            switch (v.in_dtype) {
-            case EDHIP_BOOL:
-            case EDHIP_U8: t = tap_sum<uint8_t, N>(base, order, tap, w); break;
-            case EDHIP_I8: t = tap_sum<int8_t, N>(base, order, tap, w); break;
-            case EDHIP_U16: t = tap_sum<uint16_t, N>(base, order, tap, w); break;
-            case EDHIP_I16: t = tap_sum<int16_t, N>(base, order, tap, w); break;
-            case EDHIP_U32: t = tap_sum<uint32_t, N>(base, order, tap, w); break;
-            case EDHIP_I32: t = tap_sum<int32_t, N>(base, order, tap, w); break;
-            case EDHIP_U64: t = tap_sum<uint64_t, N>(base, order, tap, w); break;
-            case EDHIP_I64: t = tap_sum<int64_t, N>(base, order, tap, w); break;
-            case EDHIP_F32: t = tap_sum<float, N>(base, order, tap, w); break;
-            default: t = tap_sum<double, N>(base, order, tap, w); break;      // float64 (the launcher admits no other)
-            }
-        }
-        store_forward(out_b + out_off, v.out_dtype, t);
-    }
+    gather_steps<N>(v, v.in + b * u.in_bstride, v.out + b * u.out_bstride + out_vox, tap, w, constant);
 }
 
 template <int N, bool LDS>

@@ -36,45 +36,6 @@ struct UnwarpGradView {
     int64_t nsrc;                             // prod I_k: the work size
 };
 
-// dz w_0 ... w_{N-1} added to the (order + 1)^N tap cells from deformed axis D on.  wo[k], k < D: the weight of the
-// current tap on the outer axes.
-template <int N, int D>
-__device__ __forceinline__ void scatter_rows(char* base, int order, bool f32, const int64_t (&tap)[N][6],
-                                             const double (&w)[N][6], double (&wo)[N], const double dz)
-{
-    if constexpr (D == N - 1) {
-#pragma unroll
-        for (int l = 0; l < 6; ++l) {
-            if (l <= order) {
-                double coeff = dz;
-                if (order > 0) {
-#pragma unroll
-                    for (int k = 0; k < D; ++k)
-                        coeff *= wo[k];
-                    coeff *= w[D][l];
-                }
-                if (f32)
-                    unsafeAtomicAdd((float*)(base + tap[D][l]), (float)coeff);
-                else
-                    unsafeAtomicAdd((double*)(base + tap[D][l]), coeff);
-            }
-        }
-    } else {
-        // rolled: the turn's weight and offset rotate through scalars (deform_unwarp.hip: tap_rows)
-        double w0 = w[D][0], w1 = w[D][1], w2 = w[D][2], w3 = w[D][3], w4 = w[D][4], w5 = w[D][5];
-        int64_t o0 = tap[D][0], o1 = tap[D][1], o2 = tap[D][2], o3 = tap[D][3], o4 = tap[D][4], o5 = tap[D][5];
-#pragma unroll 1
-        for (int l = 0; l <= order; ++l) {
-            wo[D] = w0;
-            scatter_rows<N, D + 1>(base + o0, order, f32, tap, w, wo, dz);
-            const double wr = w0;
-            const int64_t orot = o0;
-            w0 = w1, w1 = w2, w2 = w3, w3 = w4, w4 = w5, w5 = wr;
-            o0 = o1, o1 = o2, o2 = o3, o3 = o4, o4 = o5, o5 = orot;
-        }
-    }
-}
-
 template <int N, bool LDS>
 __global__ __launch_bounds__(kUnwarpThreads) void unwarp_grad_kernel(PointsArgs a, const UnwarpGradView u)
 {
@@ -89,7 +50,7 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_grad_kernel(PointsArgs 
     double w[N][6];
     int64_t tap[N][6];                        // byte offsets of the taps on each deformed axis of dY
     bool constant, inside;
-    form_taps<N>(a.g, v, q, solved, w, tap, constant, inside);
+    form_taps<N>(a.g.out_len, v, q, solved, w, tap, constant, inside);
     if (constant)
         return;                               // an empty row of A
 
@@ -100,29 +61,7 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_grad_kernel(PointsArgs 
         out_vox += v.out_stride[k] * o[k];
     char* in_b = const_cast<char*>(v.in) + b * u.in_bstride;
     const char* out_b = v.out + b * u.out_bstride + out_vox;
-    const bool f32 = v.in_dtype == EDHIP_F32;
-    // every step (channel) of the voxel reuses q, the taps and the weights
-    for (int64_t ss = 0; ss < v.nsteps; ++ss) {
-        // step (non-deformed axes) offsets, first step axis fastest (the same for every thread)
-        int64_t in_off = 0, out_off = 0;
-        {
-            int64_t r = ss;
-            for (int l = 0; l < v.nstep; ++l) {
-                const int64_t d = r / v.step_len[l];
-                const int64_t c = r - d * v.step_len[l];
-                in_off += v.in_step_stride[l] * c;
-                out_off += v.out_step_stride[l] * c;
-                r = d;
-            }
-        }
-        const double dz = f32 ? (double)*reinterpret_cast<const float*>(out_b + out_off)
-                              : *reinterpret_cast<const double*>(out_b + out_off);
-        double wo[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            wo[k] = 1.0;
-        scatter_rows<N, 0>(in_b + in_off, v.order, f32, tap, w, wo, dz);
-    }
+    scatter_steps<N>(v, in_b, out_b, tap, w);
 }
 
 template <int N>

@@ -50,65 +50,6 @@ struct UnwarpTgradView {
     double* q;                                // per sample (nsrc, N)
 };
 
-// spline_weight_derivatives for a constant order, all six slots written (weights_of_order's scheme)
-template <int ORDER>
-__device__ __forceinline__ void weight_derivatives_of_order(double c, double scale, double (&dw)[6])
-{
-    double tmp[ORDER + 1];
-    spline_weight_derivatives(c, ORDER, tmp);
-#pragma unroll
-    for (int l = 0; l < 6; ++l)
-        dw[l] = l <= ORDER ? tmp[l <= ORDER ? l : 0] * scale : 0.0;
-}
-__device__ __forceinline__ void weight_derivatives_by_order(double c, int order, double scale, double (&dw)[6])
-{
-    switch (order) {
-    case 1: weight_derivatives_of_order<1>(c, scale, dw); break;
-    case 2: weight_derivatives_of_order<2>(c, scale, dw); break;
-    case 3: weight_derivatives_of_order<3>(c, scale, dw); break;
-    case 4: weight_derivatives_of_order<4>(c, scale, dw); break;
-    case 5: weight_derivatives_of_order<5>(c, scale, dw); break;
-    default:                                  // order 0: the weight is constant
-#pragma unroll
-        for (int l = 0; l < 6; ++l)
-            dw[l] = 0.0;
-        break;
-    }
-}
-
-// sum_step dZ[step] * (the forward's tap sum with the weights w) over every step of the voxel
-template <int N>
-__device__ __forceinline__ double step_sums(const IOView& v, const char* in_b, const char* out_b,
-                                            const int64_t (&tap)[N][6], const double (&w)[N][6])
-{
-    const bool f32 = v.in_dtype == EDHIP_F32;
-    double acc = 0.0;
-    for (int64_t ss = 0; ss < v.nsteps; ++ss) {
-        // step (non-deformed axes) offsets, first step axis fastest (the same for every thread)
-        int64_t in_off = 0, out_off = 0;
-        {
-            int64_t r = ss;
-            for (int l = 0; l < v.nstep; ++l) {
-                const int64_t d = r / v.step_len[l];
-                const int64_t c = r - d * v.step_len[l];
-                in_off += v.in_step_stride[l] * c;
-                out_off += v.out_step_stride[l] * c;
-                r = d;
-            }
-        }
-        double dz, t;
-        if (f32) {
-            dz = (double)*reinterpret_cast<const float*>(out_b + out_off);
-            t = tap_sum<float, N>(in_b + in_off, v.order, tap, w);
-        } else {
-            dz = *reinterpret_cast<const double*>(out_b + out_off);
-            t = tap_sum<double, N>(in_b + in_off, v.order, tap, w);
-        }
-        acc += dz * t;
-    }
-    return acc;
-}
-
 template <int N, bool LDS>
 __global__ __launch_bounds__(kUnwarpThreads) void unwarp_tgrad_prepare(PointsArgs a, const UnwarpTgradView t)
 {
@@ -137,7 +78,7 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_tgrad_prepare(PointsArg
         double w[N][6];
         int64_t tap[N][6];                    // byte offsets of the taps on each deformed axis of Y
         bool constant, inside;
-        form_taps<N>(a.g, v, q, true, w, tap, constant, inside);
+        form_taps<N>(a.g.out_len, v, q, true, w, tap, constant, inside);
         contributes = !constant && sane_position<N>(a, q);
         if (contributes) {
             int64_t out_vox = 0;
@@ -147,21 +88,10 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_tgrad_prepare(PointsArg
             const char* in_b = v.in + b * t.in_bstride;
             const char* out_b = v.out + b * t.out_bstride + out_vox;
             double g[N];
+            coordinate_gradient<N>(a.g.out_len, v, q, in_b, out_b, tap, w, g);
 #pragma unroll
-            for (int h = 0; h < N; ++h) {
-                double keep[6];
-#pragma unroll
-                for (int l = 0; l < 6; ++l)
-                    keep[l] = w[h][l];
-                // (the coordinate form_taps took its window and weights at: not 'constant' outside, so it is m_h itself)
-                const double m = map_coordinate(q[h], a.g.out_len[h], v.mode);
-                weight_derivatives_by_order(m, v.order, map_coordinate_slope(q[h], a.g.out_len[h], v.mode), w[h]);
-                g[h] = step_sums<N>(v, in_b, out_b, tap, w);
-#pragma unroll
-                for (int l = 0; l < 6; ++l)
-                    w[h][l] = keep[l];
+            for (int h = 0; h < N; ++h)
                 cfinite = cfinite && isfinite(g[h]);
-            }
             // u = -J^-T g at the solved q (points_grad_prepare, inverse direction)
             int64_t tstride[N];
             int per = 0;

@@ -287,6 +287,29 @@ size_t inverse_tgrad_scratch_bytes(const GridGeom& g, int nbatch);
 hipError_t launch_deform_inverse_transform_gradient(const InverseCall& c, const BatchArray& ddisp, const BatchArray& dK,
                                                     char* scratch, hipStream_t stream);
 
+// The deformed image at real output positions (deform_sample.hip): per point q the coordinate r(q) of
+// launch_deform_points (forward direction) and the forward gather of `v.in` (X, deformed extents g.in_len) at r, for
+// every step.  One thread per point (grid-stride beyond kPointsMaxBlocks * 256), blockIdx.y = sample; no scratch, no
+// atomics, no synchronisation.  1 to 3 deformed axes, v.in_dtype == v.out_dtype, no 16-bit floats;
+// hipErrorNotSupported (nothing launched) otherwise.
+struct SampleCall {
+    GridGeom g;                   // g.disp: the prefiltered grid of sample 0; in_len = I (>= 2 each); out_len unused
+    IOView v;                     // sample 0: v.in = X (read, extents I); v.out = V (written; out_stride[0]: the byte
+                                  // stride of its point axis, the others unused); order, mode, cval
+                                  // (the gradient: v.in = the coefficients of X, read, or nullptr; v.out = dV, read)
+    int nbatch;
+    int64_t npts;
+    int64_t in_bstride, out_bstride, disp_bstride;   // bytes between samples
+    BatchArray pts;               // (npts, naxis) float32 / float64 (read)
+    BatchArray inside;            // uint8 (npts): 1 = a sane position with 0 <= r_k <= I_k - 1 on every axis
+};
+hipError_t launch_deform_sample(const SampleCall& c, hipStream_t stream);
+// Its gradients (deform_sample_grad.hip), the same front and taps per point, either or both per call: `acc` (X's
+// shape, float32 / float64, the cotangent's dtype) has A^T dV ADDED with float atomics; dcoord (float64 (npts, naxis))
+// gets the row g = dL/dr of its point, which needs v.in, the coefficients of X in the cotangent's dtype.
+hipError_t launch_deform_sample_gradient(const SampleCall& c, const IOView& acc, int64_t acc_bstride,
+                                         const BatchArray& dcoord, hipStream_t stream);
+
 // det J of the coordinate map on the voxel lattice and its adjoint (deform_jacobian.hip): rows along the last deformed
 // axis, the other axes contracted once per row; blockIdx.y = sample, fp64, no atomics.  1 to 3 deformed axes;
 // hipErrorNotSupported (nothing launched) otherwise.

@@ -1761,6 +1761,201 @@ int edhip_deform_inverse_transform_gradient(int nbatch, const edhip_array* input
     return EDHIP_OK;
 }
 
+// ---- the deformed image at real output positions (deform_sample.hip) and its gradients (deform_sample_grad.hip) -----
+// One X-shaped array `x` and one point-indexed array `p` (x's non-deformed axes, one axis of N points in the place of
+// the first deformed axis) as the kernels see them: v.in / in_* from x, v.out / out_* from p, out_stride[0] per point.
+static void make_sample_view(const edhip_array& x, const edhip_array& p, int naxis, const int32_t* axis, int order,
+                             int mode, double cval, ed::IOView& v)
+{
+    memset(&v, 0, sizeof(v));
+    v.in = (const char*)x.data;
+    v.out = (char*)p.data;
+    v.in_dtype = x.dtype;
+    v.out_dtype = p.dtype;
+    v.order = order;
+    v.mode = mode;
+    v.cval = cval;
+    v.nsteps = 1;
+    v.out_stride[0] = p.stride_bytes[axis[0]];
+    for (int d = 0; d < x.ndim; ++d) {
+        int k = -1;
+        for (int j = 0; j < naxis; ++j)
+            if (axis[j] == d)
+                k = j;
+        if (k >= 0) {
+            v.in_stride[k] = x.stride_bytes[d];
+        } else {
+            v.step_len[v.nstep] = x.shape[d];
+            v.in_step_stride[v.nstep] = x.stride_bytes[d];
+            v.out_step_stride[v.nstep] = p.stride_bytes[v.nstep + (d > axis[0] ? 1 : 0)];
+            v.nsteps *= x.shape[d];
+            v.nstep++;
+        }
+    }
+}
+
+// What edhip_deform_sample and edhip_deform_sample_gradient check and fill alike.  x0: the array of X's shape the
+// geometry is read from, called `x_name`; lattice0: output0 or cotangent0, called `lattice_name`.  float_only: float32 /
+// float64 arrays (the gradient); otherwise every dtype but the 16-bit floats.
+static int fill_sample_call(const char* entry, int nbatch, const edhip_array* x0, const char* x_name,
+                            const edhip_array* points0, int64_t points_batch_stride, const edhip_array* displacement0,
+                            int64_t displacement_batch_stride, const int64_t* in_len, const int64_t* output_offset,
+                            const edhip_array* lattice0, const char* lattice_name, int64_t lattice_batch_stride,
+                            int naxis, const int32_t* axis, int32_t order, int32_t mode, double cval,
+                            const double* affine, uint32_t flags, bool float_only, ed::SampleCall& c, char* err,
+                            size_t errlen)
+{
+    using namespace ed;
+    if (int st = check_batch_call(nbatch, x0 && points0 && displacement0 && lattice0 && in_len, err, errlen))
+        return st;
+    if (int st = check_axes_1_to_3(entry, axis, naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered(entry, flags, err, errlen))
+        return st;
+    const edhip_array& x = *x0;
+    const edhip_array& out = *lattice0;
+    if (x.ndim < 1 || x.ndim > EDHIP_MAX_DIMS)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "arrays must have 1..%d dimensions", EDHIP_MAX_DIMS);
+    for (int j = 0; j < naxis; ++j)
+        if (axis[j] < 0 || axis[j] >= x.ndim || (j > 0 && axis[j] <= axis[j - 1]))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "invalid axis in axis list");
+    if (order < 0 || order > 5)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "spline order not supported");
+    if (mode < 0 || mode > 4)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "boundary mode not supported");
+    if (!dtype_ok(x.dtype) || (float_only ? !f32_or_f64(&x) : (x.dtype == EDHIP_F16 || x.dtype == EDHIP_BF16)))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    if (out.dtype != x.dtype)
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "%s and %s must have one dtype", x_name, lattice_name);
+    for (int k = 0; k < naxis; ++k) {
+        if (x.shape[axis[k]] != in_len[k])
+            return fail(err, errlen, EDHIP_ERR_INVALID, "the %s's deformed axes must have the extents in_len", x_name);
+        if (in_len[k] < 2)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "deformed axes must have at least 2 elements");
+    }
+    if (points0->ndim != 2 || points0->shape[1] != naxis || points0->shape[0] < 0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "points must have shape (N, naxis)");
+    if (!f32_or_f64(points0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "points must be float32 or float64");
+    const int64_t npts = points0->shape[0];
+    {
+        // x's dimensions with the deformed axes replaced by one axis of N points at the place of the first
+        int64_t want[EDHIP_MAX_DIMS];
+        int nd = 0;
+        for (int d = 0; d < x.ndim; ++d) {
+            bool deformed = false;
+            for (int j = 0; j < naxis; ++j)
+                deformed = deformed || axis[j] == d;
+            if (d == axis[0])
+                want[nd++] = npts;
+            else if (!deformed)
+                want[nd++] = x.shape[d];
+        }
+        if (!has_shape(lattice0, nd, want))
+            return fail(err, errlen, EDHIP_ERR_INVALID,
+                        "%s must have the %s's non-deformed axes and one axis of N points", lattice_name, x_name);
+    }
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (int st = check_batch_limit(entry, nbatch, err, errlen))
+        return st;
+    memset(&c, 0, sizeof(c));
+    if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    make_sample_view(x, out, naxis, axis, order, mode, cval, c.v);
+    c.nbatch = nbatch;
+    c.npts = npts;
+    c.out_bstride = lattice_batch_stride;
+    c.disp_bstride = displacement_batch_stride;
+    c.pts = batch_array(points0, points_batch_stride);
+    return EDHIP_OK;
+}
+
+int edhip_deform_sample(int nbatch, const edhip_array* input0, int64_t input_batch_stride, const edhip_array* points0,
+                        int64_t points_batch_stride, const edhip_array* displacement0,
+                        int64_t displacement_batch_stride, const int64_t* in_len, const int64_t* output_offset,
+                        const edhip_array* output0, int64_t output_batch_stride, const edhip_array* inside0,
+                        int64_t inside_batch_stride, int naxis, const int32_t* axis, int32_t order, int32_t mode,
+                        double cval, const double* affine, uint32_t flags, void* hip_stream, char* err, size_t errlen)
+{
+    ed::SampleCall c;
+    if (int st = fill_sample_call("edhip_deform_sample", nbatch, input0, "input", points0, points_batch_stride,
+                                  displacement0, displacement_batch_stride, in_len, output_offset, output0, "output",
+                                  output_batch_stride, naxis, axis, order, mode, cval, affine, flags, false, c, err,
+                                  errlen))
+        return st;
+    if (inside0) {
+        if (!has_shape(inside0, 1, &c.npts))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "inside must have shape (N)");
+        if (inside0->dtype != EDHIP_U8)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "inside must be uint8");
+    }
+    if (nbatch == 0 || c.npts == 0 || c.v.nsteps <= 0)
+        return EDHIP_OK;
+    c.in_bstride = input_batch_stride;
+    c.inside = batch_array(inside0, inside_batch_stride);
+    const hipError_t e = ed::launch_deform_sample(c, (hipStream_t)hip_stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform sample launch");
+    return EDHIP_OK;
+}
+
+int edhip_deform_sample_gradient(int nbatch, const edhip_array* input0, int64_t input_batch_stride,
+                                 const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                 const edhip_array* points0, int64_t points_batch_stride,
+                                 const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                 const int64_t* in_len, const int64_t* output_offset, const edhip_array* dinput0,
+                                 int64_t dinput_batch_stride, const edhip_array* dcoordinate0,
+                                 int64_t dcoordinate_batch_stride, int naxis, const int32_t* axis, int32_t order,
+                                 int32_t mode, const double* affine, uint32_t flags, void* hip_stream, char* err,
+                                 size_t errlen)
+{
+    using namespace ed;
+    if (err && errlen)
+        err[0] = 0;
+    if (nbatch >= 0 && cotangent0 && points0 && displacement0 && in_len) {
+        if (!dinput0 && !dcoordinate0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "neither dinput nor dcoordinate is requested");
+        if (dcoordinate0 && !input0)
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dcoordinate needs the input");
+    }
+    // the geometry is read from the input, or from the accumulator when there is no input
+    const edhip_array* x0 = input0 ? input0 : dinput0;
+    SampleCall c;
+    if (int st = fill_sample_call("edhip_deform_sample_gradient", nbatch, x0, input0 ? "input" : "dinput", points0,
+                                  points_batch_stride, displacement0, displacement_batch_stride, in_len, output_offset,
+                                  cotangent0, "cotangent", cotangent_batch_stride, naxis, axis, order, mode, 0.0,
+                                  affine, flags, true, c, err, errlen))
+        return st;
+    IOView acc;
+    memset(&acc, 0, sizeof(acc));
+    if (dinput0) {
+        if (!has_shape(dinput0, x0->ndim, x0->shape))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinput must have the shape of the input");
+        if (dinput0->dtype != cotangent0->dtype)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinput and cotangent must have one dtype");
+        make_sample_view(*dinput0, *cotangent0, naxis, axis, order, mode, 0.0, acc);
+    }
+    if (dcoordinate0) {
+        const int64_t rows[2] = {c.npts, naxis};
+        if (!has_shape(dcoordinate0, 2, rows))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dcoordinate must have shape (N, naxis)");
+        if (dcoordinate0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dcoordinate must be float64");
+    }
+    if (nbatch == 0 || c.npts == 0 || c.v.nsteps <= 0)
+        return EDHIP_OK;
+    if (!input0)
+        c.v.in = nullptr;                     // (the view was read from the accumulator: only its shape counts)
+    c.in_bstride = input_batch_stride;
+    const hipError_t e = launch_deform_sample_gradient(c, acc, dinput_batch_stride,
+                                                       batch_array(dcoordinate0, dcoordinate_batch_stride),
+                                                       (hipStream_t)hip_stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform sample gradient launch");
+    return EDHIP_OK;
+}
+
 // ---- det J of the coordinate map on the voxel lattice and its adjoint (deform_jacobian.hip) -------------------------
 // What edhip_deform_jacobian and edhip_deform_jacobian_gradient check and fill alike.  lattice0: det (written) or ddet
 // (read), called `name` in the messages; its own dimensions are the deformed axes.

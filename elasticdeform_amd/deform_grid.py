@@ -1249,15 +1249,24 @@ def _list_or_one(results, extras, paired, like):
 
 def _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom):
     """(Plan of the image call on an array of X_shape, naxis, the leading dimensions of the points)"""
-    if batch and pts.ndim != 3:
-        raise ValueError("points should have shape (batch, N, naxis).")
+    _check_batch_points(pts, batch)
     plan = _plan_of(_shape_only(X_shape, pts.shape[0] if batch else None), batch, displacement, 3, 'constant', 0.0,
                     crop, axis, affine, rotate, zoom)
+    return (plan,) + _points_of_plan(pts, plan)
+
+
+def _check_batch_points(pts, batch):
+    if batch and pts.ndim != 3:
+        raise ValueError("points should have shape (batch, N, naxis).")
+
+
+def _points_of_plan(pts, plan):
+    """(naxis, the leading dimensions of the points), the points checked against the Plan's deformed axes"""
     n = plan.naxis
     if pts.ndim < 1 or int(pts.shape[-1]) != n:
         raise ValueError("The last dimension of the points should equal the number of deformed axes (%d), "
                          "but their shape is %s." % (n, str(tuple(pts.shape))))
-    return plan, n, tuple(int(v) for v in pts.shape[:-1])
+    return n, tuple(int(v) for v in pts.shape[:-1])
 
 
 def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, jacobian, max_iter, tol,
@@ -2163,3 +2172,282 @@ def deform_grid_inverse_affine_gradient_batch(Y, dZ, displacements, order=3, mod
     plan, _, dk = _inverse_transform_gradient(Y, dZ, displacements, order, mode, crop, prefilter, axis, affine, rotate,
                                               zoom, max_iter, tol, True, False, True)
     return _affine_result_batch(dk, plan, affine, rotate, zoom, isinstance(dZ, numpy.ndarray))
+
+
+# ---- the deformed image at real output positions (no counterpart in the reference) ---------------------------------
+
+def _sample_shapes(X_shape, count):
+    """X_shape as one shape per input: a single shape serves every input, a list of shapes is per input"""
+    if X_shape is None:
+        raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
+    per_input = isinstance(X_shape, list) and len(X_shape) > 0 and isinstance(X_shape[0], (tuple, list))
+    shapes = [tuple(int(v) for v in s) for s in X_shape] if per_input else [tuple(int(v) for v in X_shape)] * count
+    assert len(shapes) == count, 'Number of X_shape parameters should be equal to number of inputs.'
+    return shapes
+
+
+def _sample_host(X, dV, positions, displacement, X_shape, order, mode, cval, crop, prefilter, axis, affine, rotate,
+                 zoom, return_inside, batch, want):
+    """The host path of deform_grid_sample (`want` 'value': X given), of deform_grid_sample_gradient ('input': dV and
+    X_shape given, the result has the shape of X) and of deform_grid_sample_coordinate_gradient ('coordinate': X and dV
+    given, the result is g = dL/dr summed over the inputs), single call and batch.  Every argument check runs before
+    the device is touched; offsets, the inverse map K and the rotate / zoom centre are those of the image call on X
+    (the same Plan), and `crop` only sets the offset and that centre, as in deform_grid_coordinates.  Returns
+    (plan, result)."""
+    lead_array = X if want != 'input' else dV
+    if batch and (not _host.is_array(lead_array) or lead_array.ndim < 2):
+        raise Exception('%s should be an array with a leading batch axis.' % ('X' if want != 'input' else 'dV'))
+    Xs = None if want == 'input' else ([X] if batch else _host.normalize_inputs(X))
+    dVs = None if want == 'value' else ([dV] if batch else _host.normalize_inputs(dV))
+    count = len(Xs if Xs is not None else dVs)
+    nb = int(lead_array.shape[0]) if batch else None
+    if Xs is not None:
+        X_shapes = [tuple(int(v) for v in x.shape[1 if batch else 0:]) for x in Xs]
+    else:
+        X_shapes = _sample_shapes(X_shape, count)
+    pts = _as_points(positions)
+    _check_batch_points(pts, batch)
+    stand_ins = _shape_only(X_shapes[0], nb) if batch else [_host.ShapeOnly(s) for s in X_shapes]
+    plan = _plan_of(stand_ins, batch, displacement, order, mode, cval, crop, axis, affine, rotate, zoom)
+    n, lead = _points_of_plan(pts, plan)
+    if batch and lead[0] != nb:
+        raise ValueError("positions should have one set of points per sample (%d), but their shape is %s."
+                         % (nb, str(tuple(pts.shape))))
+    if n > 3:
+        raise RuntimeError('deform_grid_sample takes 1 to 3 deformed axes')    # (the library's own limit)
+    # the result of input i: its non-deformed axes in their order, then the leading dimensions of the positions
+    steps = [tuple(v for d, v in enumerate(s) if d not in plan.axis[i]) for i, s in enumerate(X_shapes)]
+    plead = lead[1:] if batch else lead
+    v_shapes = [((nb,) if batch else ()) + st + plead for st in steps]
+    if dVs is not None:
+        if len(dVs) != count:
+            raise ValueError("dV should have one array per input.")
+        got = [tuple(int(v) for v in d.shape) for d in dVs]
+        if got != v_shapes:
+            raise ValueError("dV does not match X and the positions. Expected shape of dV is %s, but %s given."
+                             % (str(v_shapes), str(got)))
+        _check_float_volumes(dVs)
+        if Xs is not None:
+            _check_float_volumes(Xs)                          # (the derivative of an integer image's rounded value)
+    elif any(name not in _lib.DTYPE_CODES or name in _lib.REDUCED_DTYPES for name in map(_volume_dtype_name, Xs)):
+        raise RuntimeError('data type not supported')         # complex, 16-bit floats
+    bl = (nb,) if batch else ()
+    torch = _torch()
+
+    if any(int(d) == 1 for d in plan.deform_shape):
+        # a deformed axis of length 1: the image call maps every voxel to the constant and no coordinate is defined
+        if want == 'value':
+            Vs = [_constant_result(x, s, c) for x, s, c in zip(Xs, v_shapes, plan.cval)]
+            ins = [_fill(pts, lead, False, 'bool')] * count
+            return plan, _list_or_one(Vs, ins, return_inside, X)
+        if want == 'input':
+            return plan, _list_or_one([_fill(d, bl + s, 0.0) for d, s in zip(dVs, X_shapes)], None, False, dV)
+        return plan, _fill(pts, lead + (n,), 0.0, 'float64')
+
+    K = plan.inverse_affine
+    deformed = tuple(int(v) for v in plan.deform_shape)
+    device = _device_for([pts, displacement] + list(Xs if Xs is not None else dVs))
+    results, insides, g_sum = [], [], None
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        pd = _to_device(pts, device)
+        pd = pd if batch else pd.reshape(-1, n)
+        npts = int(pd.shape[-2])
+        df = _prefiltered_grid(_to_device(displacement, device), batch, device, stream)
+        for i in range(count):
+            o = int(plan.order[i])
+            ax = plan.axis[i]
+            filter_axes = ([d + 1 for d in ax] if batch else list(ax)) if prefilter and o > 1 else []
+            point_axis = int(ax[0]) + (1 if batch else 0)     # where the library wants the points among V's dimensions
+            flat = bl + steps[i] + (npts,)
+
+            def lattice(t):
+                return t.reshape(flat).movedim(-1, point_axis)
+            xf = zd = None
+            if Xs is not None:
+                xd = _to_device(Xs[i], device)
+            if dVs is not None:
+                zd = _to_device(dVs[i], device)
+            if want == 'coordinate' and xd.dtype != zd.dtype:  # (the arithmetic is fp64 whatever the dtype)
+                xd, zd = xd.to(torch.float64), zd.to(torch.float64)
+            if Xs is not None:
+                # X is prepared as deform_grid prepares its input: filtered along its deformed axes
+                xf = _filter_axes(xd, filter_axes, o, False, device, stream=stream)
+            if want == 'value':
+                out = torch.empty(flat, dtype=xd.dtype, device=device)
+                ok = torch.empty(bl + (npts,), dtype=torch.uint8, device=device) if return_inside else None
+                _lib.deform_sample(nb if batch else 1, *_sample(xf, batch), *_sample(pd, batch), *_sample(df, batch),
+                                   deformed, plan.output_offset, *_sample(lattice(out), batch), *_sample(ok, batch),
+                                   ax, o, int(plan.mode[i]), float(plan.cval[i]), K, 0, stream)
+                results.append(_from_device(out.reshape(v_shapes[i]), Xs[i]))
+                insides.append(_from_device(ok.reshape(lead).to(torch.bool), pts) if ok is not None else None)
+            elif want == 'input':
+                acc = torch.zeros(bl + X_shapes[i], dtype=zd.dtype, device=device)
+                _lib.deform_sample_gradient(nb if batch else 1, None, 0, *_sample(lattice(zd), batch),
+                                            *_sample(pd, batch), *_sample(df, batch), deformed, plan.output_offset,
+                                            *_sample(acc, batch), None, 0, ax, o, int(plan.mode[i]), K, 0, stream)
+                acc = _filter_axes(acc, filter_axes, o, True, device, overwrite=True, stream=stream)
+                results.append(_from_device(acc, dVs[i]))
+            elif o > 0:                                       # (order 0 is piecewise constant in r: it adds nothing)
+                g = torch.empty(bl + (npts, n), dtype=torch.float64, device=device)
+                _lib.deform_sample_gradient(nb if batch else 1, *_sample(xf, batch), *_sample(lattice(zd), batch),
+                                            *_sample(pd, batch), *_sample(df, batch), deformed, plan.output_offset,
+                                            None, 0, *_sample(g, batch), ax, o, int(plan.mode[i]), K, 0, stream)
+                g_sum = g if g_sum is None else g_sum + g     # the inputs' rows are added in fp64 in input order
+        if want == 'coordinate':
+            if g_sum is None:
+                g_sum = torch.zeros(bl + (npts, n), dtype=torch.float64, device=device)
+            return plan, _from_device(g_sum.reshape(lead + (n,)), pts)
+    if want == 'value':
+        return plan, _list_or_one(results, insides, return_inside, X)
+    return plan, _list_or_one(results, None, False, dV)
+
+
+def _sample_run(X, positions, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                return_inside, batch):
+    return _sample_host(X, None, positions, displacement, None, order, mode, cval, crop, prefilter, axis, affine,
+                        rotate, zoom, return_inside, batch, 'value')[1]
+
+
+def deform_grid_sample(X, positions, displacement, order=3, mode='constant', cval=0.0, crop=None, prefilter=True,
+                       axis=None, affine=None, rotate=None, zoom=None, return_inside=False):
+    """
+    The deformed image at arbitrary real output positions: ``V_i = X(r(q_i))``, the piece that joins the image side
+    (:func:`deform_grid`) to the point side (:func:`deform_grid_coordinates`).  ``positions`` (shape ``(..., naxis)``)
+    are real, crop-local output positions ``q`` of
+    ``deform_grid(X, displacement, crop=crop, axis=axis, affine=affine, rotate=rotate, zoom=zoom)``:
+
+    * ``r(q)`` is exactly what :func:`deform_grid_coordinates` returns (fp64, no boundary mode);
+    * ``V = S_X(r(q))``, interpolated with the spline ``order``, boundary ``mode`` and ``cval`` the way ``deform_grid``
+      interpolates its input at a source coordinate (orders 0-5, the five legacy modes; in fp64, stored with
+      ``deform_grid``'s rounding rules for integer types).  With ``mode='constant'`` a coordinate outside ``X`` gives
+      ``cval``;
+    * a position that is not finite (or absurdly far out) gives ``cval`` in every mode.
+
+    At integer ``q`` this is the voxel ``deform_grid`` computes, to the rounding of the coordinate (about 1e-10 voxels).
+    A sampled registration metric, a read-out at landmarks or mesh vertices, sub-voxel patches and any sparse loss on a
+    deformed image need this: a few thousand points cost a few thousand gathers, not a full-volume warp.
+
+    The result has ``X``'s non-deformed axes in their order, followed by ``positions.shape[:-1]`` -- an input
+    ``(C, z, y, x)`` with ``axis=(1, 2, 3)`` and ``(N, 3)`` positions gives ``(C, N)`` -- and ``X``'s dtype.
+    ``return_inside=True`` returns ``(V, inside)``: ``inside`` (bool, ``positions.shape[:-1]``) is True exactly where
+    the position is sane and ``0 <= r_k <= I_k - 1`` on every axis, where ``V`` is interpolated from inside ``X``;
+    sampled metrics drop the other samples.
+
+    ``X``: an array or a list of arrays that share the positions (a list gives a list, of pairs with
+    ``return_inside``; ``order``, ``mode``, ``cval`` and ``axis`` may then be per-input lists as in
+    :func:`deform_grid_inverse`: an image at order 3 and its label map at order 0); 1 to 3 deformed axes; float32,
+    float64, integer and bool arrays (16-bit floats raise ``RuntimeError('data type not supported')``).
+    ``prefilter=True`` filters ``X`` along its deformed axes for ``order > 1``, as deform_grid prepares its input.
+    ``crop`` only sets the offset and the centre of ``rotate`` / ``zoom``, as in :func:`deform_grid_coordinates`.
+    float32 / float64 positions; integer positions are taken as float64.  A deformed axis of length 1 gives ``cval``
+    and nothing inside.  numpy in gives numpy out, tensors stay on their device.  One launch per input, one thread per
+    point; the same bits for a repeated call, a slice or a permutation of the positions.  No autograd flows through
+    this call itself: :func:`deform_grid_sample_gradient`, :func:`deform_grid_sample_coordinate_gradient` and
+    :func:`deform_grid_sample_points_gradient` are its gradients and ``elasticdeform_amd.torch.deform_grid_sample``
+    the differentiable wrapper.
+    """
+    return _sample_run(X, positions, displacement, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                       return_inside, False)
+
+
+def deform_grid_sample_batch(X, positions, displacements, order=3, mode='constant', cval=0.0, crop=None,
+                             prefilter=True, axis=None, affine=None, rotate=None, zoom=None, return_inside=False):
+    """:func:`deform_grid_sample` over a batch with one control grid per sample (:func:`deform_grid_batch`): ``X``
+    ``(B, ...)``, ``positions`` ``(B, N, naxis)``, ``displacements`` ``(B, naxis, n_0, ...)``, ``axis`` counts the axes
+    of one sample; everything else is shared.  The result is ``(B, non-deformed axes..., N)``.  One launch for the
+    batch; sample b equals the single call on sample b, bit for bit."""
+    return _sample_run(X, positions, displacements, order, mode, cval, crop, prefilter, axis, affine, rotate, zoom,
+                       return_inside, True)
+
+
+def deform_grid_sample_gradient(dV, positions, displacement, X_shape, order=3, mode='constant', crop=None,
+                                prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid_sample` with respect to ``X``: for ``L`` with ``dV = dL / dV`` (the shape of the
+    forward's result, float32 / float64) returns ``dL / dX`` of shape ``X_shape`` in ``dV``'s dtype.  For fixed
+    positions and deformation and ``cval = 0`` the call is linear in ``X``, ``V_i = sum_j A[i, j] Xf[j]`` with ``Xf``
+    the prefiltered ``X`` and the row ``A[i, :]`` the ``(order + 1)^naxis`` tap-weight products at ``r(q_i)``; the row
+    is empty where the position is not finite and where ``mode='constant'`` and ``r`` lies outside ``X``.  The result
+    is ``P^T A^T dV`` (``P^T``: the transposed prefilter, ``order > 1`` and ``prefilter=True``): the exact adjoint.
+    The products are formed in fp64 and added with float atomics in ``dV``'s dtype: which cell receives what is fixed,
+    the order of the adds is not, so the last bits may differ between two calls (the caveat of
+    :func:`deform_grid_inverse_gradient`); order 0 with integer-valued ``dV`` is exact and reproducible.  ``dV`` may be
+    a list (``X_shape`` then one shape or a list of shapes; per-input ``order`` / ``mode`` / ``axis`` lists).
+    """
+    return _sample_host(None, dV, positions, displacement, X_shape, order, mode, 0.0, crop, prefilter, axis, affine,
+                        rotate, zoom, False, False, 'input')[1]
+
+
+def deform_grid_sample_gradient_batch(dV, positions, displacements, X_shape, order=3, mode='constant', crop=None,
+                                      prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_sample_gradient` over a batch (:func:`deform_grid_sample_batch`): ``dV`` ``(B, ...)``,
+    ``X_shape`` the shape of ONE sample; returns ``(B,) + X_shape``.  Sample b equals the single call on sample b up
+    to the order of the float adds."""
+    return _sample_host(None, dV, positions, displacements, X_shape, order, mode, 0.0, crop, prefilter, axis, affine,
+                        rotate, zoom, False, True, 'input')[1]
+
+
+def deform_grid_sample_coordinate_gradient(X, dV, positions, displacement, order=3, mode='constant', crop=None,
+                                           prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid_sample` with respect to the coordinate the image is sampled at: ``g = dL / dr`` per
+    point, with the shape of ``positions``, float64.  ``g_h = sum_step dV[step] m'_h sum_k C[k, step] w'_h prod_{e != h}
+    w_e``: the spatial derivative of the spline interpolant of ``X`` at ``r(q)`` through the boundary ``mode`` (``X``
+    prefiltered as the forward prefilters it).  Where ``'nearest'`` clamps an axis that component is 0; at order 1 the
+    derivative at an integer coordinate is the one-sided one of the window the forward picks; ``order=0`` gives exact
+    zeros, as do a position that is not finite and, with ``mode='constant'``, a coordinate outside ``X``.  ``X`` and
+    ``dV``: float32 / float64 arrays or lists of them (the rows of a list's inputs are added in input order); integer
+    images raise ``RuntimeError('data type not supported')``.  A row depends on its point alone: the same bits on
+    every call, in a batch and after any permutation of the points.
+    """
+    return _sample_host(X, dV, positions, displacement, None, order, mode, 0.0, crop, prefilter, axis, affine, rotate,
+                        zoom, False, False, 'coordinate')[1]
+
+
+def deform_grid_sample_coordinate_gradient_batch(X, dV, positions, displacements, order=3, mode='constant', crop=None,
+                                                 prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_sample_coordinate_gradient` over a batch (:func:`deform_grid_sample_batch`); returns
+    ``(B, N, naxis)``, sample b the same bits as the single call on sample b."""
+    return _sample_host(X, dV, positions, displacements, None, order, mode, 0.0, crop, prefilter, axis, affine, rotate,
+                        zoom, False, True, 'coordinate')[1]
+
+
+def _sample_points_gradient(X, dV, positions, displacement, order, mode, crop, prefilter, axis, affine, rotate, zoom,
+                            batch, want_points=True, want_disp=True, want_map=True):
+    """g = dL/dr, then the adjoint of the coordinate map with g as the cotangent (_points_gradient): the returns of
+    _points_gradient.  The coordinate map is that of the first input (a list's inputs share their deformed extents)."""
+    if want_map and zoom is not None and float(zoom) == 0:
+        raise ValueError("zoom=0 means 'no zoom' (as in the reference): it has no gradient")
+    plan, g = _sample_host(X, dV, positions, displacement, None, order, mode, 0.0, crop, prefilter, axis, affine,
+                           rotate, zoom, False, batch, 'coordinate')
+    first = X if batch else _host.normalize_inputs(X)[0]
+    return _points_gradient(positions, g, displacement, tuple(int(v) for v in first.shape[1 if batch else 0:]), crop,
+                            tuple(int(a) for a in plan.axis[0]), affine, rotate, zoom, False, batch,
+                            want_points=want_points, want_disp=want_disp, want_map=want_map)
+
+
+def deform_grid_sample_points_gradient(X, dV, positions, displacement, order=3, mode='constant', crop=None,
+                                       prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient of :func:`deform_grid_sample` with respect to the positions and the deformation: returns
+    ``PointsGradient(points, displacement, affine, rotate, zoom, inverse_map)`` as
+    :func:`deform_grid_coordinates_gradient` does, for the cotangent ``g`` of
+    :func:`deform_grid_sample_coordinate_gradient` -- ``points`` is ``J^T g`` per position, ``displacement`` the
+    gradient of the control grid (its order-3 prefilter included), the other fields those of :class:`AffineGradient`.
+    This is what a sampled registration metric differentiates.  The sums over the points are the 64-bit fixed-point
+    sums of :func:`deform_grid_coordinates_gradient`: the same bits on every call and after any permutation of the
+    points.
+    """
+    plan, rows, ddisp, dk = _sample_points_gradient(X, dV, positions, displacement, order, mode, crop, prefilter, axis,
+                                                    affine, rotate, zoom, False)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray), False)
+
+
+def deform_grid_sample_points_gradient_batch(X, dV, positions, displacements, order=3, mode='constant', crop=None,
+                                             prefilter=True, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_sample_points_gradient` over a batch (:func:`deform_grid_sample_batch`); shapes and the
+    summed fields as for :func:`deform_grid_coordinates_gradient_batch`."""
+    plan, rows, ddisp, dk = _sample_points_gradient(X, dV, positions, displacements, order, mode, crop, prefilter, axis,
+                                                    affine, rotate, zoom, True)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray), True)

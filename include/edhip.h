@@ -731,6 +731,99 @@ int edhip_deform_jacobian_gradient(int nbatch,
                                    char* err, size_t errlen);
 
 /*
+ * The deformed image at arbitrary real output positions (deform_sample.hip; no counterpart in the reference): what
+ * joins edhip_deform to edhip_deform_points.  q is a real, crop-local output position of an edhip_deform call with the
+ * same control grid, crop offset and inverse map.
+ *   r(q)          exactly what edhip_deform_points(inverse = 0) returns: the same device code, fp64, no boundary map.
+ *   V[i, step]  = S_X(r(q_i))[step], S_X the gather edhip_deform applies to its input at a source coordinate, on the
+ *                 array X = input0 with the deformed extents in_len (the code edhip_deform_inverse runs on Y):
+ *                 map_coordinate of `mode` per axis, the (order + 1)-wide window with mirrored edge taps,
+ *                 spline_weights, the fp64 tap sum in the reference's tap order with no FMA (deform.c:841-924) and the
+ *                 per-dtype store.  A 'constant' coordinate outside [0, I_k - 1] gives cval.  A position that is not
+ *                 finite, or so far out that |control coordinate| >= 4e15, gives cval in EVERY mode and contributes
+ *                 nothing to any gradient.
+ *   inside[i]     1 exactly when the position is sane and 0 <= r_k <= I_k - 1 on every axis, else 0.
+ * At integer q this is the voxel edhip_deform computes, to the rounding of the coordinate: the points code and the
+ * image kernels agree to about 1e-10 there, so the values are equal within that times the interpolant's slope, not
+ * bit-equal.
+ * The batch is described once: sample b's input, points, control grid, output and inside are sample 0's moved by
+ * b * stride bytes (nbatch = 1: a single call); everything else is shared.
+ *   input0               X: any dtype but the 16-bit floats (EDHIP_ERR_DTYPE), any strides; spline coefficients when
+ *                        order > 1 (the caller prefilters, as for edhip_deform).
+ *   points0              (N, naxis), float32 / float64 (EDHIP_ERR_DTYPE), any strides.
+ *   displacement0        the PREFILTERED control grid (naxis, ncp_0, ...), any dtype / strides.
+ *                        EDHIP_FLAG_RAW_DISPLACEMENT is refused (EDHIP_ERR_INVALID).
+ *   in_len               host int64[naxis]: the deformed extents of input0 (>= 2 each: EDHIP_ERR_INVALID).
+ *   output0              V: input0's dtype (EDHIP_ERR_DTYPE); input0's dimensions with the deformed axes replaced by
+ *                        ONE axis of length N at the position of the first deformed axis (EDHIP_ERR_INVALID), any
+ *                        strides.
+ *   inside0              NULL, or uint8 (EDHIP_ERR_DTYPE) of shape (N) (EDHIP_ERR_INVALID).
+ *   naxis, axis          1 to 3 deformed axes of input0 (more: EDHIP_ERR_UNSUPPORTED), ascending.
+ *   order, mode, cval    0..5, enum edhip_mode, the constant.
+ *   output_offset, affine  as for edhip_deform: the forward call's own.
+ * nbatch <= 65535 (EDHIP_ERR_UNSUPPORTED).  N == 0 or nbatch == 0 launches nothing.  Every shape, dtype and flag check
+ * answers before any launch.  One launch, one thread per point (a grid-stride loop beyond 2048 * 256 points a sample),
+ * the control grid in LDS up to 7680 values; no atomics and no workspace: a point's result depends on that point and
+ * the call's arguments alone (a sample of a batch, a slice or permutation of the points and a repeated call give the
+ * same bits).  The call enqueues on hip_stream, never synchronises, never reads the environment and can be captured
+ * into a HIP graph.
+ */
+int edhip_deform_sample(int nbatch,
+                        const edhip_array* input0, int64_t input_batch_stride,
+                        const edhip_array* points0, int64_t points_batch_stride,
+                        const edhip_array* displacement0, int64_t displacement_batch_stride,
+                        const int64_t* in_len,
+                        const int64_t* output_offset,
+                        const edhip_array* output0, int64_t output_batch_stride,
+                        const edhip_array* inside0, int64_t inside_batch_stride,
+                        int naxis, const int32_t* axis,
+                        int32_t order, int32_t mode, double cval,
+                        const double* affine,
+                        uint32_t flags, void* hip_stream,
+                        char* err, size_t errlen);
+
+/*
+ * The gradients of edhip_deform_sample (deform_sample_grad.hip) for L = sum_{i, step} cotangent0[i, step] V[i, step]:
+ * the same front and the same taps per point, two optional results per call.
+ *   dinput0       A^T dV ADDED into the accumulator, A the matrix of the call for fixed positions and deformation
+ *                 (row i: the (order + 1)^naxis tap-weight products at r(q_i), folded taps added up; empty where the
+ *                 position is not sane or the mode is 'constant' and r lies outside X).  Products in fp64, rounded
+ *                 once, device-scope float atomics in the accumulator's type.  The caller zeroes dinput0 beforehand
+ *                 and applies the transposed prefilter afterwards, as for edhip_deform_inverse_gradient; the caveat is
+ *                 the same: the cells are fixed, the order in which the adds arrive is not.
+ *   dcoordinate0  g_h(i) = sum_step cotangent0[i, step] m'_h sum_k C[k, step] w'_h prod_{e != h} w_e = dL/dr_h, a
+ *                 plain store of an fp64 row per point (C = input0, the coefficients of X; m'_h the slope of the
+ *                 boundary map: 0 where 'nearest' clamps; at a window change the one-sided derivative of the chosen
+ *                 window; exact zeros at order 0 and for a point that contributes nothing).  Deterministic: a row
+ *                 depends on its point alone.
+ * The gradients with respect to the positions, the control grid and the inverse map are
+ * edhip_deform_points_gradient(inverse = 0) with dcoordinate0 as the cotangent.
+ * Arguments as for edhip_deform_sample, except:
+ *   input0               NULL, or the coefficients of X: cotangent0's dtype (EDHIP_ERR_DTYPE).  Required with
+ *                        dcoordinate0 (EDHIP_ERR_INVALID).  The shape of X is taken from it, or from dinput0.
+ *   cotangent0           dV, read: float32 / float64 (EDHIP_ERR_DTYPE), the shape of output0 (EDHIP_ERR_INVALID).
+ *   dinput0              NULL, or the accumulator: cotangent0's dtype (EDHIP_ERR_DTYPE), the shape of X.
+ *   dcoordinate0         NULL, or float64 (EDHIP_ERR_DTYPE) of shape (N, naxis) (EDHIP_ERR_INVALID).
+ *                        Both NULL: EDHIP_ERR_INVALID.
+ *   (no inside0, no cval)
+ * One launch, no workspace, no synchronisation; can be captured into a HIP graph.
+ */
+int edhip_deform_sample_gradient(int nbatch,
+                                 const edhip_array* input0, int64_t input_batch_stride,
+                                 const edhip_array* cotangent0, int64_t cotangent_batch_stride,
+                                 const edhip_array* points0, int64_t points_batch_stride,
+                                 const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                 const int64_t* in_len,
+                                 const int64_t* output_offset,
+                                 const edhip_array* dinput0, int64_t dinput_batch_stride,
+                                 const edhip_array* dcoordinate0, int64_t dcoordinate_batch_stride,
+                                 int naxis, const int32_t* axis,
+                                 int32_t order, int32_t mode,
+                                 const double* affine,
+                                 uint32_t flags, void* hip_stream,
+                                 char* err, size_t errlen);
+
+/*
  * Frees the scratch workspaces the library caches per (device, stream): per-call tables, spill
  * lists, the fp64 line buffers of the exact prefilter and the dense temporary of the order-4/5
  * cascade (up to the size of the largest array filtered that way).  Waits for the owning devices to
