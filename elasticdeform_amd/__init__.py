@@ -40,6 +40,12 @@ vertices and any sparse loss on a deformed image need.  ``deform_grid_sample_gra
 ``deform_grid_sample_coordinate_gradient`` (``dL/dr`` per point) and ``deform_grid_sample_points_gradient`` (the
 positions, the displacement and affine / rotate / zoom), with their ``_batch`` forms, are its gradients;
 ``elasticdeform_amd.torch.deform_grid_sample`` carries them through autograd.
+``deform_grid_derivatives`` / ``deform_grid_derivatives_batch`` give the local differential structure of the coordinate
+map at arbitrary real positions: ``r``, ``J = dr/dq`` and ``H = d^2r/dq dq`` (1 to 3 deformed axes);
+``deform_grid_derivatives_gradient`` / ``deform_grid_derivatives_gradient_batch`` are the adjoint of all three with
+respect to the positions, the displacement and affine / rotate / zoom, and
+``elasticdeform_amd.torch.deform_grid_derivatives`` carries them through autograd: one call for every local
+regulariser -- folding, log det, volume preservation, rigidity, diffusion, bending energy -- at sampled positions.
 """
 from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,  # noqa: F401
                           deform_grid_batch, deform_grid_gradient_batch, set_arithmetic,
@@ -59,7 +65,9 @@ from .deform_grid import (deform_grid, deform_grid_gradient, deform_random_grid,
                           deform_grid_jacobian_gradient_batch, deform_grid_sample, deform_grid_sample_batch,
                           deform_grid_sample_gradient, deform_grid_sample_gradient_batch,
                           deform_grid_sample_coordinate_gradient, deform_grid_sample_coordinate_gradient_batch,
-                          deform_grid_sample_points_gradient, deform_grid_sample_points_gradient_batch)
+                          deform_grid_sample_points_gradient, deform_grid_sample_points_gradient_batch,
+                          MapDerivatives, deform_grid_derivatives, deform_grid_derivatives_batch,
+                          deform_grid_derivatives_gradient, deform_grid_derivatives_gradient_batch)
 
 from ._lib import release_scratch  # noqa: F401,E402  (frees the library's cached device scratch)
 

@@ -57,7 +57,8 @@ EXPORTS = ('edhip_version', 'edhip_status_string', 'edhip_device_count', 'edhip_
            'edhip_deform_transform_gradient_batch_strided', 'edhip_deform_points', 'edhip_deform_labels',
            'edhip_deform_points_gradient', 'edhip_deform_inverse', 'edhip_deform_inverse_gradient',
            'edhip_deform_inverse_transform_gradient', 'edhip_deform_jacobian', 'edhip_deform_jacobian_gradient',
-           'edhip_deform_sample', 'edhip_deform_sample_gradient')
+           'edhip_deform_sample', 'edhip_deform_sample_gradient', 'edhip_deform_points_derivatives',
+           'edhip_deform_points_derivatives_gradient')
 
 
 class EdhipArray(ctypes.Structure):
@@ -187,6 +188,22 @@ def load():
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
             ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p,
             ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_points_derivatives.restype = ctypes.c_int
+        L.edhip_deform_points_derivatives.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray),
+            ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p,
+            ctypes.c_char_p, ctypes.c_size_t]
+        L.edhip_deform_points_derivatives_gradient.restype = ctypes.c_int
+        L.edhip_deform_points_derivatives_gradient.argtypes = [
+            ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+            ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
+            ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_char_p,
+            ctypes.c_size_t]
         L.edhip_deform_labels.restype = ctypes.c_int
         L.edhip_deform_labels.argtypes = [
             ctypes.c_int, ctypes.POINTER(EdhipArray), ctypes.c_int64, ctypes.POINTER(EdhipArray), ctypes.c_int64,
@@ -484,6 +501,34 @@ def deform_jacobian_gradient(nbatch, ddet_desc, ddet_bstride, disp_desc, disp_bs
     _call(load().edhip_deform_jacobian_gradient,
           (int(nbatch), *_pairs(ddet_desc, ddet_bstride, disp_desc, disp_bstride), lens, off, len(in_len), aff,
            *_pairs(ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride)), flags, stream)
+
+
+def deform_points_derivatives(nbatch, pts_desc, pts_bstride, disp_desc, disp_bstride, in_len, output_offset,
+                              inverse_affine, res_desc, res_bstride, jac_desc, jac_bstride, hess_desc, hess_bstride,
+                              flags, stream):
+    """edhip_deform_points_derivatives: r(q) at the points into `res_desc`, J = dr/dq into `jac_desc` (float64
+    (N, naxis, naxis)) and H = d^2r/dq dq into `hess_desc` (float64 (N, naxis, naxis, naxis)); None = not wanted.
+    Sample 0's descriptors plus byte strides; `disp_desc` is the PREFILTERED control grid; 1 to 3 deformed axes."""
+    lens, in_len = _ptr(in_len, numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_points_derivatives,
+          (int(nbatch), *_pairs(pts_desc, pts_bstride, disp_desc, disp_bstride), lens, off, len(in_len), aff,
+           *_pairs(res_desc, res_bstride, jac_desc, jac_bstride, hess_desc, hess_bstride)), flags, stream)
+
+
+def deform_points_derivatives_gradient(nbatch, pos_desc, pos_bstride, dres_desc, dres_bstride, djac_desc, djac_bstride,
+                                       dhess_desc, dhess_bstride, disp_desc, disp_bstride, in_len, output_offset,
+                                       inverse_affine, dpts_desc, dpts_bstride, ddisp_desc, ddisp_bstride, dinv_desc,
+                                       dinv_bstride, flags, stream):
+    """edhip_deform_points_derivatives_gradient: the adjoint of deform_points_derivatives() for the cotangents
+    `dres_desc` = dL/dr, `djac_desc` = dL/dJ, `dhess_desc` = dL/dH (None = not given).  Results as for
+    deform_points_gradient() (None = not wanted)."""
+    lens, in_len = _ptr(in_len, numpy.int64)
+    off, aff, _keep = _offset_affine(output_offset, inverse_affine)
+    _call(load().edhip_deform_points_derivatives_gradient,
+          (int(nbatch), *_pairs(pos_desc, pos_bstride, dres_desc, dres_bstride, djac_desc, djac_bstride, dhess_desc,
+                                dhess_bstride, disp_desc, disp_bstride), lens, off, len(in_len), aff,
+           *_pairs(dpts_desc, dpts_bstride, ddisp_desc, ddisp_bstride, dinv_desc, dinv_bstride)), flags, stream)
 
 
 def deform_labels(nbatch, in_desc, in_bstride, disp_desc, disp_bstride, output_offset, out_desc, out_bstride,

@@ -12,6 +12,7 @@
 
 #include "ed_device.h"
 #include "ed_params.h"
+#include "ed_points_jet.h"
 #include "ed_workspace.h"
 #include "edhip.h"
 
@@ -1494,6 +1495,170 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
     e = launch_deform_points_gradient(c, stream);
     if (e != hipSuccess)
         return hip_fail(err, errlen, e, "deform points gradient launch");
+    return EDHIP_OK;
+}
+
+// ---- r, J = dr/dq and H = d^2r/dq dq at real positions, and their adjoint (deform_points_jet.hip) -------------------
+namespace {
+
+int check_axes_jet(const char* entry, int naxis, char* err, size_t errlen)
+{
+    if (int st = check_naxis(naxis, err, errlen))
+        return st;
+    if (naxis > 3)
+        return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "%s takes 1 to 3 deformed axes", entry);
+    return EDHIP_OK;
+}
+
+// an optional per-point array of rank `ndim`: (N, naxis, ...), float64 only or float32 / float64
+int check_point_rows(const edhip_array* a, const char* name, int ndim, const int64_t* rows, bool f64_only, char* err,
+                     size_t errlen)
+{
+    if (!a)
+        return EDHIP_OK;
+    if (!has_shape(a, ndim, rows))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "%s must have shape (N%s)", name,
+                    ndim == 2 ? ", naxis" : ndim == 3 ? ", naxis, naxis" : ", naxis, naxis, naxis");
+    if (f64_only ? a->dtype != EDHIP_F64 : !f32_or_f64(a))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, f64_only ? "%s must be float64" : "%s must be float32 or float64",
+                    name);
+    return EDHIP_OK;
+}
+
+}  // namespace
+
+int edhip_deform_points_derivatives(int nbatch, const edhip_array* points0, int64_t points_batch_stride,
+                                    const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                    const int64_t* in_len, const int64_t* output_offset, int naxis,
+                                    const double* affine, const edhip_array* result0, int64_t result_batch_stride,
+                                    const edhip_array* jacobian0, int64_t jacobian_batch_stride,
+                                    const edhip_array* hessian0, int64_t hessian_batch_stride, uint32_t flags,
+                                    void* hip_stream, char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (int st = check_batch_call(nbatch, points0 && displacement0 && result0 && in_len, err, errlen))
+        return st;
+    if (int st = check_axes_jet("edhip_deform_points_derivatives", naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered("edhip_deform_points_derivatives", flags, err, errlen))
+        return st;
+    if (points0->ndim != 2 || points0->shape[1] != naxis || points0->shape[0] < 0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "points must have shape (N, naxis)");
+    const int64_t npts = points0->shape[0];
+    const int64_t rows[4] = {npts, naxis, naxis, naxis};
+    if (!has_shape(result0, 2, rows))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "result must have the shape of points");
+    if (!f32_or_f64(points0) || !f32_or_f64(result0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    if (int st = check_point_rows(jacobian0, "jacobian", 3, rows, true, err, errlen))
+        return st;
+    if (int st = check_point_rows(hessian0, "hessian", 4, rows, true, err, errlen))
+        return st;
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (int st = check_batch_limit("edhip_deform_points_derivatives", nbatch, err, errlen))
+        return st;
+    PointsJetCall c;
+    memset(&c, 0, sizeof(c));
+    if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    if (nbatch == 0 || npts == 0)
+        return EDHIP_OK;
+    c.nbatch = nbatch;
+    c.npts = npts;
+    c.disp_bstride = displacement_batch_stride;
+    c.pts = batch_array(points0, points_batch_stride);
+    c.res = batch_array(result0, result_batch_stride);
+    c.jac = batch_array(jacobian0, jacobian_batch_stride);
+    c.hess = batch_array(hessian0, hessian_batch_stride);
+    const hipError_t e = launch_deform_points_derivatives(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform points derivatives launch");
+    return EDHIP_OK;
+}
+
+int edhip_deform_points_derivatives_gradient(int nbatch, const edhip_array* positions0, int64_t positions_batch_stride,
+                                             const edhip_array* dresult0, int64_t dresult_batch_stride,
+                                             const edhip_array* djacobian0, int64_t djacobian_batch_stride,
+                                             const edhip_array* dhessian0, int64_t dhessian_batch_stride,
+                                             const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                             const int64_t* in_len, const int64_t* output_offset, int naxis,
+                                             const double* affine, const edhip_array* dpoints0,
+                                             int64_t dpoints_batch_stride, const edhip_array* ddisplacement0,
+                                             int64_t ddisplacement_batch_stride, const edhip_array* dinverse_affine0,
+                                             int64_t dinverse_affine_batch_stride, uint32_t flags, void* hip_stream,
+                                             char* err, size_t errlen)
+{
+    using namespace ed;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (int st = check_batch_call(nbatch, positions0 && displacement0 && in_len, err, errlen))
+        return st;
+    if (int st = check_axes_jet("edhip_deform_points_derivatives_gradient", naxis, err, errlen))
+        return st;
+    if (int st = check_prefiltered("edhip_deform_points_derivatives_gradient", flags, err, errlen))
+        return st;
+    if (!dresult0 && !djacobian0 && !dhessian0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "none of dresult, djacobian and dhessian is given");
+    if (!dpoints0 && !ddisplacement0 && !dinverse_affine0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "none of dpoints, ddisplacement and dinverse_affine is requested");
+    if (positions0->ndim != 2 || positions0->shape[1] != naxis || positions0->shape[0] < 0)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "positions must have shape (N, naxis)");
+    const int64_t npts = positions0->shape[0];
+    const int64_t rows[4] = {npts, naxis, naxis, naxis}, map[2] = {naxis, naxis + 1};
+    if (!f32_or_f64(positions0))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
+    if (int st = check_point_rows(dresult0, "dresult", 2, rows, false, err, errlen))
+        return st;
+    if (int st = check_point_rows(djacobian0, "djacobian", 3, rows, false, err, errlen))
+        return st;
+    if (int st = check_point_rows(dhessian0, "dhessian", 4, rows, false, err, errlen))
+        return st;
+    if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
+        return st;
+    if (int st = check_point_rows(dpoints0, "dpoints", 2, rows, false, err, errlen))
+        return st;
+    if (ddisplacement0) {
+        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        const int dt = ddisplacement0->dtype;
+        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
+    }
+    if (dinverse_affine0) {
+        if (!has_shape(dinverse_affine0, 2, map))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine0->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
+    if (int st = check_batch_limit("edhip_deform_points_derivatives_gradient", nbatch, err, errlen))
+        return st;
+    PointsJetGradCall c;
+    memset(&c, 0, sizeof(c));
+    if (int st = fill_geometry(displacement0, in_len, in_len, output_offset, naxis, affine, c.g, err, errlen))
+        return st;
+    if (nbatch == 0 || (npts == 0 && !ddisplacement0 && !dinverse_affine0))
+        return EDHIP_OK;
+    c.nbatch = nbatch;
+    c.npts = npts;
+    c.disp_bstride = displacement_batch_stride;
+    c.pos = batch_array(positions0, positions_batch_stride);
+    c.du = batch_array(dresult0, dresult_batch_stride);
+    c.dA = batch_array(djacobian0, djacobian_batch_stride);
+    c.dG = batch_array(dhessian0, dhessian_batch_stride);
+    c.dpts = batch_array(dpoints0, dpoints_batch_stride);
+    c.ddisp = batch_array(ddisplacement0, ddisplacement_batch_stride);
+    c.dK = batch_array(dinverse_affine0, dinverse_affine_batch_stride);
+    // heads and cells: the stream's workspace, behind its grid head
+    StreamGuard guard(stream);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + points_jet_scratch_bytes(c.g, nbatch), &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    c.scratch = ws + kWorkspaceGridBytes;
+    e = launch_deform_points_derivatives_gradient(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, "deform points derivatives gradient launch");
     return EDHIP_OK;
 }
 

@@ -1270,10 +1270,12 @@ def _points_of_plan(pts, plan):
 
 
 def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, jacobian, max_iter, tol,
-                batch):
+                batch, hessian=None):
     """Both directions of the coordinate map, single call and batch.  Returns (coordinates, jacobian or None,
-    converged or None) with the leading dimensions of `points`.  Every argument check runs before the device is
-    touched: offsets, the inverse map K and the rotate / zoom centre are the image call's own (the same Plan)."""
+    converged or None) with the leading dimensions of `points`.  `hessian` given (forward direction only): the
+    derivatives call, 1 to 3 deformed axes -- the third result is then H = d^2r/dq dq (float64) for True, None for
+    False.  Every argument check runs before the device is touched: offsets, the inverse map K and the rotate / zoom
+    centre are the image call's own (the same Plan)."""
     if X_shape is None:
         raise ValueError("X_shape is required: the shape of the array deform_grid deforms.")
     if inverse:
@@ -1281,13 +1283,16 @@ def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom,
     X_shape = tuple(int(v) for v in X_shape)
     pts = _as_points(points)
     plan, n, lead = _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom)
+    if hessian is not None and n > 3:
+        raise RuntimeError('deform_grid_derivatives takes 1 to 3 deformed axes')   # (the library's own limit)
 
     if any(int(d) == 1 for d in plan.deform_shape):
         # a deformed axis of length 1: the control coordinate divides by I - 1 = 0 (the image call maps every voxel
         # to cval there) -- no coordinate is defined and nothing converges
         return (_fill(pts, lead + (n,), float('nan')),
                 _fill(pts, lead + (n, n), float('nan'), 'float64') if jacobian else None,
-                _fill(pts, lead, False, 'bool') if inverse else None)
+                _fill(pts, lead, False, 'bool') if inverse else
+                _fill(pts, lead + (n, n, n), float('nan'), 'float64') if hessian else None)
 
     K = plan.inverse_affine
     M = _forward_linear(K, n) if inverse else None
@@ -1302,14 +1307,22 @@ def _points_map(points, displacement, X_shape, crop, axis, affine, rotate, zoom,
         res = torch.empty(tuple(pd.shape), dtype=pd.dtype, device=device)
         jac = torch.empty(tuple(pd.shape) + (n,), dtype=torch.float64, device=device) if jacobian else None
         ok = torch.empty(tuple(pd.shape[:-1]), dtype=torch.uint8, device=device) if inverse else None
-        _lib.deform_points(inverse, lead[0] if batch else 1, *_sample(pd, batch), *_sample(df, batch),
-                           plan.deform_shape, plan.output_offset, K, M, *_sample(res, batch), *_sample(jac, batch),
-                           *_sample(ok, batch), int(max_iter), float(tol), 0, stream)
+        if hessian is None:
+            _lib.deform_points(inverse, lead[0] if batch else 1, *_sample(pd, batch), *_sample(df, batch),
+                               plan.deform_shape, plan.output_offset, K, M, *_sample(res, batch), *_sample(jac, batch),
+                               *_sample(ok, batch), int(max_iter), float(tol), 0, stream)
+        else:
+            hess = torch.empty(tuple(pd.shape) + (n, n), dtype=torch.float64, device=device) if hessian else None
+            _lib.deform_points_derivatives(lead[0] if batch else 1, *_sample(pd, batch), *_sample(df, batch),
+                                           plan.deform_shape, plan.output_offset, K, *_sample(res, batch),
+                                           *_sample(jac, batch), *_sample(hess, batch), 0, stream)
         res = _from_device(res.reshape(lead + (n,)), pts)
         if jac is not None:
             jac = _from_device(jac.reshape(lead + (n, n)), pts)
         if ok is not None:
             ok = _from_device(ok.reshape(lead).to(torch.bool), pts)
+        elif hessian:
+            ok = _from_device(hess.reshape(lead + (n, n, n)), pts)
     return res, jac, ok
 
 
@@ -1392,10 +1405,12 @@ PointsGradient = collections.namedtuple('PointsGradient',
 
 def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affine, rotate, zoom, inverse, batch,
                      want_points=True, want_disp=True, want_map=True, max_iter=32, tol=1e-9, positions=None,
-                     converged=None):
+                     converged=None, derivatives=None):
     """The adjoint of _points_map, single call and batch: ONE library call for whatever is wanted.  `cotangent` is
     dL/dr(q) for the positions q = `points` (forward direction) or dL/dq for q = r^-1(points) (inverse; solved here
     in float64 through _points_map unless `positions`, the solved q, and optionally its mask `converged` are given).
+    `derivatives` = (dL/dJ or None, dL/dH or None) (forward direction only): the adjoint of the derivatives call, 1 to
+    3 deformed axes; `cotangent` may then be None, but not all three.
     Returns (plan, d points or None, d displacement or None, dK or None): the first two in the family of `points`, dK
     a float64 tensor (naxis, naxis+1) -- (B, naxis, naxis+1) for a batch -- on the device.  Every argument check
     runs before the device or the library is touched."""
@@ -1405,11 +1420,24 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
         _check_iteration(max_iter, tol)
     X_shape = tuple(int(v) for v in X_shape)
     pts = _as_points(points)
-    cot = _as_points(cotangent)
+    if derivatives is not None and cotangent is None and derivatives[0] is None and derivatives[1] is None:
+        raise ValueError("At least one of d_coordinates, d_jacobian and d_hessian should be given.")
+    cot = _as_points(cotangent) if cotangent is not None else None
     plan, n, lead = _points_plan(pts, X_shape, batch, displacement, crop, axis, affine, rotate, zoom)
-    if tuple(int(v) for v in cot.shape) != tuple(int(v) for v in pts.shape):
+    if cot is not None and tuple(int(v) for v in cot.shape) != tuple(int(v) for v in pts.shape):
         raise ValueError("The cotangent should have the shape of the points, %s, but its shape is %s."
                          % (str(tuple(pts.shape)), str(tuple(cot.shape))))
+    higher = []
+    if derivatives is not None:
+        if n > 3:
+            raise RuntimeError('deform_grid_derivatives_gradient takes 1 to 3 deformed axes')   # (the library's limit)
+        for name, value, tail in zip(('d_jacobian', 'd_hessian'), derivatives, ((n,), (n, n))):
+            value = _as_points(value) if value is not None else None
+            want = tuple(int(v) for v in pts.shape) + tail
+            if value is not None and tuple(int(v) for v in value.shape) != want:
+                raise ValueError("%s should have shape %s, but its shape is %s."
+                                 % (name, str(want), str(tuple(value.shape))))
+            higher.append(value)
     if positions is not None:
         positions = _as_points(positions)
         if tuple(int(v) for v in positions.shape) != tuple(int(v) for v in pts.shape):
@@ -1428,11 +1456,11 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
         return (plan, _fill(pts, lead + (n,), 0.0) if want_points else None,
                 _dgrad_zeros(displacement, pts) if want_disp else None, dk)
 
-    device = _device_for([pts, cot, displacement])
+    device = _device_for([pts, displacement] + [c for c in [cot] + higher if c is not None])
     with torch.cuda.device(device):
         stream = _stream(device)
         pd = _to_device(pts, device)
-        cd = _to_device(cot, device)
+        cd = _to_device(cot, device) if cot is not None else None
         dd = _to_device(displacement, device)
         ok = None
         if inverse:
@@ -1447,17 +1475,27 @@ def _points_gradient(points, cotangent, displacement, X_shape, crop, axis, affin
                     ok = _to_device(converged, device).to(torch.uint8)
         else:
             qd = pd
+        hd = [_to_device(c, device) if c is not None else None for c in higher]
         if not batch:
-            qd, cd = qd.reshape(-1, n), cd.reshape(-1, n)
+            qd = qd.reshape(-1, n)
+            cd = cd.reshape(-1, n) if cd is not None else None
+            hd = [c.reshape((-1,) + tuple(c.shape[len(lead):])) if c is not None else None for c in hd]
             ok = ok.reshape(-1) if ok is not None else None
         df = _prefiltered_grid(dd, batch, device, stream)
         rows = torch.empty(tuple(qd.shape), dtype=pd.dtype, device=device) if want_points else None
         dp = torch.empty(tuple(int(v) for v in dd.shape), dtype=torch.float64, device=device) if want_disp else None
         dk = torch.empty(dk_shape, dtype=torch.float64, device=device) if want_map else None
-        _lib.deform_points_gradient(inverse, lead[0] if batch else 1, *_sample(qd, batch), *_sample(cd, batch),
-                                    *_sample(ok, batch), *_sample(df, batch), plan.deform_shape, plan.output_offset,
-                                    plan.inverse_affine, *_sample(rows, batch), *_sample(dp, batch),
-                                    *_sample(dk, batch), 0, stream)
+        if derivatives is None:
+            _lib.deform_points_gradient(inverse, lead[0] if batch else 1, *_sample(qd, batch), *_sample(cd, batch),
+                                        *_sample(ok, batch), *_sample(df, batch), plan.deform_shape,
+                                        plan.output_offset, plan.inverse_affine, *_sample(rows, batch),
+                                        *_sample(dp, batch), *_sample(dk, batch), 0, stream)
+        else:
+            _lib.deform_points_derivatives_gradient(lead[0] if batch else 1, *_sample(qd, batch), *_sample(cd, batch),
+                                                    *_sample(hd[0], batch), *_sample(hd[1], batch),
+                                                    *_sample(df, batch), plan.deform_shape, plan.output_offset,
+                                                    plan.inverse_affine, *_sample(rows, batch), *_sample(dp, batch),
+                                                    *_sample(dk, batch), 0, stream)
         out = None
         if dp is not None:
             # dD = (order-3 mirror prefilter)^T dP in fp64, rounded once to the result's dtype
@@ -1536,6 +1574,84 @@ def deform_points_gradient_batch(points, d_positions, displacements, X_shape, cr
     as for :func:`deform_grid_coordinates_gradient_batch`."""
     plan, rows, ddisp, dk = _points_gradient(points, d_positions, displacements, X_shape, crop, axis, affine, rotate,
                                              zoom, True, True, max_iter=max_iter, tol=tol, positions=positions)
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   True)
+
+
+# ---- r, J and H of the coordinate map at real positions, with gradients (no counterpart in the reference) ---------
+
+MapDerivatives = collections.namedtuple('MapDerivatives', ['coordinates', 'jacobian', 'hessian'])
+
+
+def deform_grid_derivatives(positions, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                            zoom=None, hessian=True):
+    """
+    The local differential structure of the coordinate map of :func:`deform_grid` at arbitrary real positions: for
+    every crop-local output position ``q`` (``positions``, shape ``(..., naxis)``) returns
+    ``MapDerivatives(coordinates, jacobian, hessian)`` with
+
+    * ``coordinates``: ``r(q)``, exactly what :func:`deform_grid_coordinates` returns;
+    * ``jacobian``: ``J[..., h, l] = d r_h / d q_l`` (float64), exactly its ``jacobian=True`` result;
+    * ``hessian``: ``H[..., h, l, m] = d^2 r_h / d q_l d q_m`` (float64, shape ``(..., n, n, n)``), symmetric in its
+      last two axes bit for bit and independent of affine / rotate / zoom; ``None`` with ``hessian=False`` (the
+      second-derivative sweep is skipped).
+
+    This is what a local regulariser evaluated at sampled positions needs: folding (``relu(-det J)``), ``log det``,
+    volume preservation, rigidity (``|J^T J - I|^2``), diffusion (``|J - I|^2``) and the bending energy (``|H|^2``).
+    ``r`` is twice continuously differentiable: ``H`` is continuous and piecewise linear in ``q``.
+
+    1 to 3 deformed axes.  dtypes, array families and the other arguments as for :func:`deform_grid_coordinates`; a
+    position that is not finite gives NaN in all three; a deformed axis of length 1 gives NaN.  No autograd flows
+    through this call itself: :func:`deform_grid_derivatives_gradient` is its adjoint and
+    ``elasticdeform_amd.torch.deform_grid_derivatives`` the differentiable wrapper.
+    """
+    return MapDerivatives(*_points_map(positions, displacement, X_shape, crop, axis, affine, rotate, zoom, False, True,
+                                       1, 1.0, False, hessian=bool(hessian)))
+
+
+def deform_grid_derivatives_batch(positions, displacements, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                                  zoom=None, hessian=True):
+    """:func:`deform_grid_derivatives` over a batch with one control grid per sample: ``positions`` ``(B, N, naxis)``,
+    ``displacements`` ``(B, naxis, n_0, ...)``, ``X_shape`` the shape of ONE sample; everything else is shared.  One
+    launch for the batch; sample b equals the single call, bit for bit."""
+    return MapDerivatives(*_points_map(positions, displacements, X_shape, crop, axis, affine, rotate, zoom, False,
+                                       True, 1, 1.0, True, hessian=bool(hessian)))
+
+
+def deform_grid_derivatives_gradient(positions, displacement, X_shape, d_coordinates=None, d_jacobian=None,
+                                     d_hessian=None, crop=None, axis=None, affine=None, rotate=None, zoom=None):
+    """
+    Gradient through :func:`deform_grid_derivatives`: for ``L`` with ``d_coordinates = dL / d r`` (the shape of
+    ``positions``), ``d_jacobian = dL / d J`` (``(..., n, n)``) and ``d_hessian = dL / d H`` (``(..., n, n, n)``; it
+    need not be symmetric) -- float32 / float64, any of them ``None`` but not all -- returns the
+    ``PointsGradient(points, displacement, affine, rotate, zoom, inverse_map)`` of
+    :func:`deform_grid_coordinates_gradient`, in ONE library call:
+
+    * ``points``: ``dL / d positions`` per point, ``J^T d_coordinates + H : d_jacobian + T : d_hessian`` with ``T``
+      the derivative of ``H`` (constant within a knot cell of the control grid; at a knot, the cell of ``floor``);
+    * ``displacement``: ``dL / d displacement``, the order-3 prefilter of the grid included;
+    * ``affine`` / ``rotate`` / ``zoom`` / ``inverse_map``: as in :class:`AffineGradient` (``zoom=0`` raises);
+      ``d_hessian`` does not reach them.
+
+    Positions that are not finite contribute nothing (a zero row, their cotangents ignored); one non-finite cotangent
+    elsewhere makes ``displacement`` and the map's fields NaN.  The sums over the points are 64-bit integer fixed
+    point: the same bits on every call and after any permutation of the points.  1 to 3 deformed axes; numpy in
+    gives numpy out, otherwise tensors on the positions' device.  A deformed axis of length 1 gives zeros.
+    """
+    plan, rows, ddisp, dk = _points_gradient(positions, d_coordinates, displacement, X_shape, crop, axis, affine,
+                                             rotate, zoom, False, False, derivatives=(d_jacobian, d_hessian))
+    return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
+                                   False)
+
+
+def deform_grid_derivatives_gradient_batch(positions, displacements, X_shape, d_coordinates=None, d_jacobian=None,
+                                           d_hessian=None, crop=None, axis=None, affine=None, rotate=None, zoom=None):
+    """:func:`deform_grid_derivatives_gradient` over a batch with one control grid per sample: ``positions``
+    ``(B, N, naxis)`` and the cotangents with that leading shape, ``displacements`` ``(B, naxis, n_0, ...)``,
+    ``X_shape`` the shape of ONE sample.  ``points`` and ``displacement`` are per sample, the same bits as the single
+    call on that sample; the map's fields are the sum over the samples in sample order."""
+    plan, rows, ddisp, dk = _points_gradient(positions, d_coordinates, displacements, X_shape, crop, axis, affine,
+                                             rotate, zoom, False, True, derivatives=(d_jacobian, d_hessian))
     return _points_gradient_result(plan, rows, ddisp, dk, affine, rotate, zoom, isinstance(rows, numpy.ndarray),
                                    True)
 

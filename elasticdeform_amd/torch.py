@@ -25,6 +25,9 @@ from . import _host
 from . import deform_grid_coordinates_batch, deform_points_batch  # noqa: F401
 from . import deform_grid_coordinates as _deform_grid_coordinates_fn
 from . import deform_points as _deform_points_fn
+from . import deform_grid_derivatives_batch, deform_grid_derivatives_gradient  # noqa: F401
+from . import deform_grid_derivatives_gradient_batch, MapDerivatives  # noqa: F401
+from . import deform_grid_derivatives as _deform_grid_derivatives_fn
 # label-aware linear resampling of label maps (integer tensors stay on their device; no autograd)
 from . import deform_grid_labels, deform_grid_labels_batch  # noqa: F401
 # an image resampled back through the deformation and its adjoint: the package's own names (tensors stay on their
@@ -303,9 +306,10 @@ def deform_random_grid_batch(X, sigma=25, points=3, axis=None, generator=None, *
 
 # ---- points through the deformation, with autograd ------------------------------------------------------------------
 
-def _points_backward(ctx, inverse, cotangent, positions, converged):
-    """backward of both point Functions (inputs: points, displacement, affine, rotate, zoom, two non-tensors): ONE
-    library call (deform_grid.py _points_gradient) for whatever needs a gradient"""
+def _points_backward(ctx, inverse, cotangent, positions, converged, derivatives=None):
+    """backward of the point Functions (inputs: points, displacement, affine, rotate, zoom, two non-tensors): ONE
+    library call (deform_grid.py _points_gradient) for whatever needs a gradient; `derivatives`: the cotangents of J
+    and H (either may be None, and then `cotangent` too) for the adjoint of the derivatives call"""
     pts, displacement = (t.detach() for t in ctx.saved_tensors[:2])
     want_points = ctx.needs_input_grad[0]
     want_disp = ctx.disp_grad and ctx.needs_input_grad[1]
@@ -315,9 +319,10 @@ def _points_backward(ctx, inverse, cotangent, positions, converged):
     if want_points or want_disp or want_map:
         host = ctx.host
         plan, dpts, ddisp, dk = _api._points_gradient(
-            pts, cotangent.detach(), displacement, ctx.x_shape, ctx.kw.get('crop'), ctx.kw.get('axis'),
-            host.get('affine'), host.get('rotate'), host.get('zoom'), inverse, False, want_points=want_points,
-            want_disp=want_disp, want_map=want_map, positions=positions, converged=converged)
+            pts, cotangent.detach() if cotangent is not None else None, displacement, ctx.x_shape, ctx.kw.get('crop'),
+            ctx.kw.get('axis'), host.get('affine'), host.get('rotate'), host.get('zoom'), inverse, False,
+            want_points=want_points, want_disp=want_disp, want_map=want_map, positions=positions, converged=converged,
+            derivatives=derivatives)
         if ddisp is not None:
             ddisp = ddisp.to(device=displacement.device, dtype=displacement.dtype)
         if dk is not None:
@@ -423,6 +428,58 @@ def deform_points(points, displacement, X_shape, crop=None, axis=None, affine=No
                                dict(X_shape=X_shape, crop=crop, axis=axis, max_iter=max_iter, tol=tol),
                                bool(displacement_grad))
     return (q, ok) if return_converged else q
+
+
+# ---- r, J and H at real positions, with autograd ----------------------------------------------------------------------
+
+class DeformGridDerivatives(torch.autograd.Function):
+    """forward: deform_grid_derivatives; backward: ONE call of deform_grid_derivatives_gradient's kernels for whichever
+    of r, J and H received a cotangent"""
+
+    @staticmethod
+    def forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad):
+        call = _points_forward(ctx, pts, displacement, affine, rotate, zoom, kw, disp_grad)
+        ctx.save_for_backward(pts, displacement)
+        ctx.set_materialize_grads(False)
+        r, J, H = _deform_grid_derivatives_fn(pts.detach(), displacement.detach(), kw['X_shape'],
+                                              hessian=kw['hessian'], **call)
+        return r, J, H
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dr, dJ, dH=None):
+        if dr is None and dJ is None and dH is None:
+            return (None,) * 7
+        return _points_backward(ctx, False, dr, None, None,
+                                derivatives=tuple(d.detach() if d is not None else None for d in (dJ, dH)))
+
+
+def deform_grid_derivatives(positions, displacement, X_shape, crop=None, axis=None, affine=None, rotate=None,
+                            zoom=None, hessian=True, *, displacement_grad=False, affine_grad=False):
+    """
+    ``elasticdeform_amd.deform_grid_derivatives`` with autograd: ``MapDerivatives(r, J, H)`` at the positions, all
+    three differentiable -- the gradient flows to ``positions`` whenever they require it, to ``displacement`` with
+    ``displacement_grad=True`` and to tensor ``affine`` / ``rotate`` / ``zoom`` with ``affine_grad=True`` (keyword-only,
+    the switches of :func:`deform_grid_coordinates`); the backward is ONE call of
+    ``elasticdeform_amd.deform_grid_derivatives_gradient``'s kernels for whichever of the three received a cotangent,
+    and is differentiable once.  A sampled folding penalty and bending energy::
+
+        r, J, H = deform_grid_derivatives(q, D, fixed.shape, displacement_grad=True)
+        reg = relu(-det(J)).mean() + mu * (H ** 2).sum((-1, -2, -3)).mean()
+
+    With nothing requiring a gradient the call is the package's own: same bits, same types, numpy stays numpy.
+    """
+    params = (affine, rotate, zoom)
+    if not _points_need_autograd(positions, displacement, params, displacement_grad, affine_grad):
+        host = [_host_value(v) for v in params]
+        return _deform_grid_derivatives_fn(positions, displacement, X_shape, crop, axis, *host, hessian=hessian)
+    positions = torch.as_tensor(positions)
+    displacement = torch.as_tensor(displacement)
+    if not affine_grad:
+        params = tuple(_host_value(v) for v in params)
+    return MapDerivatives(*DeformGridDerivatives.apply(
+        positions, displacement, *params, dict(X_shape=X_shape, crop=crop, axis=axis, hessian=bool(hessian)),
+        bool(displacement_grad)))
 
 
 # ---- det J on the voxel lattice, with autograd ------------------------------------------------------------------------

@@ -486,6 +486,92 @@ int edhip_deform_points_gradient(int inverse, int nbatch,
                                  char* err, size_t errlen);
 
 /*
+ * The local differential structure of the coordinate map at arbitrary real positions (no counterpart in the
+ * reference): r(q) as edhip_deform_points(inverse = 0) returns it, with its first and second derivatives.  In the
+ * notation above, s_k = (ncp_k - 1) / (in_len_k - 1), w' and w'' = (1 - x, 3x - 2, 1 - 3x, x) the derivatives of the
+ * cubic weights at the fraction x = cp - floor(cp):
+ *   J[i, h, l]    = K[h, l] + sum_taps P[h, m(t)] s_l w'_l prod_{k != l} w_k                      (= d r_h / d q_l)
+ *   H[i, h, l, m] = sum_taps P[h, m(t)] (l == m ? s_l^2 w''_l prod_{k != l} w_k
+ *                                               : s_l s_m w'_l w'_m prod_{k != l, m} w_k)   (= d^2 r_h / d q_l d q_m)
+ * H is symmetric in (l, m), bit for bit, and does not depend on K.  result0 and jacobian0 are the bits
+ * edhip_deform_points writes (the same device code).  r is C2: H is continuous and piecewise linear, its derivative
+ * jumps at the knots.
+ *   points0 / result0    (N, naxis), float32 or float64 each, any strides.  N = 0 launches nothing.
+ *   displacement0        the PREFILTERED control grid (naxis, ncp_0, ...), any dtype / strides;
+ *                        EDHIP_FLAG_RAW_DISPLACEMENT is refused (EDHIP_ERR_INVALID).
+ *   in_len, output_offset, affine   as for edhip_deform_points (in_len >= 2 each).
+ *   naxis                1 to 3 (EDHIP_ERR_UNSUPPORTED beyond).
+ *   jacobian0            NULL, or float64 (N, naxis, naxis), any strides.
+ *   hessian0             NULL (the second-derivative sweep is skipped), or float64 (N, naxis, naxis, naxis).
+ *   nbatch               at most 65535; the batch is described as for edhip_deform_points.
+ * A position that is not finite, or whose control coordinate reaches 4e15, gives NaN in r, J and H; nothing is read out
+ * of range.  Every shape and dtype check answers before any launch.  One launch, one thread per point, no atomics: a
+ * point's result depends on that point and the call's arguments alone.  No workspace, no synchronisation: the call
+ * can be captured into a HIP graph.
+ */
+int edhip_deform_points_derivatives(int nbatch,
+                                    const edhip_array* points0, int64_t points_batch_stride,
+                                    const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                    const int64_t* in_len,
+                                    const int64_t* output_offset,
+                                    int naxis,
+                                    const double* affine,
+                                    const edhip_array* result0, int64_t result_batch_stride,
+                                    const edhip_array* jacobian0, int64_t jacobian_batch_stride,
+                                    const edhip_array* hessian0, int64_t hessian_batch_stride,
+                                    uint32_t flags, void* hip_stream,
+                                    char* err, size_t errlen);
+
+/*
+ * The adjoint of edhip_deform_points_derivatives.  With the cotangents u[i, :] = dL / d r(q_i), A[i] = dL / d J(q_i),
+ * G[i] = dL / d H(q_i) (any of them NULL; G need not be symmetric), beta(q, j) the folded tap-weight products of
+ * edhip_deform_points_gradient and T[h, l, m, p] = d H[h, l, m] / d q_p (the cubic's third-derivative weights
+ * (-1, 3, -3, 1) s^3 are constant per knot cell; the cell is that of floor(cp)):
+ *   ddisplacement[h, j]  = sum_i ( u[i,h] beta(q_i, j) + sum_l A[i,h,l] d_l beta(q_i, j)
+ *                                  + sum_lm G[i,h,l,m] d_l d_m beta(q_i, j) )                      (= dL / dP)
+ *   dinverse_affine[h, l < naxis] = sum_i ( u[i,h] q_i[l] + A[i,h,l] ),   [h, naxis] = sum_i u[i,h]
+ *   dpoints[i, p]        = sum_h u[i,h] J[h,p] + sum_hl A[i,h,l] H[h,l,p] + sum_hlm G[i,h,l,m] T[h,l,m,p]
+ * ddisplacement is the gradient with respect to the PREFILTERED grid; the caller applies the transposed prefilter.
+ * A position that is not finite or whose control coordinate reaches 4e15 contributes nothing: a zero row, its
+ * cotangents ignored.
+ *   positions0 / dpoints0   (N, naxis), float32 or float64 each, any strides.
+ *   dresult0 / djacobian0 / dhessian0   NULL, or (N, naxis) / (N, naxis, naxis) / (N, naxis, naxis, naxis), float32
+ *                        or float64 each.  All three NULL: EDHIP_ERR_INVALID.
+ *   displacement0, in_len, output_offset, affine, naxis (1 to 3), nbatch (at most 65535): as for the forward call.
+ *   dpoints0 / ddisplacement0 / dinverse_affine0   NULL or as for edhip_deform_points_gradient; all three NULL:
+ *                        EDHIP_ERR_INVALID.
+ * Every shape, dtype and flag check answers before any launch.  With N == 0 the requested ddisplacement /
+ * dinverse_affine are written as zeros; with nbatch == 0 nothing is launched.
+ * Resolution and bit contracts, those of edhip_deform_points_gradient: the sums are 64-bit integer fixed point.  Per
+ * sample, over the N contributing points, bP = max_{i,h} |u_h| + 1.5 sum_l s_l |A_hl| + sum_lm c_lm s_l s_m |G_hlm|
+ * (c_ll = 4, c_lm = 2.25) bounds what one point adds to one cell of ddisplacement, and bK = max_{i,h} max(|u_h|,
+ * max_l |u_h q_l| + |A_hl|) what it adds to one of dinverse_affine; a contribution is rounded to a multiple of
+ * 2^(e-62), 2^e the smallest power of two >= 2 N bP (2 N bK).  No cell can overflow and integer addition is
+ * associative: the two sums are the same bits on a repeated call, for a sample of a batch and the single call on it,
+ * after ANY permutation of the points, and eager or replayed from a captured HIP graph.  A row of dpoints depends on
+ * that point and the call's arguments alone.  One non-finite cotangent on a contributing point makes every element of
+ * that sample's ddisplacement / dinverse_affine NaN (and no other sample's).  Four launches -- the clearing of the
+ * call's scratch (the stream's workspace) and three kernels -- on hip_stream without synchronising; nothing is carried
+ * from one call to the next (warm up once on the capture stream: the workspace is allocated on first use).
+ */
+int edhip_deform_points_derivatives_gradient(int nbatch,
+                                             const edhip_array* positions0, int64_t positions_batch_stride,
+                                             const edhip_array* dresult0, int64_t dresult_batch_stride,
+                                             const edhip_array* djacobian0, int64_t djacobian_batch_stride,
+                                             const edhip_array* dhessian0, int64_t dhessian_batch_stride,
+                                             const edhip_array* displacement0, int64_t displacement_batch_stride,
+                                             const int64_t* in_len,
+                                             const int64_t* output_offset,
+                                             int naxis,
+                                             const double* affine,
+                                             const edhip_array* dpoints0, int64_t dpoints_batch_stride,
+                                             const edhip_array* ddisplacement0, int64_t ddisplacement_batch_stride,
+                                             const edhip_array* dinverse_affine0,
+                                             int64_t dinverse_affine_batch_stride,
+                                             uint32_t flags, void* hip_stream,
+                                             char* err, size_t errlen);
+
+/*
  * Label-aware linear resampling of label maps (no counterpart in the reference, whose order-1 interpolation of an
  * integer map interpolates the label NUMBERS).  For a label map L, with the classes being the distinct values of L
  * together with cval, the score of class c is the reference's own float64 order-1 result on the one-hot channel,
