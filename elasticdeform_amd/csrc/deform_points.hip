@@ -45,6 +45,9 @@ __global__ __launch_bounds__(kPointsThreads) void points_kernel(PointsArgs a)
     const int64_t b = blockIdx.y;
     a.g.disp += b * a.disp_bstride;           // this sample's control grid
     const GridGeom& g = a.g;
+    // (the tap strides and, below, the position load stand inline, not as grid_tap_strides / load_point of ed_points.h:
+    // through the helpers the 28 instances come out with another register allocation, <3, LDS, forward> with one wave
+    // per SIMD fewer; DESIGN.md, "One copy of the reduction")
     int64_t tstride[N];
     int per = 0;
     if constexpr (LDS) {
@@ -114,8 +117,7 @@ __global__ __launch_bounds__(kPointsThreads) void points_kernel(PointsArgs a)
 template <int N>
 hipError_t launch_points(const PointsArgs& a, bool inverse, int nbatch, size_t lds, hipStream_t stream)
 {
-    const int64_t want = (a.npts + kPointsThreads - 1) / kPointsThreads;
-    const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
+    const dim3 grid = points_grid(a.npts, nbatch);
     const dim3 block(kPointsThreads);
     if (lds) {
         if (inverse)

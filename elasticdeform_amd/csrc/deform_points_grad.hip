@@ -21,43 +21,15 @@ namespace ed {
 namespace {
 
 // ---- the adjoint: gradients through r(q) and through its inverse ----------------------------------------------
+// The fixed-point reduction of ed_points_grad.h, with the bounds from two maxima (its rule OWN = false):
+//   points_grad_clear     heads and cells of every sample: zero (this file compiles it for every caller)
 //   points_grad_prepare   per point: u (forward: the cotangent; inverse: -J^-T g at the solved q) into scratch, the
-//                         point's own row (forward: J^T u; inverse: J^-T g), and per sample max|u|, max|q| (one
-//                         integer atomicMax per wave on the bits of the non-negative double) and the non-finite flag
-//   points_grad_scatter   per point: the tap weights again, every u_h prod(w) as llrint(c / quantum_P) added into
-//                         64-bit integer cells (LDS per workgroup for grids up to kPointsLdsValues values, flushed
-//                         with global integer atomics; global atomics directly beyond), u_h and u_h q_l likewise with
-//                         quantum_K, reduced per wave first
-//   points_grad_finish    per cell: cell * quantum into ddisplacement / dinverse_affine
-// quantum_P = 2^(e - 62) with 2^e the smallest power of two >= 2 N max|u|; quantum_K the same from
-// N max|u| max(1, max|q|), N counting the points that contribute (so that points which contribute nothing do not
-// change a bit of the sums): no cell can overflow, and integer addition is associative, so the sums depend neither on the
-// order in which the points arrive nor on how they are dealt to workgroups.  points_grad_clear zeroes heads and cells
-// in front of every call: nothing is carried from one call to the next.
-
-// the exponent e of the smallest power of two >= bound (bound > 0 and finite)
-__device__ __forceinline__ int ceil_pow2_exponent(double bound)
-{
-    int ex;
-    const double m = frexp(bound, &ex);       // bound = m 2^ex, 0.5 <= m < 1
-    return m == 0.5 ? ex - 1 : ex;
-}
-
-// the two quanta of a sample as exponents (quantum = 2^(e - 62)); false: nothing to add (max|u| = 0) or not
-// representable (the bound overflows)
-__device__ __forceinline__ bool grad_quanta(const unsigned long long* head, int& eP, int& eK)
-{
-    const double maxu = __longlong_as_double((long long)head[0]);
-    const double maxq = __longlong_as_double((long long)head[1]);
-    const double bP = 2.0 * (double)head[3] * maxu;
-    const double bK = bP * (maxq > 1.0 ? maxq : 1.0);
-    eP = eK = 0;
-    if (!(bP > 0.0) || !isfinite(bK))
-        return false;
-    eP = ceil_pow2_exponent(bP);
-    eK = ceil_pow2_exponent(bK);
-    return true;
-}
+//                         point's own row (forward: J^T u; inverse: J^-T g), and per sample max|u|, max|q|, the
+//                         non-finite flag and the number of contributing points
+//   points_grad_scatter   per point: the tap weights again, every u_h prod(w) with quantum_P, u_h and u_h q_l with
+//                         quantum_K
+//   points_grad_finish    per cell: cell * quantum into ddisplacement / dinverse_affine (this file compiles it for
+//                         every caller, once per rule)
 
 // heads and cells of every sample: zero (a kernel of the call's own, in stream order in front of the other three)
 __global__ __launch_bounds__(kPointsThreads) void points_grad_clear(unsigned long long* words, int64_t count)
@@ -74,7 +46,7 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_prepare(PointsGrad
     PointsArgs& a = ga.p;
     a.g.disp += b * a.disp_bstride;
     const GridGeom& g = a.g;
-    const bool need_map = ga.inverse || ga.dpts;      // (the forward direction's sums need no J)
+    const bool need_map = ga.inverse || ga.o.dpts;    // (the forward direction's sums need no J)
     int64_t tstride[N];
     int per = 0;
     if constexpr (LDS) {
@@ -82,17 +54,8 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_prepare(PointsGrad
             per = stage_grid_lds<N>(g, s_grid);
             __syncthreads();
         }
-        int64_t cs = 1;
-#pragma unroll
-        for (int k = N - 1; k >= 0; --k) {
-            tstride[k] = cs;
-            cs *= g.ncp[k];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            tstride[k] = g.disp_stride[k + 1];
     }
+    grid_tap_strides<N, LDS>(g, tstride);
     const char* pts = a.pts + b * a.pts_bstride;
     const char* cot = ga.cot + b * ga.cot_bstride;
     double* urow = ga.u + b * a.npts * N;
@@ -104,10 +67,9 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_prepare(PointsGrad
          i += (int64_t)gridDim.x * blockDim.x) {
         double q[N], c[N], u[N], row[N];
         bool cfinite = true;
+        load_point<N>(a, pts, i, q);
 #pragma unroll
         for (int h = 0; h < N; ++h) {
-            const char* src = pts + i * a.pts_stride[0] + h * a.pts_stride[1];
-            q[h] = a.pts_f32 ? (double)*(const float*)src : *(const double*)src;
             const char* csrc = cot + i * ga.cot_stride[0] + h * ga.cot_stride[1];
             c[h] = ga.cot_f32 ? (double)*(const float*)csrc : *(const double*)csrc;
             cfinite = cfinite && isfinite(c[h]);
@@ -173,39 +135,10 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_prepare(PointsGrad
 #pragma unroll
         for (int h = 0; h < N; ++h)
             urow[i * N + h] = u[h];
-        if (ga.dpts) {
-            char* dst = ga.dpts + b * ga.dpts_bstride + i * ga.dpts_stride[0];
-#pragma unroll
-            for (int h = 0; h < N; ++h) {
-                if (ga.dpts_f32)
-                    *(float*)(dst + h * ga.dpts_stride[1]) = (float)row[h];
-                else
-                    *(double*)(dst + h * ga.dpts_stride[1]) = row[h];
-            }
-        }
+        if (ga.o.dpts)
+            store_point_row<N>(ga.o, b, i, row);
     }
-    // a max does not depend on the order: one integer atomicMax per wave on the bits of the non-negative doubles
-    maxu = wave_max(maxu);
-    maxq = wave_max(maxq);
-    const bool any_bad = __any(bad);
-    for (int m = warpSize / 2; m > 0; m >>= 1)
-        count += (unsigned long long)__shfl_xor((long long)count, m);
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-        unsigned long long* head = ga.head + b * kGradHead;
-        if (maxu > 0.0)
-            atomicMax(head + 0, (unsigned long long)__double_as_longlong(maxu));
-        if (maxq > 0.0)
-            atomicMax(head + 1, (unsigned long long)__double_as_longlong(maxq));
-        if (any_bad)
-            atomicMax(head + 2, 1ull);
-        if (count)
-            atomicAdd(head + 3, count);
-    }
-}
-
-__device__ __forceinline__ unsigned long long quantise(double c, int shift)
-{
-    return (unsigned long long)llrint(ldexp(c, shift));
+    publish_head(ga.o.head + b * kGradHead, maxu, maxq, bad, count);
 }
 
 template <int N, bool LDS>
@@ -216,27 +149,15 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_scatter(PointsGrad
     const PointsArgs& a = ga.p;
     const GridGeom& g = a.g;
     constexpr int NK = N * (N + 1);
-    unsigned long long* cellsK = ga.cells + b * ga.cells_per;
+    unsigned long long* cellsK = ga.o.cells + b * ga.o.cells_per;
     unsigned long long* cellsP = cellsK + NK;
-    int eP, eK;
-    const bool any = grad_quanta(ga.head + b * kGradHead, eP, eK);
-    if (!any)
-        return;                                       // (uniform over the workgroup)
-    const bool wantP = ga.ddisp != nullptr, wantK = ga.dK != nullptr;
-    if constexpr (LDS) {
-        if (wantP) {
-            for (int e = threadIdx.x; e < ga.values; e += blockDim.x)
-                s_cells[e] = 0ull;
-            __syncthreads();
-        }
-    }
+    int eP, eK, sP, sK;
+    grad_quanta<false>(ga.o.head + b * kGradHead, eP, eK, sP, sK);
+    if (sP <= 0)
+        return;                                       // (uniform over the workgroup; one state for both quanta)
+    const bool wantP = ga.o.ddisp != nullptr, wantK = ga.o.dK != nullptr;
     int64_t cstride[N];
-    int64_t per = 1;
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-        cstride[k] = per;
-        per *= g.ncp[k];
-    }
+    const int64_t per = scatter_begin<N, LDS>(g, ga.o, wantP, s_cells, cstride);
     const char* pts = a.pts + b * a.pts_bstride;
     const double* urow = ga.u + b * a.npts * N;
     unsigned long long accK[NK];
@@ -248,10 +169,9 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_scatter(PointsGrad
          i += (int64_t)gridDim.x * blockDim.x) {
         double q[N], u[N];
         bool zero = true, finite = true;
+        load_point<N>(a, pts, i, q);
 #pragma unroll
         for (int h = 0; h < N; ++h) {
-            const char* src = pts + i * a.pts_stride[0] + h * a.pts_stride[1];
-            q[h] = a.pts_f32 ? (double)*(const float*)src : *(const double*)src;
             u[h] = urow[i * N + h];
             zero = zero && u[h] == 0.0;
             finite = finite && isfinite(u[h]);
@@ -332,68 +252,72 @@ __global__ __launch_bounds__(kPointsThreads) void points_grad_scatter(PointsGrad
             }
         }
     }
-    if (wantK) {
-        // per wave first, then one atomic per wave and cell
-#pragma unroll
-        for (int e = 0; e < NK; ++e) {
-            unsigned long long v = accK[e];
-            for (int m = warpSize / 2; m > 0; m >>= 1)
-                v += (unsigned long long)__shfl_xor((long long)v, m);
-            if ((threadIdx.x & (warpSize - 1)) == 0 && v != 0ull)
-                atomicAdd(&cellsK[e], v);
-        }
-    }
-    if constexpr (LDS) {
-        if (wantP) {
-            __syncthreads();
-            for (int e = threadIdx.x; e < ga.values; e += blockDim.x) {
-                const unsigned long long v = s_cells[e];
-                if (v != 0ull)
-                    atomicAdd(&cellsP[e], v);
-            }
-        }
-    }
+    scatter_end<N, LDS>(ga.o, wantP, wantK, accK, s_cells, cellsK);
 }
 
-template <int N>
-__global__ __launch_bounds__(kPointsThreads) void points_grad_finish(PointsGradArgs ga)
+// OWN: the rule that turns the head into the two quanta (ed_points_grad.h)
+template <int N, bool OWN>
+__global__ __launch_bounds__(kPointsThreads) void points_grad_finish(GradSums o, GridGeom g)
 {
     const int64_t b = blockIdx.y;
-    const GridGeom& g = ga.p.g;
     constexpr int NK = N * (N + 1);
-    const unsigned long long* head = ga.head + b * kGradHead;
-    const unsigned long long* cells = ga.cells + b * ga.cells_per;
-    int eP, eK;
-    const bool any = grad_quanta(head, eP, eK);
-    const bool zero = __longlong_as_double((long long)head[0]) == 0.0;     // no contribution at all: exact zeros
-    const bool nan = head[2] != 0ull || (!any && !zero);
+    const unsigned long long* head = o.head + b * kGradHead;
+    const unsigned long long* cells = o.cells + b * o.cells_per;
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ga.cells_per)
+    if (e >= o.cells_per)
         return;
-    if (e < NK) {
-        if (!ga.dK)
-            return;
-        const double v = nan ? NAN : (any ? ldexp((double)(long long)cells[e], eK - 62) : 0.0);
-        *(double*)(ga.dK + b * ga.dK_bstride + (e / (N + 1)) * ga.dK_stride[0] + (e % (N + 1)) * ga.dK_stride[1]) = v;
+    const bool isK = e < NK;
+    if (isK ? !o.dK : !o.ddisp)
+        return;
+    int eP, eK, sP, sK;
+    grad_quanta<OWN>(head, eP, eK, sP, sK);
+    const int state = isK ? sK : sP, ex = isK ? eK : eP;
+    // a non-finite cotangent on a contributing point, or a bound that overflows: NaN; nothing to add: exact zeros
+    const double v = (head[2] != 0ull || state < 0) ? NAN : (state > 0 ? ldexp((double)(long long)cells[e], ex - 62) : 0.0);
+    if (isK) {
+        *(double*)(o.dK + b * o.dK_bstride + (e / (N + 1)) * o.dK_stride[0] + (e % (N + 1)) * o.dK_stride[1]) = v;
         return;
     }
-    if (!ga.ddisp)
-        return;
-    const double v = nan ? NAN : (any ? ldexp((double)(long long)cells[e], eP - 62) : 0.0);
     int64_t r = e - NK;
     int64_t per = 1;
 #pragma unroll
     for (int k = 0; k < N; ++k)
         per *= g.ncp[k];
-    int64_t off = (r / per) * ga.ddisp_stride[0];
+    int64_t off = (r / per) * o.ddisp_stride[0];
     r %= per;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         per /= g.ncp[k];
-        off += (r / per) * ga.ddisp_stride[k + 1];
+        off += (r / per) * o.ddisp_stride[k + 1];
         r %= per;
     }
-    store_cast(ga.ddisp + b * ga.ddisp_bstride + off, ga.ddisp_dtype, v);
+    store_cast(o.ddisp + b * o.ddisp_bstride + off, o.ddisp_dtype, v);
+}
+
+template <int N>
+hipError_t launch_finish(const GradSums& o, const GridGeom& g, int nbatch, bool own_bounds, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((o.cells_per + kPointsThreads - 1) / kPointsThreads), (unsigned)nbatch);
+    if (own_bounds)
+        hipLaunchKernelGGL((points_grad_finish<N, true>), grid, dim3(kPointsThreads), 0, stream, o, g);
+    else
+        hipLaunchKernelGGL((points_grad_finish<N, false>), grid, dim3(kPointsThreads), 0, stream, o, g);
+    return hipGetLastError();
+}
+
+hipError_t finish_sums(const GradSums& o, const GridGeom& g, int nbatch, bool own_bounds, hipStream_t stream)
+{
+    if (!o.ddisp && !o.dK)
+        return hipSuccess;
+    switch (g.naxis) {
+    case 1: return launch_finish<1>(o, g, nbatch, own_bounds, stream);
+    case 2: return launch_finish<2>(o, g, nbatch, own_bounds, stream);
+    case 3: return launch_finish<3>(o, g, nbatch, own_bounds, stream);
+    case 4: return launch_finish<4>(o, g, nbatch, own_bounds, stream);
+    case 5: return launch_finish<5>(o, g, nbatch, own_bounds, stream);
+    case 6: return launch_finish<6>(o, g, nbatch, own_bounds, stream);
+    default: return launch_finish<7>(o, g, nbatch, own_bounds, stream);
+    }
 }
 
 // prepare (unless the caller has written the u rows and the heads itself), scatter and finish
@@ -401,11 +325,10 @@ template <int N>
 hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, bool prepare, hipStream_t stream)
 {
     const dim3 block(kPointsThreads);
-    const int64_t npts = ga.p.npts;
-    if (npts > 0) {
-        const int64_t want = (npts + kPointsThreads - 1) / kPointsThreads;
-        const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
-        const size_t grid_lds = lds ? (size_t)ga.values * sizeof(double) : 0;
+    const GradSums& o = ga.o;
+    if (ga.p.npts > 0) {
+        const dim3 grid = points_grid(ga.p.npts, nbatch);
+        const size_t grid_lds = lds ? (size_t)o.values * sizeof(double) : 0;
         hipError_t e = hipSuccess;
         if (prepare) {
             if (lds)
@@ -416,10 +339,10 @@ hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, bo
             if (e != hipSuccess)
                 return e;
         }
-        if (ga.ddisp || ga.dK) {
+        if (o.ddisp || o.dK) {
             if (lds)
                 hipLaunchKernelGGL((points_grad_scatter<N, true>), grid, block,
-                                   ga.ddisp ? (size_t)ga.values * sizeof(unsigned long long) : 0, stream, ga);
+                                   o.ddisp ? (size_t)o.values * sizeof(unsigned long long) : 0, stream, ga);
             else
                 hipLaunchKernelGGL((points_grad_scatter<N, false>), grid, block, 0, stream, ga);
             e = hipGetLastError();
@@ -427,56 +350,31 @@ hipError_t launch_points_grad(const PointsGradArgs& ga, int nbatch, bool lds, bo
                 return e;
         }
     }
-    if (ga.ddisp || ga.dK) {
-        const dim3 grid((unsigned)((ga.cells_per + kPointsThreads - 1) / kPointsThreads), (unsigned)nbatch);
-        hipLaunchKernelGGL((points_grad_finish<N>), grid, block, 0, stream, ga);
-        return hipGetLastError();
-    }
-    return hipSuccess;
+    return finish_sums(o, ga.p.g, nbatch, false, stream);
 }
 
-// the call as the kernels take it; returns whether grid and cells fit LDS
-bool fill_points_grad_args(const PointsGradCall& c, PointsGradArgs& ga)
+bool points_grad_call_ok(const GridGeom& g, int nbatch)
 {
-    const int n = c.g.naxis;
-    memset(&ga, 0, sizeof(ga));
-    PointsArgs& a = ga.p;
-    const int64_t values = fill_points_args(a, c.g, c.disp_bstride, nullptr, 0, 0.0);
-    unpack(c.pos, a.pts, a.pts_stride, a.pts_bstride);
-    unpack(c.cot, ga.cot, ga.cot_stride, ga.cot_bstride);
-    unpack(c.status, ga.status, ga.status_stride, ga.status_bstride);
-    unpack(c.dpts, ga.dpts, ga.dpts_stride, ga.dpts_bstride);
-    unpack(c.ddisp, ga.ddisp, ga.ddisp_stride, ga.ddisp_bstride);
-    unpack(c.dK, ga.dK, ga.dK_stride, ga.dK_bstride);
-    a.pts_f32 = c.pos.dtype == EDHIP_F32;
-    ga.cot_f32 = c.cot.dtype == EDHIP_F32;
-    ga.dpts_f32 = c.dpts.dtype == EDHIP_F32;
-    ga.ddisp_dtype = c.ddisp.dtype;
-    a.npts = c.npts;
-    ga.inverse = c.inverse;
-    if (!c.inverse)
-        ga.status = nullptr;
-    ga.cells_per = values + n * (n + 1);
-    const bool lds = values <= kPointsLdsValues;
-    ga.values = lds ? (int)values : 0;
-    // scratch (ed_points_grad.h): [nbatch heads | nbatch x cells | nbatch x npts x naxis doubles]; heads and cells are
-    // cleared by every call itself, so that nothing is carried from an earlier call (a captured graph replays
-    // self-contained)
-    ga.head = (unsigned long long*)c.scratch;
-    ga.cells = ga.head + (size_t)c.nbatch * kGradHead;
-    ga.u = (double*)(ga.cells + (size_t)c.nbatch * (size_t)ga.cells_per);
-    return lds;
-}
-
-bool points_grad_call_ok(const PointsGradCall& c)
-{
-    return c.g.naxis >= 1 && c.g.naxis <= kMaxAxes && c.nbatch <= 65535;
+    return g.naxis >= 1 && g.naxis <= kMaxAxes && nbatch <= 65535;
 }
 
 hipError_t launch_points_grad_kernels(const PointsGradCall& c, bool prepare, hipStream_t stream)
 {
     PointsGradArgs ga;
-    const bool lds = fill_points_grad_args(c, ga);
+    memset(&ga, 0, sizeof(ga));
+    PointsArgs& a = ga.p;
+    fill_points_args(a, c.g, c.disp_bstride, nullptr, 0, 0.0);
+    unpack(c.pos, a.pts, a.pts_stride, a.pts_bstride);
+    unpack(c.cot, ga.cot, ga.cot_stride, ga.cot_bstride);
+    unpack(c.status, ga.status, ga.status_stride, ga.status_bstride);
+    a.pts_f32 = c.pos.dtype == EDHIP_F32;
+    ga.cot_f32 = c.cot.dtype == EDHIP_F32;
+    a.npts = c.npts;
+    ga.inverse = c.inverse;
+    if (!c.inverse)
+        ga.status = nullptr;
+    const bool lds = fill_grad_sums(ga.o, c.dpts, c.ddisp, c.dK, c.g, c.scratch, c.nbatch);
+    ga.u = (double*)(ga.o.cells + (size_t)c.nbatch * (size_t)ga.o.cells_per);   // the u rows: behind heads and cells
     switch (c.g.naxis) {
     case 1: return launch_points_grad<1>(ga, c.nbatch, lds, prepare, stream);
     case 2: return launch_points_grad<2>(ga, c.nbatch, lds, prepare, stream);
@@ -495,22 +393,34 @@ size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts)
     return (size_t)nbatch * (size_t)(kGradHead + points_grad_cells_per(g) + npts * g.naxis) * 8;
 }
 
-hipError_t launch_points_grad_clear(const PointsGradCall& c, hipStream_t stream)
+hipError_t launch_points_grad_clear(const GridGeom& g, int nbatch, char* scratch, hipStream_t stream)
 {
-    if (!points_grad_call_ok(c))
+    if (!points_grad_call_ok(g, nbatch))
         return hipErrorNotSupported;
-    if (c.nbatch <= 0)
+    if (nbatch <= 0)
         return hipSuccess;
-    const int64_t words = (int64_t)c.nbatch * (kGradHead + points_grad_cells_per(c.g));
-    const int64_t blocks = (words + kPointsThreads - 1) / kPointsThreads;
-    hipLaunchKernelGGL(points_grad_clear, dim3((unsigned)(blocks < kPointsMaxBlocks ? blocks : kPointsMaxBlocks)),
-                       dim3(kPointsThreads), 0, stream, (unsigned long long*)c.scratch, words);
+    const int64_t words = (int64_t)nbatch * (kGradHead + points_grad_cells_per(g));
+    hipLaunchKernelGGL(points_grad_clear, dim3(points_grid(words, 1).x), dim3(kPointsThreads), 0, stream,
+                       (unsigned long long*)scratch, words);
     return hipGetLastError();
+}
+
+hipError_t launch_points_grad_finish(const GridGeom& g, int nbatch, const BatchArray& ddisp, const BatchArray& dK,
+                                     char* scratch, bool own_bounds, hipStream_t stream)
+{
+    if (!points_grad_call_ok(g, nbatch))
+        return hipErrorNotSupported;
+    if (nbatch <= 0)
+        return hipSuccess;
+    GradSums o;
+    memset(&o, 0, sizeof(o));
+    fill_grad_sums(o, BatchArray{}, ddisp, dK, g, scratch, nbatch);
+    return finish_sums(o, g, nbatch, own_bounds, stream);
 }
 
 hipError_t launch_points_grad_reduce(const PointsGradCall& c, hipStream_t stream)
 {
-    if (!points_grad_call_ok(c))
+    if (!points_grad_call_ok(c.g, c.nbatch))
         return hipErrorNotSupported;
     if (c.nbatch <= 0)
         return hipSuccess;
@@ -519,7 +429,7 @@ hipError_t launch_points_grad_reduce(const PointsGradCall& c, hipStream_t stream
 
 hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream)
 {
-    const hipError_t e = launch_points_grad_clear(c, stream);
+    const hipError_t e = launch_points_grad_clear(c.g, c.nbatch, c.scratch, stream);
     if (e != hipSuccess || c.nbatch <= 0)
         return e;
     return launch_points_grad_kernels(c, true, stream);

@@ -21,23 +21,17 @@
 //   dP[h, j]   = sum_i ( u[i,h] beta(q_i, j) + sum_l A[i,h,l] d_l beta(q_i, j) + sum_lm G[i,h,l,m] d_l d_m beta(q_i, j) )
 //   dK[h, l<n] = sum_i ( u[i,h] q_i[l] + A[i,h,l] )        dK[h, n] = sum_i u[i,h]
 //   dq_i[p]    = sum_h u[i,h] J[h,p] + sum_hl A[i,h,l] H[h,l,p] + sum_hlm G[i,h,l,m] T[h,l,m,p]
-// in the three-pass shape of deform_points_grad.hip, with its bit contracts:
-//   points_jet_grad_clear     heads and cells of every sample: zero, in front of every call
+// by the fixed-point reduction of ed_points_grad.h (the scheme, its bit contract and the clear and finish kernels
+// are there and in deform_points_grad.hip), with the rule of own bounds (OWN = true):
 //   points_jet_grad_prepare   per point the row dq (jet_sums<N, 1, 3>, or <N, 1, 2> without G); per sample the bounds
 //                             bP = max_{i,h} |u_h| + 1.5 sum_l s_l |A_hl| + sum_lm c_lm s_l s_m |G_hlm| (c_ll = 4,
 //                             c_lm = 2.25: sum_t |w_t| = 1, sum_t |w'_t| <= 1.5, sum_t |w''_t| <= 4 on [0, 1)), which
 //                             bounds what one point adds to one cell however its taps fold, and
-//                             bK = max_{i,h} max(|u_h|, max_l |u_h q_l| + |A_hl|); one integer atomicMax per wave on
-//                             the bits of the non-negative doubles; the non-finite flag; the number of contributing points
-//   points_jet_grad_scatter   per point and tap the coefficient u_h W + sum_l A_hl d_l W + sum_lm G_hlm d_l d_m W as
-//                             llrint(c / quantum_P) added into 64-bit integer cells (LDS per workgroup for grids up to
-//                             kPointsLdsValues values, flushed with global integer atomics; global atomics beyond); the
-//                             dK terms likewise with quantum_K, reduced per wave first
-//   points_jet_grad_finish    per cell: cell * quantum into ddisplacement / dinverse_affine
-// quantum_P = 2^(e - 62), 2^e the smallest power of two >= 2 N bP with N the number of contributing points; quantum_K
-// the same from bK: no cell can overflow and integer addition is associative, so the sums depend neither on the order
-// of the points nor on how they are dealt to workgroups.  Nothing is carried from one call to the next.  The cotangents
-// are read from the caller's arrays in both passes: the scratch holds heads and cells only.
+//                             bK = max_{i,h} max(|u_h|, max_l |u_h q_l| + |A_hl|); the non-finite flag; the number of
+//                             contributing points
+//   points_jet_grad_scatter   per point and tap the coefficient u_h W + sum_l A_hl d_l W + sum_lm G_hlm d_l d_m W with
+//                             quantum_P, the dK terms with quantum_K
+// The cotangents are read from the caller's arrays in both passes: the scratch holds heads and cells only.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -70,19 +64,7 @@ struct JetGradArgs {
     int64_t du_stride[2], du_bstride;
     int64_t dA_stride[3], dA_bstride;
     int64_t dG_stride[4], dG_bstride;
-    char* dpts;                               // (npts, naxis) float32 / float64, or nullptr
-    int dpts_f32;
-    int64_t dpts_stride[2], dpts_bstride;
-    char* ddisp;                              // the grid's shape, a floating dtype, or nullptr
-    int ddisp_dtype;
-    int64_t ddisp_stride[kMaxAxes + 1], ddisp_bstride;
-    char* dK;                                 // float64 (naxis, naxis + 1), or nullptr
-    int64_t dK_stride[2], dK_bstride;
-    unsigned long long* head;                 // per sample: bits of bP, bits of bK, the non-finite flag, the number of
-                                              // contributing points
-    unsigned long long* cells;                // per sample: naxis (naxis + 1) cells of dK, then the cells of dP
-    int values;                               // naxis prod ncp when the dP cells (and the grid) fit LDS, else 0
-    int64_t cells_per;
+    GradSums o;                               // head: bits of bP, of bK, the flag, the count
 };
 
 // four values that take turns at the front: what a rolled tap loop reads without indexing a register array
@@ -243,34 +225,6 @@ __device__ __forceinline__ double load_cot(const char* base, int f32, int64_t of
     return f32 ? (double)*(const float*)(base + off) : *(const double*)(base + off);
 }
 
-template <int N>
-__device__ __forceinline__ void load_point(const PointsArgs& a, const char* pts, int64_t i, double (&q)[N])
-{
-#pragma unroll
-    for (int h = 0; h < N; ++h) {
-        const char* src = pts + i * a.pts_stride[0] + h * a.pts_stride[1];
-        q[h] = a.pts_f32 ? (double)*(const float*)src : *(const double*)src;
-    }
-}
-
-// tap strides of the evaluator: elements of the LDS copy (C order), or bytes of the caller's grid
-template <int N, bool LDS>
-__device__ __forceinline__ void grid_tap_strides(const GridGeom& g, int64_t (&tstride)[N])
-{
-    if constexpr (LDS) {
-        int64_t cs = 1;
-#pragma unroll
-        for (int k = N - 1; k >= 0; --k) {
-            tstride[k] = cs;
-            cs *= g.ncp[k];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            tstride[k] = g.disp_stride[k + 1];
-    }
-}
-
 // ---- forward: r, J, H -----------------------------------------------------------------------------------------------
 template <int N, bool LDS, bool HESS>
 __global__ __launch_bounds__(kPointsThreads) void points_jet_kernel(JetArgs ja)
@@ -342,8 +296,7 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_kernel(JetArgs ja)
 template <int N>
 hipError_t launch_points_jet(const JetArgs& ja, int nbatch, size_t lds, hipStream_t stream)
 {
-    const int64_t want = (ja.p.npts + kPointsThreads - 1) / kPointsThreads;
-    const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
+    const dim3 grid = points_grid(ja.p.npts, nbatch);
     const dim3 block(kPointsThreads);
     if (lds) {
         if (ja.hess)
@@ -360,34 +313,6 @@ hipError_t launch_points_jet(const JetArgs& ja, int nbatch, size_t lds, hipStrea
 }
 
 // ---- the adjoint ----------------------------------------------------------------------------------------------------
-
-// the exponent e of the smallest power of two >= bound (bound > 0 and finite); this and jet_quantise restate the two
-// helpers that deform_points_grad.hip keeps to itself
-__device__ __forceinline__ int jet_pow2_exponent(double bound)
-{
-    int ex;
-    const double m = frexp(bound, &ex);       // bound = m 2^ex, 0.5 <= m < 1
-    return m == 0.5 ? ex - 1 : ex;
-}
-
-// One quantum of a sample as its exponent (quantum = 2^(e - 62)) from the bound's bits and the number of contributing
-// points.  0: nothing to add (exact zeros), 1: e is set, -1: not representable (the bound overflows)
-__device__ __forceinline__ int jet_quantum(unsigned long long bits, unsigned long long count, int& e)
-{
-    const double bound = 2.0 * (double)count * __longlong_as_double((long long)bits);
-    e = 0;
-    if (!(bound > 0.0))
-        return 0;
-    if (!isfinite(bound))
-        return -1;
-    e = jet_pow2_exponent(bound);
-    return 1;
-}
-
-__device__ __forceinline__ unsigned long long jet_quantise(double c, int shift)
-{
-    return (unsigned long long)llrint(ldexp(c, shift));
-}
 
 // the cotangents of component h of point i: u_h, A_h[l], G_h[l][m] (zeros for an absent array); false when one of
 // them is not finite
@@ -412,12 +337,6 @@ __device__ __forceinline__ bool load_cotangents(const JetGradArgs& ga, int64_t b
     return finite;
 }
 
-__global__ __launch_bounds__(kPointsThreads) void points_jet_grad_clear(unsigned long long* words, int64_t count)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-        words[i] = 0ull;
-}
-
 template <int N, bool LDS, bool THIRD>
 __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_prepare(JetGradArgs ga)
 {
@@ -430,7 +349,7 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_prepare(JetGra
     int64_t tstride[N];
     int per = 0;
     if constexpr (LDS) {
-        if (ga.dpts) {                        // (the sums need no derivative of the map)
+        if (ga.o.dpts) {                      // (the sums need no derivative of the map)
             per = stage_grid_lds<N>(g, s_grid);
             __syncthreads();
         }
@@ -446,7 +365,7 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_prepare(JetGra
         double q[N], row[N];
         load_point<N>(a, pts, i, q);
         const bool contributes = sane_position<N>(a, q);
-        const bool sweep = contributes && ga.dpts;
+        const bool sweep = contributes && ga.o.dpts;
         typename Grid::Off toff[N][4];
         double wj[N][4][4];
         if (sweep)
@@ -505,34 +424,10 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_prepare(JetGra
                 maxK = bK > maxK ? bK : maxK;
             }
         }
-        if (ga.dpts) {
-            char* dst = ga.dpts + b * ga.dpts_bstride + i * ga.dpts_stride[0];
-#pragma unroll
-            for (int h = 0; h < N; ++h) {
-                if (ga.dpts_f32)
-                    *(float*)(dst + h * ga.dpts_stride[1]) = (float)row[h];
-                else
-                    *(double*)(dst + h * ga.dpts_stride[1]) = row[h];
-            }
-        }
+        if (ga.o.dpts)
+            store_point_row<N>(ga.o, b, i, row);
     }
-    // a max does not depend on the order: one integer atomicMax per wave on the bits of the non-negative doubles
-    maxP = wave_max(maxP);
-    maxK = wave_max(maxK);
-    const bool any_bad = __any(bad);
-    for (int m = warpSize / 2; m > 0; m >>= 1)
-        count += (unsigned long long)__shfl_xor((long long)count, m);
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-        unsigned long long* head = ga.head + b * kGradHead;
-        if (maxP > 0.0)
-            atomicMax(head + 0, (unsigned long long)__double_as_longlong(maxP));
-        if (maxK > 0.0)
-            atomicMax(head + 1, (unsigned long long)__double_as_longlong(maxK));
-        if (any_bad)
-            atomicMax(head + 2, 1ull);
-        if (count)
-            atomicAdd(head + 3, count);
-    }
+    publish_head(ga.o.head + b * kGradHead, maxP, maxK, bad, count);
 }
 
 template <int N, bool LDS>
@@ -543,28 +438,16 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_scatter(JetGra
     const PointsArgs& a = ga.p;
     const GridGeom& g = a.g;
     constexpr int NK = N * (N + 1);
-    const unsigned long long* head = ga.head + b * kGradHead;
-    unsigned long long* cellsK = ga.cells + b * ga.cells_per;
+    unsigned long long* cellsK = ga.o.cells + b * ga.o.cells_per;
     unsigned long long* cellsP = cellsK + NK;
-    int eP, eK;
-    const bool wantP = jet_quantum(head[0], head[3], eP) > 0 && ga.ddisp != nullptr;
-    const bool wantK = jet_quantum(head[1], head[3], eK) > 0 && ga.dK != nullptr;
+    int eP, eK, sP, sK;
+    grad_quanta<true>(ga.o.head + b * kGradHead, eP, eK, sP, sK);
+    const bool wantP = sP > 0 && ga.o.ddisp != nullptr;
+    const bool wantK = sK > 0 && ga.o.dK != nullptr;
     if (!wantP && !wantK)
         return;                                       // (uniform over the workgroup)
-    if constexpr (LDS) {
-        if (wantP) {
-            for (int e = threadIdx.x; e < ga.values; e += blockDim.x)
-                s_cells[e] = 0ull;
-            __syncthreads();
-        }
-    }
     int64_t cstride[N];
-    int64_t per = 1;
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-        cstride[k] = per;
-        per *= g.ncp[k];
-    }
+    const int64_t per = scatter_begin<N, LDS>(g, ga.o, wantP, s_cells, cstride);
     const char* pts = a.pts + b * a.pts_bstride;
     unsigned long long accK[NK];
 #pragma unroll
@@ -595,13 +478,13 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_scatter(JetGra
             if (wantK) {
 #pragma unroll
                 for (int l = 0; l < N; ++l)
-                    accK[h * (N + 1) + l] += jet_quantise(u * q[l] + A[l], 62 - eK);
-                accK[h * (N + 1) + N] += jet_quantise(u, 62 - eK);
+                    accK[h * (N + 1) + l] += quantise(u * q[l] + A[l], 62 - eK);
+                accK[h * (N + 1) + N] += quantise(u, 62 - eK);
             }
             if (!wantP)
                 continue;
             auto add = [&](int64_t off, double c) {
-                const unsigned long long v = jet_quantise(c, 62 - eP);
+                const unsigned long long v = quantise(c, 62 - eP);
                 if constexpr (LDS)
                     atomicAdd(&s_cells[h * per + off], v);
                 else
@@ -656,108 +539,37 @@ __global__ __launch_bounds__(kPointsThreads) void points_jet_grad_scatter(JetGra
             }
         }
     }
-    if (wantK) {
-        // per wave first, then one atomic per wave and cell
-#pragma unroll
-        for (int e = 0; e < NK; ++e) {
-            unsigned long long v = accK[e];
-            for (int m = warpSize / 2; m > 0; m >>= 1)
-                v += (unsigned long long)__shfl_xor((long long)v, m);
-            if ((threadIdx.x & (warpSize - 1)) == 0 && v != 0ull)
-                atomicAdd(&cellsK[e], v);
-        }
-    }
-    if constexpr (LDS) {
-        if (wantP) {
-            __syncthreads();
-            for (int e = threadIdx.x; e < ga.values; e += blockDim.x) {
-                const unsigned long long v = s_cells[e];
-                if (v != 0ull)
-                    atomicAdd(&cellsP[e], v);
-            }
-        }
-    }
+    scatter_end<N, LDS>(ga.o, wantP, wantK, accK, s_cells, cellsK);
 }
 
-template <int N>
-__global__ __launch_bounds__(kPointsThreads) void points_jet_grad_finish(JetGradArgs ga)
-{
-    const int64_t b = blockIdx.y;
-    const GridGeom& g = ga.p.g;
-    constexpr int NK = N * (N + 1);
-    const unsigned long long* head = ga.head + b * kGradHead;
-    const unsigned long long* cells = ga.cells + b * ga.cells_per;
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ga.cells_per)
-        return;
-    const bool isK = e < NK;
-    if (isK ? !ga.dK : !ga.ddisp)
-        return;
-    int ex;
-    const int state = jet_quantum(head[isK ? 1 : 0], head[3], ex);
-    // a non-finite cotangent on a contributing point, or a bound that overflows: NaN; nothing to add: exact zeros
-    const double v = (head[2] != 0ull || state < 0) ? NAN : (state > 0 ? ldexp((double)(long long)cells[e], ex - 62) : 0.0);
-    if (isK) {
-        *(double*)(ga.dK + b * ga.dK_bstride + (e / (N + 1)) * ga.dK_stride[0] + (e % (N + 1)) * ga.dK_stride[1]) = v;
-        return;
-    }
-    int64_t r = e - NK;
-    int64_t per = 1;
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        per *= g.ncp[k];
-    int64_t off = (r / per) * ga.ddisp_stride[0];
-    r %= per;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        per /= g.ncp[k];
-        off += (r / per) * ga.ddisp_stride[k + 1];
-        r %= per;
-    }
-    store_cast(ga.ddisp + b * ga.ddisp_bstride + off, ga.ddisp_dtype, v);
-}
-
+// prepare and scatter over npts > 0 points
 template <int N>
 hipError_t launch_points_jet_grad(const JetGradArgs& ga, int nbatch, bool lds, hipStream_t stream)
 {
     const dim3 block(kPointsThreads);
-    const int64_t npts = ga.p.npts;
-    const bool sums = ga.ddisp || ga.dK;
-    if (npts > 0) {
-        const int64_t want = (npts + kPointsThreads - 1) / kPointsThreads;
-        const dim3 grid((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
-        const size_t grid_lds = lds && ga.dpts ? (size_t)ga.values * sizeof(double) : 0;
-        if (lds) {
-            if (ga.dG)
-                hipLaunchKernelGGL((points_jet_grad_prepare<N, true, true>), grid, block, grid_lds, stream, ga);
-            else
-                hipLaunchKernelGGL((points_jet_grad_prepare<N, true, false>), grid, block, grid_lds, stream, ga);
-        } else {
-            if (ga.dG)
-                hipLaunchKernelGGL((points_jet_grad_prepare<N, false, true>), grid, block, 0, stream, ga);
-            else
-                hipLaunchKernelGGL((points_jet_grad_prepare<N, false, false>), grid, block, 0, stream, ga);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-        if (sums) {
-            if (lds)
-                hipLaunchKernelGGL((points_jet_grad_scatter<N, true>), grid, block,
-                                   ga.ddisp ? (size_t)ga.values * sizeof(unsigned long long) : 0, stream, ga);
-            else
-                hipLaunchKernelGGL((points_jet_grad_scatter<N, false>), grid, block, 0, stream, ga);
-            e = hipGetLastError();
-            if (e != hipSuccess)
-                return e;
-        }
+    const GradSums& o = ga.o;
+    const dim3 grid = points_grid(ga.p.npts, nbatch);
+    const size_t grid_lds = lds && o.dpts ? (size_t)o.values * sizeof(double) : 0;
+    if (lds) {
+        if (ga.dG)
+            hipLaunchKernelGGL((points_jet_grad_prepare<N, true, true>), grid, block, grid_lds, stream, ga);
+        else
+            hipLaunchKernelGGL((points_jet_grad_prepare<N, true, false>), grid, block, grid_lds, stream, ga);
+    } else {
+        if (ga.dG)
+            hipLaunchKernelGGL((points_jet_grad_prepare<N, false, true>), grid, block, 0, stream, ga);
+        else
+            hipLaunchKernelGGL((points_jet_grad_prepare<N, false, false>), grid, block, 0, stream, ga);
     }
-    if (sums) {
-        const dim3 grid((unsigned)((ga.cells_per + kPointsThreads - 1) / kPointsThreads), (unsigned)nbatch);
-        hipLaunchKernelGGL((points_jet_grad_finish<N>), grid, block, 0, stream, ga);
-        return hipGetLastError();
-    }
-    return hipSuccess;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || (!o.ddisp && !o.dK))
+        return e;
+    if (lds)
+        hipLaunchKernelGGL((points_jet_grad_scatter<N, true>), grid, block,
+                           o.ddisp ? (size_t)o.values * sizeof(unsigned long long) : 0, stream, ga);
+    else
+        hipLaunchKernelGGL((points_jet_grad_scatter<N, false>), grid, block, 0, stream, ga);
+    return hipGetLastError();
 }
 
 bool jet_call_ok(const GridGeom& g, int nbatch)
@@ -806,40 +618,30 @@ hipError_t launch_deform_points_derivatives_gradient(const PointsJetGradCall& c,
     JetGradArgs ga;
     memset(&ga, 0, sizeof(ga));
     PointsArgs& a = ga.p;
-    const int64_t values = fill_points_args(a, c.g, c.disp_bstride, nullptr, 0, 0.0);
+    fill_points_args(a, c.g, c.disp_bstride, nullptr, 0, 0.0);
     unpack(c.pos, a.pts, a.pts_stride, a.pts_bstride);
     unpack(c.du, ga.du, ga.du_stride, ga.du_bstride);
     unpack(c.dA, ga.dA, ga.dA_stride, ga.dA_bstride);
     unpack(c.dG, ga.dG, ga.dG_stride, ga.dG_bstride);
-    unpack(c.dpts, ga.dpts, ga.dpts_stride, ga.dpts_bstride);
-    unpack(c.ddisp, ga.ddisp, ga.ddisp_stride, ga.ddisp_bstride);
-    unpack(c.dK, ga.dK, ga.dK_stride, ga.dK_bstride);
     a.pts_f32 = c.pos.dtype == EDHIP_F32;
     ga.du_f32 = c.du.dtype == EDHIP_F32;
     ga.dA_f32 = c.dA.dtype == EDHIP_F32;
     ga.dG_f32 = c.dG.dtype == EDHIP_F32;
-    ga.dpts_f32 = c.dpts.dtype == EDHIP_F32;
-    ga.ddisp_dtype = c.ddisp.dtype;
     a.npts = c.npts;
-    ga.cells_per = values + c.g.naxis * (c.g.naxis + 1);
-    const bool lds = values <= kPointsLdsValues;
-    ga.values = lds ? (int)values : 0;
-    // scratch: [nbatch heads | nbatch x cells], cleared by every call itself, so that nothing is carried from an
-    // earlier call (a captured graph replays self-contained)
-    ga.head = (unsigned long long*)c.scratch;
-    ga.cells = ga.head + (size_t)c.nbatch * kGradHead;
-    const int64_t words = (int64_t)c.nbatch * (kGradHead + ga.cells_per);
-    const int64_t blocks = (words + kPointsThreads - 1) / kPointsThreads;
-    hipLaunchKernelGGL(points_jet_grad_clear, dim3((unsigned)(blocks < kPointsMaxBlocks ? blocks : kPointsMaxBlocks)),
-                       dim3(kPointsThreads), 0, stream, ga.head, words);
-    const hipError_t e = hipGetLastError();
+    const bool lds = fill_grad_sums(ga.o, c.dpts, c.ddisp, c.dK, c.g, c.scratch, c.nbatch);
+    hipError_t e = launch_points_grad_clear(c.g, c.nbatch, c.scratch, stream);
     if (e != hipSuccess)
         return e;
-    switch (c.g.naxis) {
-    case 1: return launch_points_jet_grad<1>(ga, c.nbatch, lds, stream);
-    case 2: return launch_points_jet_grad<2>(ga, c.nbatch, lds, stream);
-    default: return launch_points_jet_grad<3>(ga, c.nbatch, lds, stream);
+    if (c.npts > 0) {
+        switch (c.g.naxis) {
+        case 1: e = launch_points_jet_grad<1>(ga, c.nbatch, lds, stream); break;
+        case 2: e = launch_points_jet_grad<2>(ga, c.nbatch, lds, stream); break;
+        default: e = launch_points_jet_grad<3>(ga, c.nbatch, lds, stream); break;
+        }
+        if (e != hipSuccess)
+            return e;
     }
+    return launch_points_grad_finish(c.g, c.nbatch, c.ddisp, c.dK, c.scratch, true, stream);
 }
 
 }  // namespace ed

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kPointsThreads) void sample_kernel(PointsArgs a, co
 template <int N>
 hipError_t launch_sample(const PointsArgs& a, const SampleView& u, int64_t values, int nbatch, hipStream_t stream)
 {
-    const dim3 grid = sample_grid(a.npts, nbatch);
+    const dim3 grid = points_grid(a.npts, nbatch);
     if (values <= kPointsLdsValues)
         hipLaunchKernelGGL((sample_kernel<N, true>), grid, dim3(kPointsThreads), (size_t)values * sizeof(double),
                            stream, a, u);

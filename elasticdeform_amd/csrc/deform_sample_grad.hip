@@ -84,7 +84,7 @@ template <int N>
 hipError_t launch_sample_grad(const PointsArgs& a, const SampleGradView& t, int64_t values, int nbatch,
                               hipStream_t stream)
 {
-    const dim3 grid = sample_grid(a.npts, nbatch);
+    const dim3 grid = points_grid(a.npts, nbatch);
     if (values <= kPointsLdsValues)
         hipLaunchKernelGGL((sample_grad_kernel<N, true>), grid, dim3(kPointsThreads), (size_t)values * sizeof(double),
                            stream, a, t);

@@ -22,14 +22,15 @@
 //     right-hand side tells a singular J from a non-finite cotangent);
 //   * stores u = -s and q as fp64 rows of the call's scratch (ed_points_grad.h), zeros for a voxel that contributes
 //     nothing: not solved, 'constant' and outside Y (Z = cval there), a position that is not sane, a singular J;
-//   * takes part in the wave reductions of the sample's head: bits of max|u|, bits of max|q|, the non-finite flag,
-//     the number of contributing voxels -- one integer atomic per wave each.  Lanes past the lattice take part with
-//     zeros: they do not return after solve_voxel.
-// points_grad_clear in front, points_grad_scatter and points_grad_finish behind (deform_points_grad.hip, unchanged)
-// turn the rows into dP and dK: 64-bit integer fixed-point sums, so the results do not depend on the order in which
-// the voxels arrive -- a repeated call, a sample of a batch and a graph replay give the same bits.  Where 'nearest'
-// clamps an axis its slope is 0; at a window change (order 1 at integer q_h) the derivative is the one-sided one of
-// spline_weight_derivatives.  Order 0 is piecewise constant: nothing but clear and finish runs, the results are zeros.
+//   * takes part in the wave reductions of the sample's head (publish_head): max|u|, max|q|, the non-finite flag, the
+//     number of contributing voxels.  Lanes past the lattice take part with zeros: they do not return after
+//     solve_voxel.
+// points_grad_clear in front, points_grad_scatter and points_grad_finish behind (deform_points_grad.hip) turn the rows
+// into dP and dK by the fixed-point reduction of ed_points_grad.h, its rule of the two maxima: the results do not depend
+// on the order in which the voxels arrive -- a repeated call, a sample of a batch and a graph replay give the same bits.
+// Where 'nearest' clamps an axis its slope is 0; at a window change (order 1 at integer q_h) the derivative is the
+// one-sided one of spline_weight_derivatives.  Order 0 is piecewise constant: nothing but clear and finish runs, the
+// results are zeros.
 #include <cmath>
 #include <cstring>
 
@@ -155,23 +156,7 @@ __global__ __launch_bounds__(kUnwarpThreads) void unwarp_tgrad_prepare(PointsArg
             t.q[row + h] = q[h];
         }
     }
-    // a max does not depend on the order: one integer atomicMax per wave on the bits of the non-negative doubles
-    maxu = wave_max(maxu);
-    maxq = wave_max(maxq);
-    const bool any_bad = __any(bad);
-    for (int m = warpSize / 2; m > 0; m >>= 1)
-        count += (unsigned long long)__shfl_xor((long long)count, m);
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-        unsigned long long* head = t.head + b * kGradHead;
-        if (maxu > 0.0)
-            atomicMax(head + 0, (unsigned long long)__double_as_longlong(maxu));
-        if (maxq > 0.0)
-            atomicMax(head + 1, (unsigned long long)__double_as_longlong(maxq));
-        if (any_bad)
-            atomicMax(head + 2, 1ull);
-        if (count)
-            atomicAdd(head + 3, count);
-    }
+    publish_head(t.head + b * kGradHead, maxu, maxq, bad, count);
 }
 
 template <int N>
@@ -249,7 +234,7 @@ hipError_t launch_deform_inverse_transform_gradient(const InverseCall& c, const 
     p.dK = dK;
     p.scratch = scratch;
 
-    hipError_t e = launch_points_grad_clear(p, stream);
+    hipError_t e = launch_points_grad_clear(g, c.nbatch, scratch, stream);
     if (e != hipSuccess)
         return e;
     if (rows) {

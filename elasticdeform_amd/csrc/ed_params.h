@@ -231,12 +231,17 @@ struct PointsGradCall {
 };
 size_t points_grad_scratch_bytes(const GridGeom& g, int nbatch, int64_t npts);
 hipError_t launch_deform_points_gradient(const PointsGradCall& c, hipStream_t stream);
-// The two ends of that call for a caller whose own kernel writes the u rows and the sample heads into the scratch
-// (ed_points_grad.h has the layout): _clear zeroes heads and cells, in front of that kernel; _reduce runs the scatter
-// and the finish behind it, reading q from `pos` (no status: a row that contributes nothing is zero) and leaving
-// `ddisp` / `dK`.  `cot` and `dpts` play no part.
-hipError_t launch_points_grad_clear(const PointsGradCall& c, hipStream_t stream);
+// The ends of that call's fixed-point reduction for the other callers (ed_points_grad.h has the scheme and the
+// scratch layout).  _clear zeroes the heads and cells at the front of `scratch`, in front of the caller's own kernels.
+// _reduce, for a caller whose own kernel has written the u rows and the sample heads: the scatter and the finish,
+// reading q from `pos` (no status: a row that contributes nothing is zero) and leaving `ddisp` / `dK`; `cot` and
+// `dpts` play no part.  _finish, for a caller that has scattered into the cells itself: cell * quantum into `ddisp` /
+// `dK` (nothing launched when neither is wanted); own_bounds: the heads hold the two bounds themselves, not max|u|
+// and max|q|.
+hipError_t launch_points_grad_clear(const GridGeom& g, int nbatch, char* scratch, hipStream_t stream);
 hipError_t launch_points_grad_reduce(const PointsGradCall& c, hipStream_t stream);
+hipError_t launch_points_grad_finish(const GridGeom& g, int nbatch, const BatchArray& ddisp, const BatchArray& dK,
+                                     char* scratch, bool own_bounds, hipStream_t stream);
 
 // Label-aware linear resampling of label maps (deform_vote.hip): per output voxel the order-1 weights are summed per
 // distinct label among the 2^naxis source voxels, the label with the largest sum is stored (ties: the smallest label).

@@ -1,7 +1,8 @@
 // ed_points.h -- what the kernels of deform_points.hip (the coordinate map at real positions and its inverse), of
 // deform_points_grad.hip (their adjoint) and of deform_unwarp.hip / deform_unwarp_grad.hip (an image resampled back
-// through the deformation, and the adjoint of that) share: the argument block, the control grid's readers, the separable tap sum, r(q) with its Jacobian, the n x n solve
-// and the damped Newton inversion.  Notation: the head of deform_points.hip.
+// through the deformation, and the adjoint of that) share: the argument block, the launch shape, the control grid's
+// readers, the position load and the tap strides, the separable tap sum, r(q) with its Jacobian, the n x n solve and
+// the damped Newton inversion.  Notation: the head of deform_points.hip.
 #pragma once
 
 #include <cmath>
@@ -77,6 +78,14 @@ inline void unpack(const BatchArray& s, P*& ptr, int64_t& stride, int64_t& bstri
     bstride = s.bstride;
 }
 
+// the launch shape of the per-point kernels: blocks of kPointsThreads over the points of one sample (a grid-stride
+// loop beyond kPointsMaxBlocks of them), blockIdx.y = sample
+inline dim3 points_grid(int64_t npts, int nbatch)
+{
+    const int64_t want = (npts + kPointsThreads - 1) / kPointsThreads;
+    return dim3((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
+}
+
 constexpr int ipow4(int e) { return e == 0 ? 1 : 4 * ipow4(e - 1); }
 
 // a[t] for a runtime t without indexing a register array dynamically
@@ -107,6 +116,35 @@ struct GlobalGrid {
         return load_as_double(base + h * hstride + off, dtype);
     }
 };
+
+// point i of a sample's positions (`pts`: the sample's first row), widened to fp64
+template <int N>
+__device__ __forceinline__ void load_point(const PointsArgs& a, const char* pts, int64_t i, double (&q)[N])
+{
+#pragma unroll
+    for (int h = 0; h < N; ++h) {
+        const char* src = pts + i * a.pts_stride[0] + h * a.pts_stride[1];
+        q[h] = a.pts_f32 ? (double)*(const float*)src : *(const double*)src;
+    }
+}
+
+// tap strides of the evaluator: elements of the LDS copy (C order), or bytes of the caller's grid
+template <int N, bool LDS>
+__device__ __forceinline__ void grid_tap_strides(const GridGeom& g, int64_t (&tstride)[N])
+{
+    if constexpr (LDS) {
+        int64_t cs = 1;
+#pragma unroll
+        for (int k = N - 1; k >= 0; --k) {
+            tstride[k] = cs;
+            cs *= g.ncp[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            tstride[k] = g.disp_stride[k + 1];
+    }
+}
 
 // Separable tap sum over grid axes D..N-1 (every loop unrolled but the outermost of three):
 //   v     = sum_t C[t] prod_e w_e

@@ -22,9 +22,11 @@ struct PointsJetCall {
 hipError_t launch_deform_points_derivatives(const PointsJetCall& c, hipStream_t stream);
 
 // The adjoint for the cotangents u = dL/dr, A = dL/dJ, G = dL/dH (any of them empty): the per-point rows dL/dq, the
-// gradient with respect to the prefiltered grid and with respect to the inverse map K.  Sums are 64-bit integer fixed
-// point (order-independent bits).  The call clears its scratch itself: [per sample kGradHead words | per sample
-// naxis (naxis + 1) + naxis prod ncp cells], points_jet_scratch_bytes() bytes from the caller.  Four launches.
+// gradient with respect to the prefiltered grid and with respect to the inverse map K.  The sums go through the
+// fixed-point reduction of ed_points_grad.h (order-independent bits), with its rule of own bounds: each of the two
+// quanta has a state of its own.  The call clears its scratch itself: [per sample kGradHead words | per sample
+// naxis (naxis + 1) + naxis prod ncp cells] and no u rows, points_jet_scratch_bytes() bytes from the caller.  Four
+// launches.
 struct PointsJetGradCall {
     GridGeom g;
     int nbatch;

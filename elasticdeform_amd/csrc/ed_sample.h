@@ -58,6 +58,8 @@ template <int N, bool LDS>
 __device__ __forceinline__ bool sample_point(const PointsArgs& a, const double* s_grid, const SampleFront<N>& f,
                                              const int64_t b, const int64_t i, double (&r)[N])
 {
+    // (load_point's lines and, above, grid_tap_strides', kept inline: through the helpers of ed_points.h the two sample
+    // kernels come out with another register allocation; DESIGN.md, "One copy of the reduction")
     const char* pts = a.pts + b * a.pts_bstride + i * a.pts_stride[0];
     double q[N], J[N][N];
 #pragma unroll
@@ -74,13 +76,6 @@ __device__ __forceinline__ bool sample_point(const PointsArgs& a, const double* 
     for (int h = 0; h < N; ++h)
         ok = ok && isfinite(r[h]);
     return ok;
-}
-
-// the launch shape of both kernels: points_kernel's
-inline dim3 sample_grid(int64_t npts, int nbatch)
-{
-    const int64_t want = (npts + kPointsThreads - 1) / kPointsThreads;
-    return dim3((unsigned)(want < kPointsMaxBlocks ? want : kPointsMaxBlocks), (unsigned)nbatch);
 }
 
 // the checks both launchers make, and what they fill alike; hipSuccess with *launch false: nothing to launch

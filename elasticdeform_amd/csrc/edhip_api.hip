@@ -126,6 +126,67 @@ bool has_shape(const edhip_array* a, int ndim, const int64_t* shape)
 
 bool f32_or_f64(const edhip_array* a) { return a->dtype == EDHIP_F32 || a->dtype == EDHIP_F64; }
 
+// an optional per-point array of rank `ndim`: (N, naxis, ...), float64 only or float32 / float64
+int check_point_rows(const edhip_array* a, const char* name, int ndim, const int64_t* rows, bool f64_only, char* err,
+                     size_t errlen)
+{
+    if (!a)
+        return EDHIP_OK;
+    if (!has_shape(a, ndim, rows))
+        return fail(err, errlen, EDHIP_ERR_INVALID, "%s must have shape (N%s)", name,
+                    ndim == 2 ? ", naxis" : ndim == 3 ? ", naxis, naxis" : ", naxis, naxis, naxis");
+    if (f64_only ? a->dtype != EDHIP_F64 : !f32_or_f64(a))
+        return fail(err, errlen, EDHIP_ERR_DTYPE, f64_only ? "%s must be float64" : "%s must be float32 or float64",
+                    name);
+    return EDHIP_OK;
+}
+
+// the dtype rules of ddisplacement, by entry
+bool f32_or_f64_dtype(int dt) { return dt == EDHIP_F32 || dt == EDHIP_F64; }
+bool floating_dtype(int dt) { return dt == EDHIP_F16 || dt == EDHIP_BF16 || f32_or_f64_dtype(dt); }
+const char* const kFloatingDdisp = "ddisplacement must have a floating-point dtype";
+
+// The two sums a gradient entry leaves, each optional: ddisplacement with the shape of the (checked) displacement and
+// a dtype the entry takes -- `ddisp_dtype`, refused with `ddisp_dtype_message` --, dinverse_affine float64
+// (naxis, naxis + 1).
+int check_gradient_outputs(const edhip_array* ddisplacement, const edhip_array* displacement, bool (*ddisp_dtype)(int),
+                           const char* ddisp_dtype_message, const edhip_array* dinverse_affine, int naxis, char* err,
+                           size_t errlen)
+{
+    if (ddisplacement) {
+        if (!has_shape(ddisplacement, displacement->ndim, displacement->shape))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
+        if (!ddisp_dtype(ddisplacement->dtype))
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "%s", ddisp_dtype_message);
+    }
+    if (dinverse_affine) {
+        const int64_t map[2] = {naxis, naxis + 1};
+        if (!has_shape(dinverse_affine, 2, map))
+            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
+        if (dinverse_affine->dtype != EDHIP_F64)
+            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
+    }
+    return EDHIP_OK;
+}
+
+// The tail of the point-gradient entries: `bytes` of the stream's workspace, behind its grid head, as the call's
+// scratch; then the launch, reported as `what`.
+template <typename Call>
+int launch_with_scratch(Call& c, size_t bytes, hipError_t (*launch)(const Call&, hipStream_t), const char* what,
+                        hipStream_t stream, char* err, size_t errlen)
+{
+    ed::StreamGuard guard(stream);
+    hipError_t e = hipSuccess;
+    char* ws = (char*)ed::workspace_reserve(stream, ed::kWorkspaceGridBytes + bytes, &e);
+    if (!ws)
+        return hip_fail(err, errlen, e, "scratch allocation");
+    c.scratch = ws + ed::kWorkspaceGridBytes;
+    e = launch(c, stream);
+    if (e != hipSuccess)
+        return hip_fail(err, errlen, e, what);
+    return EDHIP_OK;
+}
+
 // the optional solved-mask of the inverse direction: uint8 (npts)
 int check_status(const edhip_array* status, bool inverse, int64_t npts, char* err, size_t errlen)
 {
@@ -1127,21 +1188,9 @@ static int dgrad_impl(int ninputs, const edhip_array* inputs, const edhip_array*
         return st;
     if (!ddisplacement && !dinverse_affine)
         return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
-    if (ddisplacement) {
-        if (ddisplacement->ndim != displacement->ndim)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        for (int k = 0; k <= naxis; ++k)
-            if (ddisplacement->shape[k] != displacement->shape[k])
-                return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        if (!dtype_ok(ddisplacement->dtype))
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    }
-    if (dinverse_affine) {
-        if (dinverse_affine->ndim != 2 || dinverse_affine->shape[0] != naxis || dinverse_affine->shape[1] != naxis + 1)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
-        if (dinverse_affine->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
-    }
+    if (int st = check_gradient_outputs(ddisplacement, displacement, dtype_ok, "data type not supported",
+                                        dinverse_affine, naxis, err, errlen))
+        return st;
     const bool raw = (flags & EDHIP_FLAG_RAW_DISPLACEMENT) != 0;
     if (raw && points > 4096)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "raw displacement grids are limited to 4096 points");
@@ -1374,14 +1423,10 @@ int edhip_deform_points(int inverse, int nbatch, const edhip_array* points0, int
         return fail(err, errlen, EDHIP_ERR_INVALID, "result must have the shape of points");
     if (!f32_or_f64(points0) || !f32_or_f64(result0))
         return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
-    if (jacobian0) {
-        if (inverse)
-            return fail(err, errlen, EDHIP_ERR_INVALID, "the jacobian belongs to the forward direction");
-        if (!has_shape(jacobian0, 3, rows))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "jacobian must have shape (N, naxis, naxis)");
-        if (jacobian0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "jacobian must be float64");
-    }
+    if (jacobian0 && inverse)
+        return fail(err, errlen, EDHIP_ERR_INVALID, "the jacobian belongs to the forward direction");
+    if (int st = check_point_rows(jacobian0, "jacobian", 3, rows, true, err, errlen))
+        return st;
     if (int st = check_status(status0, inverse != 0, npts, err, errlen))
         return st;
     if (inverse)
@@ -1439,7 +1484,7 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
     if (positions0->ndim != 2 || positions0->shape[1] != naxis || positions0->shape[0] < 0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "positions must have shape (N, naxis)");
     const int64_t npts = positions0->shape[0];
-    const int64_t rows[2] = {npts, naxis}, map[2] = {naxis, naxis + 1};
+    const int64_t rows[2] = {npts, naxis};
     if (!has_shape(cotangent0, 2, rows))
         return fail(err, errlen, EDHIP_ERR_INVALID, "cotangent must have the shape of positions");
     if (!f32_or_f64(positions0) || !f32_or_f64(cotangent0))
@@ -1454,19 +1499,9 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
         if (!f32_or_f64(dpoints0))
             return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     }
-    if (ddisplacement0) {
-        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        const int dt = ddisplacement0->dtype;
-        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
-    }
-    if (dinverse_affine0) {
-        if (!has_shape(dinverse_affine0, 2, map))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
-        if (dinverse_affine0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
-    }
+    if (int st = check_gradient_outputs(ddisplacement0, displacement0, floating_dtype, kFloatingDdisp,
+                                        dinverse_affine0, naxis, err, errlen))
+        return st;
     if (int st = check_batch_limit("edhip_deform_points_gradient", nbatch, err, errlen))
         return st;
     PointsGradCall c;
@@ -1485,17 +1520,9 @@ int edhip_deform_points_gradient(int inverse, int nbatch, const edhip_array* pos
     c.dpts = batch_array(dpoints0, dpoints_batch_stride);
     c.ddisp = batch_array(ddisplacement0, ddisplacement_batch_stride);
     c.dK = batch_array(dinverse_affine0, dinverse_affine_batch_stride);
-    // cells, maxima, flags and the per-point u rows: the stream's workspace, behind its grid head
-    StreamGuard guard(stream);
-    hipError_t e = hipSuccess;
-    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + points_grad_scratch_bytes(c.g, nbatch, npts), &e);
-    if (!ws)
-        return hip_fail(err, errlen, e, "scratch allocation");
-    c.scratch = ws + kWorkspaceGridBytes;
-    e = launch_deform_points_gradient(c, stream);
-    if (e != hipSuccess)
-        return hip_fail(err, errlen, e, "deform points gradient launch");
-    return EDHIP_OK;
+    // heads, cells and the per-point u rows
+    return launch_with_scratch(c, points_grad_scratch_bytes(c.g, nbatch, npts), launch_deform_points_gradient,
+                               "deform points gradient launch", stream, err, errlen);
 }
 
 // ---- r, J = dr/dq and H = d^2r/dq dq at real positions, and their adjoint (deform_points_jet.hip) -------------------
@@ -1507,21 +1534,6 @@ int check_axes_jet(const char* entry, int naxis, char* err, size_t errlen)
         return st;
     if (naxis > 3)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED, "%s takes 1 to 3 deformed axes", entry);
-    return EDHIP_OK;
-}
-
-// an optional per-point array of rank `ndim`: (N, naxis, ...), float64 only or float32 / float64
-int check_point_rows(const edhip_array* a, const char* name, int ndim, const int64_t* rows, bool f64_only, char* err,
-                     size_t errlen)
-{
-    if (!a)
-        return EDHIP_OK;
-    if (!has_shape(a, ndim, rows))
-        return fail(err, errlen, EDHIP_ERR_INVALID, "%s must have shape (N%s)", name,
-                    ndim == 2 ? ", naxis" : ndim == 3 ? ", naxis, naxis" : ", naxis, naxis, naxis");
-    if (f64_only ? a->dtype != EDHIP_F64 : !f32_or_f64(a))
-        return fail(err, errlen, EDHIP_ERR_DTYPE, f64_only ? "%s must be float64" : "%s must be float32 or float64",
-                    name);
     return EDHIP_OK;
 }
 
@@ -1605,7 +1617,7 @@ int edhip_deform_points_derivatives_gradient(int nbatch, const edhip_array* posi
     if (positions0->ndim != 2 || positions0->shape[1] != naxis || positions0->shape[0] < 0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "positions must have shape (N, naxis)");
     const int64_t npts = positions0->shape[0];
-    const int64_t rows[4] = {npts, naxis, naxis, naxis}, map[2] = {naxis, naxis + 1};
+    const int64_t rows[4] = {npts, naxis, naxis, naxis};
     if (!f32_or_f64(positions0))
         return fail(err, errlen, EDHIP_ERR_DTYPE, "data type not supported");
     if (int st = check_point_rows(dresult0, "dresult", 2, rows, false, err, errlen))
@@ -1618,19 +1630,9 @@ int edhip_deform_points_derivatives_gradient(int nbatch, const edhip_array* posi
         return st;
     if (int st = check_point_rows(dpoints0, "dpoints", 2, rows, false, err, errlen))
         return st;
-    if (ddisplacement0) {
-        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        const int dt = ddisplacement0->dtype;
-        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
-    }
-    if (dinverse_affine0) {
-        if (!has_shape(dinverse_affine0, 2, map))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
-        if (dinverse_affine0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
-    }
+    if (int st = check_gradient_outputs(ddisplacement0, displacement0, floating_dtype, kFloatingDdisp,
+                                        dinverse_affine0, naxis, err, errlen))
+        return st;
     if (int st = check_batch_limit("edhip_deform_points_derivatives_gradient", nbatch, err, errlen))
         return st;
     PointsJetGradCall c;
@@ -1649,17 +1651,9 @@ int edhip_deform_points_derivatives_gradient(int nbatch, const edhip_array* posi
     c.dpts = batch_array(dpoints0, dpoints_batch_stride);
     c.ddisp = batch_array(ddisplacement0, ddisplacement_batch_stride);
     c.dK = batch_array(dinverse_affine0, dinverse_affine_batch_stride);
-    // heads and cells: the stream's workspace, behind its grid head
-    StreamGuard guard(stream);
-    hipError_t e = hipSuccess;
-    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + points_jet_scratch_bytes(c.g, nbatch), &e);
-    if (!ws)
-        return hip_fail(err, errlen, e, "scratch allocation");
-    c.scratch = ws + kWorkspaceGridBytes;
-    e = launch_deform_points_derivatives_gradient(c, stream);
-    if (e != hipSuccess)
-        return hip_fail(err, errlen, e, "deform points derivatives gradient launch");
-    return EDHIP_OK;
+    // heads and cells
+    return launch_with_scratch(c, points_jet_scratch_bytes(c.g, nbatch), launch_deform_points_derivatives_gradient,
+                               "deform points derivatives gradient launch", stream, err, errlen);
 }
 
 // ---- label-aware linear resampling of label maps (deform_vote.hip) --------------------------------------------
@@ -1896,20 +1890,9 @@ int edhip_deform_inverse_transform_gradient(int nbatch, const edhip_array* input
         return st;
     if (!ddisplacement0 && !dinverse_affine0)
         return fail(err, errlen, EDHIP_ERR_INVALID, "neither ddisplacement nor dinverse_affine is requested");
-    if (ddisplacement0) {
-        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        const int dt = ddisplacement0->dtype;
-        if (dt != EDHIP_F16 && dt != EDHIP_BF16 && dt != EDHIP_F32 && dt != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must have a floating-point dtype");
-    }
-    if (dinverse_affine0) {
-        const int64_t map[2] = {naxis, naxis + 1};
-        if (!has_shape(dinverse_affine0, 2, map))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
-        if (dinverse_affine0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
-    }
+    if (int st = check_gradient_outputs(ddisplacement0, displacement0, floating_dtype, kFloatingDdisp,
+                                        dinverse_affine0, naxis, err, errlen))
+        return st;
     if (!launch)
         return EDHIP_OK;
     // heads, cells and the per-voxel u and q rows: the stream's workspace, behind its grid head
@@ -2101,13 +2084,9 @@ int edhip_deform_sample_gradient(int nbatch, const edhip_array* input0, int64_t 
             return fail(err, errlen, EDHIP_ERR_DTYPE, "dinput and cotangent must have one dtype");
         make_sample_view(*dinput0, *cotangent0, naxis, axis, order, mode, 0.0, acc);
     }
-    if (dcoordinate0) {
-        const int64_t rows[2] = {c.npts, naxis};
-        if (!has_shape(dcoordinate0, 2, rows))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dcoordinate must have shape (N, naxis)");
-        if (dcoordinate0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dcoordinate must be float64");
-    }
+    const int64_t rows[2] = {c.npts, naxis};
+    if (int st = check_point_rows(dcoordinate0, "dcoordinate", 2, rows, true, err, errlen))
+        return st;
     if (nbatch == 0 || c.npts == 0 || c.v.nsteps <= 0)
         return EDHIP_OK;
     if (!input0)
@@ -2146,19 +2125,9 @@ static int fill_jacobian_call(const char* entry, int nbatch, const edhip_array* 
         return fail(err, errlen, EDHIP_ERR_DTYPE, "%s must be float32 or float64", name);
     if (int st = check_displacement(displacement0, naxis, nullptr, err, errlen))
         return st;
-    if (ddisplacement0) {
-        if (!has_shape(ddisplacement0, displacement0->ndim, displacement0->shape))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "ddisplacement must have the shape of displacement");
-        if (!f32_or_f64(ddisplacement0))
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "ddisplacement must be float32 or float64");
-    }
-    if (dinverse_affine0) {
-        const int64_t map[2] = {naxis, naxis + 1};
-        if (!has_shape(dinverse_affine0, 2, map))
-            return fail(err, errlen, EDHIP_ERR_INVALID, "dinverse_affine must have shape (naxis, naxis + 1)");
-        if (dinverse_affine0->dtype != EDHIP_F64)
-            return fail(err, errlen, EDHIP_ERR_DTYPE, "dinverse_affine must be float64");
-    }
+    if (int st = check_gradient_outputs(ddisplacement0, displacement0, f32_or_f64_dtype,
+                                        "ddisplacement must be float32 or float64", dinverse_affine0, naxis, err, errlen))
+        return st;
     if (int st = check_batch_limit(entry, nbatch, err, errlen))
         return st;
     memset(&c, 0, sizeof(c));

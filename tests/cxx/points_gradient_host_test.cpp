@@ -4,7 +4,8 @@
 // live in global memory, non-finite and huge positions, non-finite cotangents, unsolved points and 1 to 5 axes.  Every
 // array is a heap block of exactly the promised size, so a read or write beyond it is a report.  Also checked: the
 // sums against what they must add up to (sum_j dP[h, j] = sum_i u[i, h], dK = u^T [q, 1]), exact bit equality after
-// reversing the points, zero rows for points that contribute nothing.
+// reversing the points, zero rows for points that contribute nothing, and a bound that overflows (NaN in both sums, in
+// its own sample alone).
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -x c++ \
 //       -Itests/cxx/host_hip -Ielasticdeform_amd/csrc -Iinclude tests/cxx/points_gradient_host_test.cpp -o t && ./t
@@ -229,8 +230,96 @@ static void one_case(int n, int ncp, int64_t npts, int inverse)
         CHECK(v == 0.0);
 }
 
+// The bound rule of this call: bP = 2 N max|u| and bK = bP max(1, max|q|); bP > 0 with a bK that overflows makes
+// BOTH outputs of the sample NaN.  One sample, two axes, a 4 x 4 grid on an 8 x 8 image, float64, one point at
+// (100, 0.5) -- sane: the limit is a control coordinate of 4e15 -- with the cotangent (4e307, 0): bP = 8e307 is
+// finite, bK = bP * 100 is not.  The point's own row J^T u stays finite.  In a batch the overflow poisons its own
+// sample only: a second sample with the cotangent (1, 0) gives the bits of a call of its own.
+struct Overflow {
+    double rows[4], dP[64], dK[12];
+};
+
+static Overflow overflow_run(int nbatch, const double* cot_of_sample)
+{
+    using namespace ed;
+    const int n = 2, ncp = 4, values = n * ncp * ncp;
+    Block<double> grid((size_t)nbatch * values), pos((size_t)nbatch * n), cot((size_t)nbatch * n);
+    Block<double> rows((size_t)nbatch * n), dP((size_t)nbatch * values), dK((size_t)nbatch * n * (n + 1));
+    uint64_t seed = 11;
+    for (int e = 0; e < values; ++e) {
+        const double v = uniform(seed) - 0.5;
+        for (int b = 0; b < nbatch; ++b)
+            grid[b * values + e] = v;
+    }
+    for (int b = 0; b < nbatch; ++b) {
+        pos[b * n] = 100.0, pos[b * n + 1] = 0.5;
+        cot[b * n] = cot_of_sample[b], cot[b * n + 1] = 0.0;
+    }
+    PointsGradCall call;
+    memset(&call, 0, sizeof(call));
+    GridGeom& g = call.g;
+    g.naxis = n;
+    g.disp_dtype = EDHIP_F64;
+    g.disp = (const char*)grid.p;
+    for (int k = 0; k < n; ++k) {
+        g.in_len[k] = g.out_len[k] = 8;
+        g.ncp[k] = ncp;
+    }
+    g.disp_stride[0] = ncp * ncp * 8, g.disp_stride[1] = ncp * 8, g.disp_stride[2] = 8;
+    call.nbatch = nbatch;
+    call.npts = 1;
+    call.disp_bstride = values * 8;
+    call.pos.ptr = (char*)pos.p;
+    call.cot.ptr = (char*)cot.p;
+    call.dpts.ptr = (char*)rows.p;
+    call.pos.dtype = call.cot.dtype = call.dpts.dtype = call.ddisp.dtype = EDHIP_F64;
+    call.pos.stride[0] = call.cot.stride[0] = call.dpts.stride[0] = n * 8;
+    call.pos.stride[1] = call.cot.stride[1] = call.dpts.stride[1] = 8;
+    call.pos.bstride = call.cot.bstride = call.dpts.bstride = n * 8;
+    call.ddisp.ptr = (char*)dP.p;
+    call.ddisp.stride[0] = ncp * ncp * 8, call.ddisp.stride[1] = ncp * 8, call.ddisp.stride[2] = 8;
+    call.ddisp.bstride = values * 8;
+    call.dK.ptr = (char*)dK.p;
+    call.dK.stride[0] = (n + 1) * 8, call.dK.stride[1] = 8;
+    call.dK.bstride = n * (n + 1) * 8;
+    Block<char> scratch(points_grad_scratch_bytes(g, nbatch, 1));
+    memset(scratch.p, 0xff, scratch.n);
+    call.scratch = scratch.p;
+    CHECK(launch_deform_points_gradient(call, nullptr) == hipSuccess);
+    Overflow r;
+    memset(&r, 0, sizeof(r));
+    memcpy(r.rows, rows.p, rows.n * 8);
+    memcpy(r.dP, dP.p, dP.n * 8);
+    memcpy(r.dK, dK.p, dK.n * 8);
+    return r;
+}
+
+static void overflowing_bound()
+{
+    const double huge[2] = {4e307, 1.0}, one[1] = {1.0};
+    const Overflow x = overflow_run(1, huge), both = overflow_run(2, huge), alone = overflow_run(1, one);
+    for (int e = 0; e < 32; ++e)
+        CHECK(x.dP[e] != x.dP[e]);
+    for (int e = 0; e < 6; ++e)
+        CHECK(x.dK[e] != x.dK[e]);
+    CHECK(std::isfinite(x.rows[0]) && std::isfinite(x.rows[1]));
+    // the batch: sample 0 as the single call, sample 1 the bits of its own call (finite, not all zero)
+    CHECK(memcmp(both.dP, x.dP, 32 * 8) == 0 && memcmp(both.dK, x.dK, 6 * 8) == 0);
+    CHECK(memcmp(both.rows, x.rows, 2 * 8) == 0);
+    CHECK(memcmp(both.dP + 32, alone.dP, 32 * 8) == 0 && memcmp(both.dK + 6, alone.dK, 6 * 8) == 0);
+    CHECK(memcmp(both.rows + 2, alone.rows, 2 * 8) == 0);
+    double sum = 0.0;
+    for (int e = 0; e < 32; ++e) {
+        CHECK(std::isfinite(alone.dP[e]));
+        sum += alone.dP[e];
+    }
+    CHECK(fabs(sum - 1.0) <= 1e-12);
+    CHECK(alone.dK[0] == 100.0 && alone.dK[1] == 0.5 && alone.dK[2] == 1.0);
+}
+
 int main()
 {
+    overflowing_bound();
     for (int inverse = 0; inverse < 2; ++inverse) {
         for (int n = 1; n <= 5; ++n)
             one_case(n, 2, n <= 3 ? 700 : 60, inverse);      // the folded two-point grid: every window is mirrored

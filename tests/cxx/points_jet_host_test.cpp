@@ -1,6 +1,6 @@
-// Host-only run of the kernels of csrc/deform_points_jet.hip (points_jet_kernel, points_jet_grad_clear / _prepare /
-// _scatter / _finish) under AddressSanitizer and UndefinedBehaviorSanitizer: the device functions compiled as plain C++
-// against the stand-in runtime of tests/cxx/host_hip (one emulated thread per workgroup, dynamic LDS poisoned beyond the
+// Host-only run of the kernels of csrc/deform_points_jet.hip (points_jet_kernel, points_jet_grad_prepare / _scatter,
+// with points_grad_clear / _finish of csrc/deform_points_grad.hip at their two ends) under AddressSanitizer and
+// UndefinedBehaviorSanitizer: the device functions compiled as plain C++ against the stand-in runtime of tests/cxx/host_hip (one emulated thread per workgroup, dynamic LDS poisoned beyond the
 // launch's size).  Every array is a heap block of exactly the promised size, so a read or write beyond it is a report.
 // Cases, with 1, 2 and 3 axes each: the two-point grid (every tap folds), a grid read from global memory (more than
 // kPointsLdsValues values), N = 1, a crop offset with an affine map, two samples; positions on knots, outside the
@@ -9,7 +9,8 @@
 // the forward without H against the forward with it (same bits), dP against step-1 differences of
 // L = sum u r + A J + G H (exact up to rounding: L is linear in every grid value), dK against its plain sum, the rows dq
 // against central differences of L away from the knots, zero rows for points that contribute nothing, NaN sums after a
-// non-finite cotangent, zeros for N = 0, and bit-equal results from two runs and for both samples.
+// non-finite cotangent, zeros for N = 0, bit-equal results from two runs and for both samples, and a bound that
+// overflows (NaN in dinverse_affine alone, and in its own sample alone).
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -x c++ \
 //       -Itests/cxx/host_hip -Ielasticdeform_amd/csrc -Iinclude tests/cxx/points_jet_host_test.cpp -o t && ./t
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "deform_points_jet.hip"
+#include "deform_points_grad.hip"                // points_grad_clear / _finish: the reduction's two ends live there
 
 namespace ed {
 namespace {
@@ -477,8 +479,99 @@ static void no_points(const Case& c)
     CHECK(f.r.empty() && f.H.empty());
 }
 
+// The bound rule of this call: the head holds bP and bK themselves and each quantum has its own state, so a bK that
+// overflows makes dK NaN and leaves dP finite.  One sample, two axes, a 4 x 4 grid on an 8 x 8 image, float64, one
+// point at (100, 0.5) -- sane: the limit is a control coordinate of 4e15 -- with u = (4e307, 0) and no A, no G:
+// bP = 4e307 gives a finite 2 N bP, bK = |u_0 q_0| = 4e309 is not finite.  dP[h, j] is u_h beta(q, j) to the quantum
+// 2^(1023 - 62) -- at most four taps of this point fold into one cell, half a quantum each -- and to the rounding of
+// the products in fp64 (beta is formed here from plainly evaluated weights: 64 ulp of 4e307 is generous).  In a batch
+// the overflow poisons its own sample only: a second sample with u = (1, 0) gives the bits of a call of its own.
+static Adjoint overflow_run(int nbatch, const double* u0_of_sample)
+{
+    using namespace ed;
+    const Case c = {2, {4, 4}, {8, 8}, {0, 0}, false};
+    const int n = 2, values = 32;
+    Block<double> gr((size_t)nbatch * values), pts((size_t)nbatch * n), du((size_t)nbatch * n), rows((size_t)nbatch * n);
+    Block<double> dP((size_t)nbatch * values), dK((size_t)nbatch * n * (n + 1));
+    uint64_t seed = 11;
+    for (int e = 0; e < values; ++e) {
+        const double v = uniform(seed) - 0.5;
+        for (int b = 0; b < nbatch; ++b)
+            gr[b * values + e] = v;
+    }
+    for (int b = 0; b < nbatch; ++b) {
+        pts[b * n] = 100.0, pts[b * n + 1] = 0.5;
+        du[b * n] = u0_of_sample[b], du[b * n + 1] = 0.0;
+    }
+    memset(rows.p, 0xff, rows.n * 8);
+    memset(dP.p, 0xff, dP.n * 8);
+    memset(dK.p, 0xff, dK.n * 8);
+    PointsJetGradCall call;
+    memset(&call, 0, sizeof(call));
+    call.g = geometry(c, gr.p);
+    call.nbatch = nbatch;
+    call.npts = 1;
+    call.disp_bstride = values * 8;
+    call.pos = rows_array(pts.p, 2, n, 1);
+    call.du = rows_array(du.p, 2, n, 1);
+    call.dpts = rows_array(rows.p, 2, n, 1);
+    call.ddisp.ptr = (char*)dP.p;
+    call.ddisp.dtype = EDHIP_F64;
+    call.ddisp.stride[0] = 16 * 8, call.ddisp.stride[1] = 4 * 8, call.ddisp.stride[2] = 8;
+    call.ddisp.bstride = values * 8;
+    call.dK.ptr = (char*)dK.p;
+    call.dK.dtype = EDHIP_F64;
+    call.dK.stride[0] = (n + 1) * 8, call.dK.stride[1] = 8;
+    call.dK.bstride = n * (n + 1) * 8;
+    Block<char> scratch(points_jet_scratch_bytes(call.g, nbatch));
+    memset(scratch.p, 0xff, scratch.n);
+    call.scratch = scratch.p;
+    CHECK(launch_deform_points_derivatives_gradient(call, nullptr) == hipSuccess);
+    Adjoint r;
+    r.rows.assign(rows.p, rows.p + rows.n);
+    r.dP.assign(dP.p, dP.p + dP.n);
+    r.dK.assign(dK.p, dK.p + dK.n);
+    return r;
+}
+
+static void overflowing_bound()
+{
+    const double huge[2] = {4e307, 1.0}, one[1] = {1.0};
+    const Adjoint x = overflow_run(1, huge), both = overflow_run(2, huge), alone = overflow_run(1, one);
+    // beta(q, j): the cubic weights of each axis at cp = 3 q / 7, folded onto the four control points
+    double beta[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    const double q[2] = {100.0, 0.5};
+    for (int k = 0; k < 2; ++k) {
+        const double cp = 3.0 * q[k] / 7.0, fl = floor(cp), t = cp - fl, z = 1.0 - t;
+        const double w[4] = {z * z * z / 6, (3 * t * t * t - 6 * t * t + 4) / 6, (3 * z * z * z - 6 * z * z + 4) / 6,
+                             t * t * t / 6};
+        for (int s = 0; s < 4; ++s)
+            beta[k][fold((int64_t)fl - 1 + s, 4)] += w[s];
+    }
+    const double tol = 2.0 * ldexp(1.0, 1023 - 62) + 64.0 * ldexp(4e307, -52);
+    for (int j0 = 0; j0 < 4; ++j0)
+        for (int j1 = 0; j1 < 4; ++j1) {
+            const double got = x.dP[j0 * 4 + j1];
+            CHECK(std::isfinite(got) && fabs(got - 4e307 * (beta[0][j0] * beta[1][j1])) <= tol);
+            CHECK(x.dP[16 + j0 * 4 + j1] == 0.0);
+        }
+    for (double v : x.dK)
+        CHECK(v != v);
+    CHECK(std::isfinite(x.rows[0]) && std::isfinite(x.rows[1]));
+    // the batch: sample 0 as the single call, sample 1 the bits of its own call
+    CHECK(memcmp(both.dP.data(), x.dP.data(), 32 * 8) == 0 && memcmp(both.dK.data(), x.dK.data(), 6 * 8) == 0);
+    CHECK(memcmp(both.rows.data(), x.rows.data(), 2 * 8) == 0);
+    CHECK(memcmp(both.dP.data() + 32, alone.dP.data(), 32 * 8) == 0);
+    CHECK(memcmp(both.dK.data() + 6, alone.dK.data(), 6 * 8) == 0);
+    CHECK(memcmp(both.rows.data() + 2, alone.rows.data(), 2 * 8) == 0);
+    for (int e = 0; e < 16; ++e)
+        CHECK(fabs(alone.dP[e] - beta[0][e / 4] * beta[1][e % 4]) <= 1e-14);
+    CHECK(alone.dK[0] == 100.0 && alone.dK[1] == 0.5 && alone.dK[2] == 1.0);
+}
+
 int main()
 {
+    overflowing_bound();
     const Case two[3] = {{1, {2}, {9}, {0}, false}, {2, {2, 2}, {9, 11}, {1, 0}, true}, {3, {2, 2, 2}, {9, 7, 8}, {0, 2, 1}, true}};
     const Case mid[3] = {{1, {5}, {17}, {3}, true}, {2, {4, 5}, {13, 17}, {2, 3}, true}, {3, {4, 4, 5}, {12, 14, 10}, {1, 0, 2}, false}};
     // more than kPointsLdsValues = 7680 values: the grid is read from, and the cells live in, global memory

@@ -295,3 +295,56 @@ def test_one_descent_step_lowers_the_bending_energy():
     e1 = energy((Dt - step * g).detach(), False)
     print("bending energy %.6g -> %.6g" % (float(e0.detach()), float(e1)))
     assert float(e1) < float(e0.detach())
+
+
+def _library_call(u0):
+    """edhip_deform_points_derivatives_gradient itself on len(u0) samples of one point at (100, 0.5) -- sane: the limit
+    is a control coordinate of 4e15 --, a prefiltered 4 x 4 grid on an 8 x 8 image, float64, d_coordinates (u0[b], 0)
+    for sample b and nothing else: the gradient of the PREFILTERED grid, without the host layer's transposed filter
+    (whose gain would take 4e307 past the largest double)."""
+    api = importlib.import_module("elasticdeform_amd.deform_grid")
+    from elasticdeform_amd import _lib
+    nb = len(u0)
+    P = torch.from_numpy(np.random.default_rng(11).random((2, 4, 4)) - 0.5).cuda().repeat(nb, 1, 1, 1)
+    q = torch.tensor([[100.0, 0.5]], dtype=torch.float64).cuda().repeat(nb, 1, 1)
+    u = torch.tensor([[[v, 0.0]] for v in u0], dtype=torch.float64).cuda()
+    rows, dP = torch.full_like(q, 7.0), torch.full_like(P, 7.0)
+    dK = torch.full((nb, 2, 3), 7.0, dtype=torch.float64).cuda()
+    _lib.deform_points_derivatives_gradient(nb, *api._desc_sample0(q), *api._desc_sample0(u), None, 0, None, 0,
+                                            *api._desc_sample0(P), (8, 8), None, None, *api._desc_sample0(rows),
+                                            *api._desc_sample0(dP), *api._desc_sample0(dK), 0, api._stream(q.device))
+    torch.cuda.synchronize()
+    return rows.cpu().numpy(), dP.cpu().numpy(), dK.cpu().numpy()
+
+
+def test_a_bound_that_overflows_poisons_its_own_sum_of_its_sample_only():
+    """d_coordinates = (4e307, 0) alone: bP = 4e307 gives a finite 2 N bP, bK = |u_0 q_0| = 4e309 is not finite.  This
+    call's rule keeps one state per quantum: dinverse_affine is NaN, ddisplacement is finite and equals u_h beta(q, j)
+    to the quantum 2^(1023 - 62) -- at most four taps of the point fold into one cell, half a quantum each -- and to
+    the rounding of the products in fp64 (beta is formed here from plainly evaluated weights: 64 ulp of 4e307 is
+    generous).  A second sample with d_coordinates (1, 0) in the same call gives the bits of a call of its own."""
+    rows, dP, dK = _library_call([4e307])
+    beta = []
+    for qk in (100.0, 0.5):
+        cp = 3.0 * qk / 7.0
+        fl = int(np.floor(cp))
+        t = cp - fl
+        z = 1.0 - t
+        w = [z ** 3 / 6, (3 * t ** 3 - 6 * t * t + 4) / 6, (3 * z ** 3 - 6 * z * z + 4) / 6, t ** 3 / 6]
+        b = np.zeros(4)
+        for s in range(4):
+            j = (fl - 1 + s) % 6
+            b[6 - j if j >= 4 else j] += w[s]
+        beta.append(b)
+    want = 4e307 * np.outer(beta[0], beta[1])
+    tol = 2.0 * 2.0 ** (1023 - 62) + 64 * 4e307 * 2.0 ** -52
+    err = np.abs(dP[0, 0] - want)
+    print("worst |ddisplacement - u beta| = %.3g, bound %.3g" % (err.max(), tol))
+    assert np.isfinite(dP).all() and (err <= tol).all() and not dP[0, 1].any()
+    assert np.isnan(dK).all() and np.isfinite(rows).all()
+    rows2, dP2, dK2 = _library_call([4e307, 1.0])
+    rows1, dP1, dK1 = _library_call([1.0])
+    assert _same(rows2[0], rows[0]) and _same(dP2[0], dP[0]) and _same(dK2[0], dK[0])
+    assert _same(rows2[1], rows1[0]) and _same(dP2[1], dP1[0]) and _same(dK2[1], dK1[0])
+    assert np.abs(dP1[0, 0] - np.outer(beta[0], beta[1])).max() <= 1e-14
+    assert np.array_equal(dK1[0], [[100.0, 0.5, 1.0], [0.0, 0.0, 0.0]])

@@ -1,6 +1,7 @@
 """
-CPU test of the kernels of csrc/deform_points_jet.hip (points_jet_kernel, points_jet_grad_clear / _prepare / _scatter /
-_finish) as host code under AddressSanitizer and UndefinedBehaviorSanitizer.  tests/cxx/points_jet_host_test.cpp is a
+CPU test of the kernels of csrc/deform_points_jet.hip (points_jet_kernel, points_jet_grad_prepare / _scatter, with
+points_grad_clear / _finish of csrc/deform_points_grad.hip, which the program includes as well, at their two ends) as
+host code under AddressSanitizer and UndefinedBehaviorSanitizer.  tests/cxx/points_jet_host_test.cpp is a
 stand-alone program (its own main, no GPU, no HIP call, not loaded into Python): it compiles the kernels' device
 functions as plain C++ against the stand-in runtime of tests/cxx/host_hip -- workgroups of one emulated thread, dynamic
 LDS poisoned beyond the launch's size -- and runs 1, 2 and 3 axes, the two-point grid, grids read from global memory

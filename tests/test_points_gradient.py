@@ -578,3 +578,38 @@ def test_float32_points_round_once_and_array_families(inverse):
         _same_bits(torch.as_tensor(g.points).cpu().numpy(), want.points)
         _same_bits(torch.as_tensor(g.displacement).cpu().numpy(), want.displacement)
         _same_bits(torch.as_tensor(g.inverse_map).cpu().numpy(), want.inverse_map)
+
+
+def _library_call(u0):
+    """edhip_deform_points_gradient itself (forward direction) on len(u0) samples of one point at (100, 0.5) -- sane:
+    the limit is a control coordinate of 4e15 --, a prefiltered 4 x 4 grid on an 8 x 8 image, float64, the cotangent
+    (u0[b], 0) for sample b: the gradient of the PREFILTERED grid, without the host layer's transposed filter (whose
+    gain would take 4e307 past the largest double)."""
+    import importlib
+    api = importlib.import_module("elasticdeform_amd.deform_grid")
+    from elasticdeform_amd import _lib
+    nb = len(u0)
+    P = torch.from_numpy(np.random.default_rng(11).random((2, 4, 4)) - 0.5).cuda().repeat(nb, 1, 1, 1)
+    q = torch.tensor([[100.0, 0.5]], dtype=torch.float64).cuda().repeat(nb, 1, 1)
+    u = torch.tensor([[[v, 0.0]] for v in u0], dtype=torch.float64).cuda()
+    rows, dP = torch.full_like(q, 7.0), torch.full_like(P, 7.0)
+    dK = torch.full((nb, 2, 3), 7.0, dtype=torch.float64).cuda()
+    _lib.deform_points_gradient(0, nb, *api._desc_sample0(q), *api._desc_sample0(u), None, 0, *api._desc_sample0(P),
+                                (8, 8), None, None, *api._desc_sample0(rows), *api._desc_sample0(dP),
+                                *api._desc_sample0(dK), 0, api._stream(q.device))
+    torch.cuda.synchronize()
+    return rows.cpu().numpy(), dP.cpu().numpy(), dK.cpu().numpy()
+
+
+def test_a_bound_that_overflows_poisons_both_sums_of_its_sample_only():
+    """bP = 2 N max|u| = 8e307 is finite, bK = bP max(1, max|q|) = bP * 100 is not: this call's rule makes BOTH sums
+    of the sample NaN; the point's own row J^T u is finite.  A second sample with the cotangent (1, 0) in the same
+    call gives the bits of a call of its own."""
+    rows, dP, dK = _library_call([4e307])
+    assert np.isnan(dP).all() and np.isnan(dK).all() and np.isfinite(rows).all()
+    rows2, dP2, dK2 = _library_call([4e307, 1.0])
+    rows1, dP1, dK1 = _library_call([1.0])
+    _same_bits(rows2[0], rows[0]), _same_bits(dP2[0], dP[0]), _same_bits(dK2[0], dK[0])
+    _same_bits(rows2[1], rows1[0]), _same_bits(dP2[1], dP1[0]), _same_bits(dK2[1], dK1[0])
+    assert np.isfinite(dP1).all() and abs(dP1[0, 0].sum() - 1.0) <= 1e-12 and not dP1[0, 1].any()
+    assert np.array_equal(dK1[0], [[100.0, 0.5, 1.0], [0.0, 0.0, 0.0]])
