@@ -492,6 +492,25 @@ __device__ __forceinline__ void weights_from_frac2(T x, T* w)
     w[ORDER] = last;
 }
 
+// The weights of the LDS gradient kernels below.  Order 5 in float32: the two outer Horner forms w[1] and w[4] (terms
+// up to 2 in size cancelling down to weights below 0.43) and the last weight, which collects every error, are evaluated
+// in double on the float32 fraction and rounded once.  In float32 they are 8e-7 off (the three others 6e-8 at most),
+// which the transposed prefilter of order 5 raises above the float32 gradient's bound when dY is one isolated pixel
+// (tests/test_fast_routes.py, G5 and G9: 7.2e-7 against 6.2e-7 allowed).
+template <typename T, int ORDER>
+__device__ __forceinline__ void weights_of_frac(T x, T* w)
+{
+    weights_from_frac2<T, ORDER>(x, w);
+    if constexpr (ORDER == 5 && sizeof(T) == 4) {
+        const double y = (double)x + 1.0, zz = 2.0 - (double)x;
+        const double w1 = y * (y * (y * (y * (y * (1.0 / 24.0) - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
+        const double w4 = zz * (zz * (zz * (zz * (zz * (1.0 / 24.0) - 0.375) + 1.25) - 1.75) + 0.625) + 0.425;
+        w[1] = (T)w1;
+        w[4] = (T)w4;
+        w[5] = (T)(1.0 - ((((double)w[0] + w1) + (double)w[2]) + ((double)w[3] + w4)));
+    }
+}
+
 // ================================================================================================
 // K2 in 2-D with an LDS accumulator (float32 / float64, orders 1-5).  The generic kernel above
 // sends every tap to global memory as a float atomic: (order+1)^2 of them per pixel, 268M for a
@@ -682,8 +701,8 @@ __global__ __launch_bounds__(kBlock) void deform_fast2_grad_kernel(const GridGeo
                 // direct global atomics: blocks without a box, inf / NaN gradients
                 if (gval[i] != (T)0) {
                     T w0[NT], w1[NT];
-                    weights_from_frac2<T, ORDER>(fr[i][0], w0);
-                    weights_from_frac2<T, ORDER>(fr[i][1], w1);
+                    weights_of_frac<T, ORDER>(fr[i][0], w0);
+                    weights_of_frac<T, ORDER>(fr[i][1], w1);
 #pragma unroll 1
                     for (int t = 0; t < NT * NT; ++t) {
                         const int l0 = t / NT, l1 = t % NT;
@@ -717,8 +736,8 @@ __global__ __launch_bounds__(kBlock) void deform_fast2_grad_kernel(const GridGeo
             if (gval[i] == (T)0)
                 continue;
             T w0[NT], w1[NT];
-            weights_from_frac2<T, ORDER>(fr[i][0], w0);
-            weights_from_frac2<T, ORDER>(fr[i][1], w1);
+            weights_of_frac<T, ORDER>(fr[i][0], w0);
+            weights_of_frac<T, ORDER>(fr[i][1], w1);
             acc_t* bp = s_box + ((st[i][0] - b0[0]) * pitch + (st[i][1] - b0[1]));
             const T gs = gval[i] * scale;
 #pragma unroll
@@ -943,7 +962,7 @@ __global__ __launch_bounds__(kBlock) void deform_fast4_grad_kernel(const GridGeo
     if (act) {
 #pragma unroll
         for (int h = 0; h < 4; ++h)
-            weights_from_frac2<T, ORDER>(fr[h], w[h]);
+            weights_of_frac<T, ORDER>(fr[h], w[h]);
     }
     // taps of the two slow axes picked with select chains inside rolled loops (fully unrolled: 256 registers)
     auto pick = [&](int h, int l) {
@@ -1078,6 +1097,7 @@ hipError_t launch_typed(const GridGeom& g, const IOView& v, int gradient, hipStr
         }
     }
     // (order 1: 16 taps per voxel -- the row kernel's 16 global atomics are faster, 0.32 against 0.72 ms for 32^4)
+    // (beyond kMaxE4, ncp_x 6 | 7: order 2 goes on to the row kernel below, order 3 never gets here -- deform_fast_supported)
     if constexpr (NAXIS == 4 && ORDER >= 2 && ORDER <= 3) {
         if (gradient && 4 * g.ncp[3] <= kMaxE4 && !ed_env("EDHIP_4D_DIRECT_GRAD")) {
             const int64_t ta = (g.out_len[0] + kT4A - 1) / kT4A, tb = (g.out_len[1] + kT4B - 1) / kT4B,
@@ -1143,6 +1163,7 @@ bool deform_fast_supported(const GridGeom& g, const IOView& v, int gradient)
     // (four axes, order 3, gradient: the LDS-accumulating kernel of round 5 for control grids of up to 6 points along x;
     // beyond that 256 global atomics per voxel on either kernel -- 32^4 float32: 8.0 ms here against 7.1 ms on the exact
     // kernel, which stays in charge)
+    // (24 is kMaxE4, the same ncp_x 6 | 7 boundary as in launch_typed; order 2 beyond it stays here, on the row kernel)
     if (g.naxis == 4 && gradient && v.order == 3 && 4 * g.ncp[3] > 24)
         return false;
     if (v.in_dtype != v.out_dtype)
