@@ -53,6 +53,7 @@
 #include "ed_gridfilter.h"
 #include "ed_workspace.h"
 #include "ed_tile.h"
+#include "ed_tile_host.h"
 
 #ifdef EDHIP_EXPERIMENTS
 // profiling build: control columns the per-strip Q window of a wide grid (TileGeom::q_win) did not hold -- the
@@ -1026,99 +1027,8 @@ __global__ __launch_bounds__(kBlock) void deform_tile3_direct_kernel(const GridG
     }
 }
 
-// ---- host side -------------------------------------------------------------------------------------
-
-inline int ceil_log2(int64_t n)
-{
-    int l = 0;
-    while (((int64_t)1 << l) < n)
-        ++l;
-    return l;
-}
-
-inline size_t q_bytes(const GridGeom& g) { return 8 * (size_t)(kT * kT * 4) * (size_t)g.ncp[2]; }
-// near-tie list of the label kernel: up to 1M voxel ids (4 MiB), never more than the output has
-inline size_t label_list_bytes(const GridGeom& g)
-{
-    int64_t nvox = 1;
-    for (int k = 0; k < 3; ++k)
-        nvox *= g.out_len[k];
-    const int64_t cap = nvox < (1 << 20) ? nvox : (1 << 20);
-    return (size_t)(cap + 32) * sizeof(int) + 64;
-}
-
-// the tile kernels keep a strip's 64 Q rows in LDS next to a 32 KiB box: up to this many control columns
-inline bool wide_grid(const GridGeom& g) { return kOffQ + q_bytes(g) + 16 + 32768 > (size_t)64 * 1024; }
-// wide grids: strips of kWideStripTiles tiles, the columns such a strip touches (conservative; <= kWideMaxWin or the
-// row kernel of deform_fast.hip takes the call)
-constexpr int kWideStripTiles = 4;
-constexpr int kWideMaxWin = 16;
-inline int wide_window(const GridGeom& g)
-{
-    const double r = g.in_len[2] > 1 ? (double)(g.ncp[2] - 1) / (double)(g.in_len[2] - 1) : 0.0;
-    return (int)std::floor(kWideStripTiles * kT * r) + 6;
-}
-// x table + the per-sample margins of K1's sampled boxes (TileGeom::slack) behind it
-inline size_t xt_only_bytes(const GridGeom& g) { return (sizeof(AxTab) * (size_t)g.out_len[2] + 63) & ~(size_t)63; }
-inline size_t xt_block_bytes(const GridGeom& g, int nbatch) { return xt_only_bytes(g) + (((size_t)nbatch * 32 + 63) & ~(size_t)63); }
-// float64 volumes (round 5): the per-strip layout also where the whole grid would still fit next to a box -- with 9 to 14
-// control columns the Q rows take 18-29 KB of LDS, the level-2 kernel is left with half a box of 8-byte cells and a
-// rough deformation sends most tiles to the direct kernel (256^3, 13^3 grid, order 3 gradient: 8.0 ms, of which 6.8 in
-// float64 global atomics; per-strip tables of 7 columns: see profiles/r05_bench_misc.txt).  Worth it when the window is
-// narrower than the grid.
-inline bool wide_optional(const GridGeom& g)
-{
-    if (wide_grid(g))
-        return false;
-    const int win = wide_window(g);
-    const int64_t strips = (g.out_len[2] + kWideStripTiles * kT - 1) / (kWideStripTiles * kT);
-    if (win + 2 > g.ncp[2] || win > kWideMaxWin || strips > 256)
-        return false;
-    return 8.0 * (double)g.out_len[0] * (double)g.out_len[1] * 4.0 * (double)(strips * win) <= (double)((size_t)512 << 20);
-}
-inline size_t q_global_bytes(const GridGeom& g, bool wide_opt = false)
-{
-    size_t cols = (size_t)g.ncp[2];
-    if (wide_grid(g) || (wide_opt && wide_optional(g))) {
-        // Q[o_z][o_y][strip][window][4] (TileGeom::q_win)
-        const size_t strips = (size_t)((g.out_len[2] + kWideStripTiles * kT - 1) / (kWideStripTiles * kT));
-        const size_t per_strip = strips * (size_t)wide_window(g);
-        cols = per_strip > cols ? per_strip : cols;
-    }
-    return 8 * (size_t)g.out_len[0] * (size_t)g.out_len[1] * 4 * cols;
-}
-// The geometry buffer of the forward route of deform_k1z.hip (ed::GeoBuffer, its own allocation), size and layout:
-//   counters (4 KiB, cleared at allocation) | ZGen (512) | z table | the per-tile arrays | step offsets | R per sample
-// Per tile: its record (8 ints), a flag and a summary (1 + 1 per strip, at most one strip per tile), a slot in each of the
-// two work lists dealt per XCD (entry k of XCD x at slot 8 k + x: 8 + 8 per strip, in case one XCD gets them all) and the
-// records of its z halves (16).
-constexpr size_t kK1zMaxSteps = 4096;
-constexpr size_t kK1zRecInts = 8, kK1zMissedInts = 1, kK1zInfoInts = 1, kK1zListInts = 8, kK1zHalfInts = 16;
-constexpr size_t kK1zTileBytes = sizeof(int) * (kK1zRecInts + kK1zMissedInts + kK1zInfoInts + 2 * kK1zListInts + kK1zHalfInts);
-struct K1zGeoLayout {
-    size_t zgen, zt, recs, missed, sinfo, list_g, list_f, recs_half, steps, r;   // byte offsets
-    size_t r_stride;      // bytes between the R tables of consecutive samples
-    size_t total;
-};
-inline K1zGeoLayout k1z_geo_layout(const GridGeom& g, int64_t ntiles, int nbatch)
-{
-    auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t nt = (size_t)ntiles * (size_t)nbatch;
-    K1zGeoLayout l;
-    l.zgen = 4096;
-    l.zt = l.zgen + 512;
-    l.recs = l.zt + pad64(sizeof(AxTab) * (size_t)g.out_len[0]);
-    l.missed = l.recs + nt * kK1zRecInts * sizeof(int);
-    l.sinfo = l.missed + nt * kK1zMissedInts * sizeof(int);
-    l.list_g = l.sinfo + nt * kK1zInfoInts * sizeof(int);
-    l.list_f = l.list_g + nt * kK1zListInts * sizeof(int);
-    l.recs_half = l.list_f + nt * kK1zListInts * sizeof(int);
-    l.steps = l.recs + pad64(nt * kK1zTileBytes);
-    l.r = l.steps + kK1zMaxSteps * 2 * sizeof(long long);
-    l.r_stride = pad64(k1z_r_bytes(g));
-    l.total = l.r + l.r_stride * (size_t)nbatch;
-    return l;
-}
+// ---- host side (the scratch layout, the wide-grid decision, the addressing limits and the strip lengths:
+//      ed_tile_host.h) ------------------------------------------------------------------------------
 
 // margin of the sampled tile boxes (deform_k1.hip, deform_k1z.hip): 15 % of the rigorous bound of multilinear
 // interpolation between samples (see the tables kernel) -- everything of it but the largest control coefficient
@@ -1380,22 +1290,124 @@ void fill_hot_geom(HotGeom& hg, const TileGeom& tg, const IOView& ve, const IOVi
         hg.affine[k] = tg.affine[k];
 }
 
-template <typename T, int ORDER, bool PAIR, bool GRAD>
-hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, const DeformBatch* batch)
+// The argument block of the z-walk route (deform_k1z.hip) on its geometry buffer `gb`, laid out as `gl`; the parity of
+// the work lists' counters and the launches are the caller's.
+void fill_zgeom(ZGeom& zg, const GridGeom& g, const TileGeom& tg, int order, char* gb, const K1zGeoLayout& gl)
 {
-    TileGeom tg;
-    IOView ve = v;
+    memset(&zg, 0, sizeof(zg));
+    zg.slack_scale = box_margin_scale(g);
+    zg.ctl = (int*)gb;                       // the lists' counters: 32 ints in the cleared head
+    zg.zgen = gb + gl.zgen;
+    zg.zt = (const AxTab*)(gb + gl.zt);
+    zg.recs = (int*)(gb + gl.recs);
+    zg.missed = (int*)(gb + gl.missed);
+    zg.sinfo = (int*)(gb + gl.sinfo);
+    zg.list_g = (int*)(gb + gl.list_g);
+    zg.list_f = (int*)(gb + gl.list_f);
+    zg.recs_half = (int*)(gb + gl.recs_half);
+    zg.steps = (long long*)(gb + gl.steps);
+    zg.r = (const double*)(gb + gl.r);
+    zg.r_bstride = (long long)(gl.r_stride / 8);
+    zg.disp_bstride = tg.disp_bstride;
+    zg.ncpz = (int)g.ncp[0];
+    zg.order = order;
+    // strips of 4 tiles where that leaves the chip enough of them (256^3: 8192); strips of 2 below ~4096 (128^3:
+    // 1024 -> 2048 strips, level-1 launch 45.8 -> 37.0 us; 192^3: 105.8 -> 91.8; at 256^3 strips of 2 cost 6 %);
+    // single tiles only for volumes that have fewer than 1024 pairs (profiles/r06_k1_route_sweep.txt)
+    const int64_t across = (int64_t)tg.tiles[1] * tg.tiles[2];
+    zg.strip_tiles = 4;
+    if (strip_count(tg.nbatch, across, tg.tiles[0], 4) < 4096)
+        zg.strip_tiles = 2;
+    if (strip_count(tg.nbatch, across, tg.tiles[0], 2) < 1024)
+        zg.strip_tiles = 1;
+#ifdef EDHIP_EXPERIMENTS
+    if (const char* st = ed_env("EDHIP_ZSTRIP"))
+        zg.strip_tiles = atoi(st) >= 1 ? atoi(st) : zg.strip_tiles;
+#endif
+    zg.nstrips = (int)strip_count(1, across, tg.tiles[0], zg.strip_tiles);
+    zg.total_strips = zg.nstrips * tg.nbatch;
+    zg.hint = tg.hint;
+    zg.hint_host = tg.hint_host;
+    zg.hint_seq = tg.hint_seq;
+}
+
+// EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the host-side key of everything the forward kernel's tile boxes depend on
+void fill_keep_key(KeepKey& cur, const GridGeom& g, const TileGeom& tg, int order, const DeformBatch& batch)
+{
+    memset(&cur, 0, sizeof(cur));
+    int n = 0;
+    cur.w[n++] = 1;                                   // valid
+    cur.w[n++] = (unsigned long long)(size_t)batch.disp_id;
+    cur.w[n++] = (unsigned long long)g.disp_dtype | ((unsigned long long)batch.raw << 8) |
+                 ((unsigned long long)order << 16) | ((unsigned long long)tg.mode << 24) |
+                 ((unsigned long long)g.has_affine << 32);
+    cur.w[n++] = (unsigned long long)tg.nbatch;
+    cur.w[n++] = (unsigned long long)batch.disp_bstride;
+    for (int k = 0; k < 3; ++k) {
+        cur.w[n++] = (unsigned long long)g.in_len[k];
+        cur.w[n++] = (unsigned long long)g.out_len[k];
+        cur.w[n++] = (unsigned long long)g.off[k];
+        cur.w[n++] = (unsigned long long)g.ncp[k];
+    }
+    for (int k = 0; k < 4; ++k)      // (RAW: the strides of the filtered copy -- a function of ncp)
+        cur.w[n++] = (unsigned long long)g.disp_stride[k];
+    if (g.has_affine)
+        for (int k = 0; k < 12; ++k)
+            memcpy(&cur.w[n++], &g.affine[k], sizeof(double));
+}
+
+// The per-call tables launch (the z-walk route launches its geometry kernel in its place).  A gradient call hands it
+// the EDHIP_FLAG_ZERO_GRADIENT block to clear, a single volume the raw control grid to filter.
+hipError_t launch_tables(const GridGeom& g, TileGeom& tg, bool grad, hipStream_t stream, const DeformBatch* batch)
+{
+    const int nb = tg.nbatch;
+    unsigned fill_blocks = 0;
+    tg.zero_ptr = nullptr;
+    tg.zero_bytes = 0;
+    if (grad && batch && batch->zero_ptr && !batch->zero_done && nb == 1 && ((uintptr_t)batch->zero_ptr & 15) == 0) {
+        tg.zero_ptr = batch->zero_ptr;
+        tg.zero_bytes = batch->zero_bytes;
+        const long long want = (batch->zero_bytes + 65535) / 65536;       // 64 KiB per workgroup and round
+        fill_blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
+        batch->zero_done = true;
+    }
+    // (a raw grid is filtered inside this launch when it fits next to the plane slab; the kernel has ~1.2 KB of
+    // static LDS on top: a flat grid of 1342-1365 points would pass 64 KiB)
+    GridPrefilter gp;
+    const bool own = take_grid_prefilter(batch, nb, sizeof(double) * 3 * (size_t)g.ncp[1] * (size_t)g.ncp[2], gp);
+    hipLaunchKernelGGL(tile_tables_kernel, dim3((unsigned)g.out_len[0] + fill_blocks, (unsigned)nb), dim3(kBlock),
+                       sizeof(double) * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)gp.total), stream, g, tg, gp);
+    const hipError_t e = hipGetLastError();
+    if (own && e == hipSuccess)
+        batch->gridpf_done = true;       // (only a launch that went out has filtered the grid: ADVICE r5)
+    return e;
+}
+
+// What the three launchers below share: the tile geometry `tg` and the element-stride view `ve` of a call on elements
+// of esz bytes, how the control grid's width is served (`w`: the shared answer of ed_tile_host.h with the switches of
+// the experiments build applied), strips, the LDS budget (`lds`: what the general kernels ask for), the workspace
+// (`scratch`: behind the control-grid head, laid out as `l`) and, for label maps, integer volumes and order 0, the
+// tables launch.  hipSuccess with tg.nstrips == 0: an empty output, nothing to do.  Declines before anything is
+// launched.
+hipError_t tile_prologue(const GridGeom& g, const IOView& v, size_t esz, bool integral, int order, bool pair, bool grad,
+                         hipStream_t stream, const DeformBatch* batch, TileGeom& tg, IOView& ve, WideTables& w,
+                         size_t& lds, char*& scratch, TileScratch& l)
+{
+    const int64_t es = (int64_t)esz;
+    const bool f32 = !integral && esz == 4;
+    ve = v;
     const int nb = batch ? batch->nbatch : 1;
     tg.nbatch = nb;
-    tg.in_bstride = batch ? batch->in_bstride / (int64_t)sizeof(T) : 0;
-    tg.out_bstride = batch ? batch->out_bstride / (int64_t)sizeof(T) : 0;
+    tg.nstrips = 0;
+    tg.in_bstride = batch ? batch->in_bstride / es : 0;
+    tg.out_bstride = batch ? batch->out_bstride / es : 0;
     tg.disp_bstride = batch ? batch->disp_bstride : 0;
     for (int k = 0; k < 3; ++k) {
         tg.in_len[k] = (int)g.in_len[k];
         tg.out_len[k] = (int)g.out_len[k];
         tg.tiles[k] = (int)((g.out_len[k] + kT - 1) / kT);
-        tg.in_stride[k] = (int)(v.in_stride[k] / (int64_t)sizeof(T));
-        tg.out_stride[k] = (int)(v.out_stride[k] / (int64_t)sizeof(T));
+        tg.in_stride[k] = (int)(v.in_stride[k] / es);
+        tg.out_stride[k] = (int)(v.out_stride[k] / es);
         tg.off[k] = (int)g.off[k];
         // boundary-map period of the axis (deform.c:56,65,75 / :94,104,114)
         const double len = (double)g.in_len[k];
@@ -1407,65 +1419,58 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
     tg.has_affine = g.has_affine;
     for (int k = 0; k < 12; ++k)
         tg.affine[k] = g.affine[k];
-    for (int l = 0; l < v.nstep; ++l) {
-        ve.in_step_stride[l] = v.in_step_stride[l] / (int64_t)sizeof(T);
-        ve.out_step_stride[l] = v.out_step_stride[l] / (int64_t)sizeof(T);
+    for (int s = 0; s < v.nstep; ++s) {
+        ve.in_step_stride[s] = v.in_step_stride[s] / es;
+        ve.out_step_stride[s] = v.out_step_stride[s] / es;
     }
+    const bool unit_x = tg.in_stride[2] == 1 && tg.out_stride[2] == 1;
+    const bool no_hot = ed_env("EDHIP_NO_HOT") || ed_env("EDHIP_WAVE");
+    // Wide control grid: per-strip Q tables, the level-1 kernels in self-serve form; float32 orders 4 / 5 on the one-wave
+    // kernels of deform_wave.hip with plain tables -- what they cannot hold goes straight to the direct level, because
+    // the level-2 kernel stages Q rows like the others (256^3, 16^3 grid, order 5 on the row kernel: forward 4.7 ms,
+    // gradient 83 ms); or nothing: the row kernel of deform_fast.hip then takes the call (at 24.7 ms for the gradient of
+    // a 256^3 volume with a 16^3 grid, where this route takes 0.x ms).  (Round 5: the general kernels read the per-strip
+    // layout too -- float64 volumes and layouts without unit stride along x no longer fall to the row kernel.)
+    w = WideTables();
+    if (integral) {
+        if (wide_grid(g))
+            return hipErrorNotSupported;      // (unreachable behind deform_label_supported: wide grids are a float route)
+    } else {
+        w = wide_tables(g, esz == 8, order, unit_x, nb);
+        if (w.optional && ed_env("EDHIP_NO_WIDE64"))
+            w = WideTables();
+        if (w.kind == QTables::kWavePlain && no_hot)
+            w = wide_tables(g, esz == 8, order, false, nb);
+        // Behind deform_tile_supported, which asks the same function, only a batch of a wide grid is declined here
+        // (nbatch is not part of what it is given); order 0 and a window or strip count beyond the per-strip layout
+        // are unreachable, but for the experiments build's switches above.
+        if (w.kind == QTables::kNone)
+            return hipErrorNotSupported;
+    }
+    tg.q_win = tg.q_strip_vox = 0;
+    tg.q_strips = 1;
+    if (w.kind == QTables::kPerStrip) {
+        tg.q_win = w.win;
+        tg.q_strip_vox = kWideStripTiles * kT;
+        tg.q_strips = (int)w.strips;
+    }
+    // 16-bit output side: the level-1 kernels of deform_hot.hip (float32, orders 1-3) in self-serve form, or nothing.
+    // (Remains: deform_tile_supported does not look at out16 -- edhip_deform sets it only for calls that pass here --
+    // and does not know nbatch.)
+    if (v.out16 && !(f32 && order >= 1 && order <= 3 && nb == 1 && unit_x && !no_hot))
+        return hipErrorNotSupported;
     // strips of 8 tiles amortise the prologue; small outputs (crops) take shorter strips so that the
     // launch still has a few workgroups per CU (even lengths for the gradient: its kernel walks 16-wide
     // tiles; the forward kernels go down to one tile per workgroup -- a tile is a serial chain of
     // coordinates, box reduction, staging and gather, ~8 us, and a 32^3 volume has 64 of them)
-    // Wide control grid: the level-1 kernels of deform_hot.hip on per-strip Q tables, in self-serve form, or nothing
-    // (hipErrorNotSupported before anything is launched: the row kernel of deform_fast.hip then takes the call --
-    // at 24.7 ms for the gradient of a 256^3 volume with a 16^3 grid, where this route takes 0.x ms)
-    const bool wide_opt = sizeof(T) == 8 && std::is_floating_point<T>::value && ORDER >= 1 && nb == 1 &&
-                          !ed_env("EDHIP_NO_WIDE64") && wide_optional(g);
-    const bool wide = wide_grid(g) || wide_opt;
-    tg.q_win = tg.q_strip_vox = 0;
-    tg.q_strips = 1;
-    // (orders 4 / 5: the one-wave kernels of deform_wave.hip read their Q columns from global memory as they walk --
-    // no LDS limit on the grid's width: plain tables, and what they cannot hold goes straight to the direct level,
-    // because the level-2 kernel stages Q rows like the others.  256^3, 16^3 grid, order 5 on the row kernel:
-    // forward 4.7 ms, gradient 83 ms)
-    constexpr bool kWaveOrder = std::is_same<T, float>::value && ORDER >= 4;
-    const bool wide_wave = wide && kWaveOrder && tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ed_env("EDHIP_NO_HOT") &&
-                           !ed_env("EDHIP_WAVE");
-    // (round 5: the general kernels read the per-strip layout too -- float64 volumes and layouts without unit stride along x
-    // no longer fall to the row kernel: 256^3 float64, 16^3 grid, order 3 gradient 22.3 ms -> see profiles/r05_bench_misc.txt)
-    bool wide_hot = false;       // the level-1 kernels of deform_hot.hip / deform_k1.hip / deform_wave.hip take the call
-    if (wide) {
-        if constexpr (!(std::is_floating_point<T>::value && ORDER >= 1))
-            return hipErrorNotSupported;
-        if (nb != 1)
-            return hipErrorNotSupported;
-        wide_hot = std::is_same<T, float>::value && tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ed_env("EDHIP_NO_HOT") &&
-                   !ed_env("EDHIP_WAVE");
-        if (!wide_wave) {
-            const int win = wide_window(g);
-            const int64_t strips = (g.out_len[2] + kWideStripTiles * kT - 1) / (kWideStripTiles * kT);
-            if (win > kWideMaxWin || strips > 256)
-                return hipErrorNotSupported;
-            tg.q_win = win;
-            tg.q_strip_vox = kWideStripTiles * kT;
-            tg.q_strips = (int)strips;
-        }
-    }
-    if (v.out16) {
-        // 16-bit output side: the level-1 kernels of deform_hot.hip (orders 1-3) in self-serve form, or nothing
-        if constexpr (!(std::is_same<T, float>::value && ORDER >= 1 && ORDER <= 3))
-            return hipErrorNotSupported;
-        if (nb != 1 || tg.in_stride[2] != 1 || tg.out_stride[2] != 1 || ed_env("EDHIP_NO_HOT") || ed_env("EDHIP_WAVE"))
-            return hipErrorNotSupported;
-    }
     // (the forward kernels prefer strips of 4: 256^3 order 3, K1 call 237.5 -> 228.7 us, sigma 10 342.8 -> 338.0, order 1
     // 159.4 -> 155.8 -- twice the workgroups for the tail of the launch to be dealt from; the gradient kernel, which
     // walks a strip in 16-wide tiles, prefers 8: 310.7 against 313.3 us; profiles/r04_bench_misc.txt)
-    tg.strip_tiles = GRAD ? kStrip : kStrip / 2;
     if (tg.q_win)
         tg.strip_tiles = kWideStripTiles;       // (the per-strip Q layout is made for exactly this length)
-    while (!tg.q_win && tg.strip_tiles > (GRAD ? 2 : 1) &&
-           (int64_t)nb * tg.tiles[0] * tg.tiles[1] * ((tg.tiles[2] + tg.strip_tiles - 1) / tg.strip_tiles) < 1024)
-        tg.strip_tiles >>= 1;
+    else
+        tg.strip_tiles = shorten_strips(grad ? kStrip : kStrip / 2, grad ? 2 : 1, 1024, nb,
+                                        (int64_t)tg.tiles[0] * tg.tiles[1], tg.tiles[2]);
 #ifdef EDHIP_EXPERIMENTS
     if (const char* st = ed_env("EDHIP_STRIP"))
         tg.strip_tiles = atoi(st) >= 1 && atoi(st) <= kStrip ? atoi(st) : tg.strip_tiles;
@@ -1477,460 +1482,162 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
         return hipSuccess;
     if (ntiles * nb > 0x3fffffffLL || nstrips * nb > 0x3fffffffLL)
         return hipErrorInvalidValue;
-    tg.nstrips = (int)nstrips;
     tg.ntiles = (int)ntiles;
-    tg.q_bstride = (long long)(q_global_bytes(g, wide_opt) / 8);
     // (wide grids: the kernels see a grid of q_win columns, the strip's window)
     const size_t qcols = tg.q_win ? (size_t)tg.q_win : (size_t)g.ncp[2];
     tg.ncpx = (int)qcols;
     // LDS: head | Q | overlay (box | D, P).  K1 float32 odd orders: two shifted copies of 4096
     // elements; otherwise one copy (6144 x 4 bytes or 4096 x 8 bytes)
     size_t box;
-    if (GRAD) {
+    if (grad) {
         // 32 KiB of fixed-point cells (int32 for float32, int64 for float64) + the float64 wave sums
-        tg.box_cap = (int)(32768 / sizeof(T));
+        tg.box_cap = (int)(32768 / esz);
         box = 32768 + 64;
-    } else if (PAIR) {
+    } else if (pair) {
         tg.box_cap = 3704;      // 57 * 64 + 56; two copies + head + Q stay under 40 KiB -> 4 blocks per CU
-        box = 2 * 3704 * sizeof(T);
+        box = 2 * 3704 * esz;
     } else {
         // single copy: orders 4 / 5 have 5- / 6-wide windows and need the larger budget
-        tg.box_cap = sizeof(T) == 4 ? (ORDER >= 4 ? 8192 : 6144) : 4096;
-        box = (size_t)tg.box_cap * sizeof(T);
+        tg.box_cap = esz == 4 ? (order >= 4 ? 8192 : 6144) : 4096;
+        box = (size_t)tg.box_cap * esz;
     }
     tg.off_ov = (int)(kOffQ + ((8 * (size_t)(kT * kT * 4) * qcols + 15) & ~(size_t)15));
     if (tg.off_ov + box > (size_t)64 * 1024) {
         // the Q rows of a wide window leave less than the standard box inside the 64 KiB a block may ask for
         const size_t room = (size_t)64 * 1024 - tg.off_ov;
+        // (remains: deform_tile_supported does not do this LDS arithmetic.  A per-strip window, at most kWideMaxWin
+        // columns, always leaves 16 KiB; the one-wave kernels' plain tables of 23 to 30 columns do not, and edhip_deform
+        // hands the call to the row kernel.  Beyond that off_ov passes 64 KiB, `room` wraps and the call goes on with
+        // a budget only the general kernels would read, which plain tables never reach.)
         if (room < (size_t)16 * 1024)
             return hipErrorNotSupported;
-        if (GRAD) {
-            tg.box_cap = (int)(((room - 64) / sizeof(T)) & ~(size_t)15);
-            box = (size_t)tg.box_cap * sizeof(T) + 64;
-        } else if (PAIR) {
-            size_t cap = room / (2 * sizeof(T));
+        if (grad) {
+            tg.box_cap = (int)(((room - 64) / esz) & ~(size_t)15);
+            box = (size_t)tg.box_cap * esz + 64;
+        } else if (pair) {
+            size_t cap = room / (2 * esz);
             cap = ((cap - 56) / 64) * 64 + 56;
             tg.box_cap = (int)cap;
-            box = 2 * cap * sizeof(T);
+            box = 2 * cap * esz;
         } else {
-            tg.box_cap = (int)((room / sizeof(T)) & ~(size_t)15);
-            box = (size_t)tg.box_cap * sizeof(T);
+            tg.box_cap = (int)((room / esz) & ~(size_t)15);
+            box = (size_t)tg.box_cap * esz;
         }
     }
-    size_t overlay = (box + 15) & ~(size_t)15;
-    size_t lds = tg.off_ov + overlay;
+    lds = tg.off_ov + ((box + 15) & ~(size_t)15);
     if (const char* pad = ed_env("EDHIP_LDS_PAD"))
         lds += (size_t)atoi(pad);
     {
         const char* dbg = ed_env("EDHIP_TILE_DBG");
         tg.dbg = dbg ? atoi(dbg) : 0;
     }
-    // scratch: first-level spill list | second-level spill list | x table | Q
-    const size_t list_bytes = (sizeof(int) * ((size_t)ntiles * nb + 1) + 63) & ~(size_t)63;
-    const size_t xt_bytes = xt_block_bytes(g, nb);
-    const size_t q_all = ((q_global_bytes(g, wide_opt) * (size_t)nb) + 63) & ~(size_t)63;
+    // scratch (ed_tile_host.h): first-level spill list | second-level spill list | x table | slack | Q | label list.
+    // edhip_deform reserved deform_tile_workspace_bytes() up front -- the same layout, with the optional per-strip tables
+    // allowed wherever this call may take them -- so this does not move the prefiltered control grid that may sit in the
+    // head of the workspace.
+    l = tile_scratch_layout(g, nb, w.optional);
     hipError_t e = hipSuccess;
-    // (edhip_deform reserved deform_tile_workspace_bytes() up front, so this does not move the
-    // prefiltered control grid that may sit in the head of the workspace)
-    void* ws = workspace_reserve(stream, kWorkspaceGridBytes + 2 * list_bytes + xt_bytes + q_all +
-                                             label_list_bytes(g), &e);
+    char* ws = (char*)workspace_reserve(stream, kWorkspaceGridBytes + l.total, &e);
     if (!ws)
         return e;
-    ws = (char*)ws + kWorkspaceGridBytes;
-    int* list_a = (int*)ws;
-    int* list_b = (int*)((char*)ws + list_bytes);
-    // (a fixed place in the stream's workspace, whatever the geometry of the call: the unused tail of the
-    // control-grid head, in front of edhip_source_box's 64 result bytes)
-    tg.hint = (int*)((char*)ws - 128);
-    tg.xt_global = (const AxTab*)((char*)ws + 2 * list_bytes);
+    scratch = ws + kWorkspaceGridBytes;
+    tg.nstrips = (int)nstrips;
+    tg.q_bstride = (long long)(l.q_stride / 8);
+    tg.spill = (int*)(scratch + l.list_a);
+    tg.spill_next = (int*)(scratch + l.list_b);
+    tg.xt_global = (const AxTab*)(scratch + l.xt);
     tg.slack = nullptr;          // (set by the route that reads it: K1 of deform_k1.hip)
     tg.slack_scale = 0.0;
-    tg.q_global = (const double*)((char*)ws + 2 * list_bytes + xt_bytes);
+    tg.q_global = (const double*)(scratch + l.q);
     tg.worklist = nullptr;
-    tg.spill = list_a;
-    tg.spill_next = list_b;
     tg.label_list = nullptr;
     tg.label_cap = 0;
-    if (std::is_integral<T>::value) {
-        tg.label_list = (int*)((char*)ws + 2 * list_bytes + xt_bytes + q_all);
+    if (integral) {
+        tg.label_list = (int*)(scratch + l.label);
         tg.label_cap = (int)(label_list_bytes(g) / sizeof(int)) - 32;
     }
-    // level-1 spill feedback (float32, orders 1-5): standard, large or huge boxes, self-serve or the spill levels
-    SpillFeedback fb;
-    if constexpr (std::is_same<T, float>::value && ORDER >= 1)
-        fb = spill_feedback(g, v.mode, ORDER, GRAD, nb, ntiles, stream);
-    tg.hint_host = fb.hint_host;
-    tg.hint_seq = fb.hint_seq;
-    // (a call without spill feedback -- integer volumes, order 0 -- must leave the counters of the float call in
-    // front of it alone: its tables kernel used to reset them unreported, and a multi-input call such as
-    // BASELINE cfg4 never learned that its geometry does not spill)
-    if (!fb.hint_host)
-        tg.hint = nullptr;
-    // the per-call tables launch (the z-walk route launches its geometry kernel in its place)
-    bool tables_done = false;
-    auto launch_tables = [&]() {
-        if (tables_done || e != hipSuccess)
-            return;
-        tables_done = true;
-        unsigned fill_blocks = 0;
-        tg.zero_ptr = nullptr;
-        tg.zero_bytes = 0;
-        if (GRAD && batch && batch->zero_ptr && !batch->zero_done && nb == 1 && ((uintptr_t)batch->zero_ptr & 15) == 0) {
-            tg.zero_ptr = batch->zero_ptr;
-            tg.zero_bytes = batch->zero_bytes;
-            const long long want = (batch->zero_bytes + 65535) / 65536;       // 64 KiB per workgroup and round
-            fill_blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-            batch->zero_done = true;
-        }
-        // (a raw grid is filtered inside this launch when it fits next to the plane slab; the kernel has ~1.2 KB of
-        // static LDS on top: a flat grid of 1342-1365 points would pass 64 KiB)
-        GridPrefilter gp;
-        const bool own = take_grid_prefilter(batch, nb, sizeof(double) * 3 * (size_t)g.ncp[1] * (size_t)g.ncp[2], gp);
-        hipLaunchKernelGGL(tile_tables_kernel, dim3((unsigned)g.out_len[0] + fill_blocks, (unsigned)nb), dim3(kBlock),
-                           sizeof(double) * (3 * (size_t)g.ncp[1] * (size_t)g.ncp[2] + (size_t)gp.total), stream, g, tg,
-                           gp);
-        e = hipGetLastError();
-        if (own && e == hipSuccess)
-            batch->gridpf_done = true;       // (only a launch that went out has filtered the grid: ADVICE r5)
-    };
-    if (std::is_integral<T>::value || ORDER < 1)
-        launch_tables();
-    if constexpr (std::is_integral<T>::value) {
-        if (nb != 1)
-            return hipErrorNotSupported;      // the label kernels take one volume per call
-        if (e == hipSuccess && v.order >= 1) {
-            // 8- / 16-bit integer volumes, orders 1-5: the wave-per-tile kernel with fp64 taps; the voxels it
-            // lists (value near a rounding tie, coordinate on a boundary) are redone by the exact kernel
-            HotGeom hg;
-            fill_hot_geom(hg, tg, ve, v);
-            hg.cvald = ve.cval;
-            hg.tie_list = tg.label_list;
-            hg.tie_cap = tg.label_cap;
-            hg.strip_tiles = 4;
-            while (hg.strip_tiles > 1 &&
-                   (int64_t)tg.tiles[0] * tg.tiles[1] * ((tg.tiles[2] + hg.strip_tiles - 1) / hg.strip_tiles) < 8192)
-                hg.strip_tiles >>= 1;
-            hg.strips_x = (tg.tiles[2] + hg.strip_tiles - 1) / hg.strip_tiles;
-            const int64_t wstrips = (int64_t)tg.tiles[0] * tg.tiles[1] * hg.strips_x;
-            if (wstrips > 0x3fffffffLL)
-                return hipErrorNotSupported;
-            hg.nstrips = hg.total_strips = (int)wstrips;
-            const size_t wlds = wave_lds_bytes(false, 3, &hg.box_cap);
-            const unsigned wblk = (unsigned)(((wstrips + 7) / 8) * 8);
-            e = launch_wave_int(hg, v.order, v.in_dtype, ve.in, ve.out, wblk, wlds, stream);
-            if (e == hipSuccess)
-                e = launch_deform_exact_list(g, v, tg.label_list, tg.label_cap, stream);
-            return e;
-        }
-        if (e == hipSuccess) {
-            const unsigned nblk = (unsigned)(ntiles < (1 << 20) ? ntiles : (1 << 20));
-            hipLaunchKernelGGL(deform_tile3_label_kernel<T>, dim3(nblk), dim3(kBlock), 0, stream, g, ve, tg);
-            e = hipGetLastError();
-            // the near-tie voxels, in the reference's evaluation order: the exact kernel's list form (control grid in
-            // LDS; it leaves at once when the list is empty).  A kernel of this file used to do it with the grid in
-            // global memory: its handful of voxels sat in ONE wave that walked 192 dependent loads -- 50 us behind a
-            // 29 us label kernel (128^3 uint8).
-            if (e == hipSuccess)
-                e = launch_deform_exact_list(g, v, tg.label_list, tg.label_cap, stream);
-        }
+    // (a call without spill feedback -- integer volumes, order 0, float64 -- must leave the counters of the float call
+    // in front of it alone: its tables kernel used to reset them unreported, and a multi-input call such as BASELINE
+    // cfg4 never learned that its geometry does not spill; the float launcher sets these for a call that takes part)
+    tg.hint = nullptr;
+    tg.hint_host = nullptr;
+    tg.hint_seq = 0;
+    if (integral || order < 1)
+        e = launch_tables(g, tg, grad, stream, batch);
+    return e;
+}
+
+// Label maps (order 0, any dtype) and the integer fast path (orders 1-5) on elements the size of T.
+template <typename T>
+hipError_t launch_tile_int(const GridGeom& g, const IOView& v, hipStream_t stream, const DeformBatch* batch)
+{
+    TileGeom tg;
+    IOView ve;
+    WideTables w;
+    size_t lds;
+    char* scratch;
+    TileScratch l;
+    // (forward, single copy: the budget of a general order-0 call, which these kernels do not draw on)
+    hipError_t e = tile_prologue(g, v, sizeof(T), true, 0, false, false, stream, batch, tg, ve, w, lds, scratch, l);
+    if (e != hipSuccess || tg.nstrips == 0)
         return e;
+    // the label kernels take one volume per call (unreachable: launch_deform_label / launch_deform_int are handed
+    // single volumes)
+    if (tg.nbatch != 1)
+        return hipErrorNotSupported;
+    if (v.order >= 1) {
+        // 8- / 16-bit integer volumes, orders 1-5: the wave-per-tile kernel with fp64 taps; the voxels it
+        // lists (value near a rounding tie, coordinate on a boundary) are redone by the exact kernel
+        HotGeom hg;
+        fill_hot_geom(hg, tg, ve, v);
+        hg.cvald = ve.cval;
+        hg.tie_list = tg.label_list;
+        hg.tie_cap = tg.label_cap;
+        const int64_t across = (int64_t)tg.tiles[0] * tg.tiles[1];
+        hg.strip_tiles = shorten_strips(4, 1, 8192, 1, across, tg.tiles[2]);
+        hg.strips_x = (tg.tiles[2] + hg.strip_tiles - 1) / hg.strip_tiles;
+        const int64_t wstrips = strip_count(1, across, tg.tiles[2], hg.strip_tiles);
+        if (wstrips > 0x3fffffffLL)
+            return hipErrorNotSupported;      // (unreachable: no more strips than tiles, which the prologue has bounded)
+        hg.nstrips = hg.total_strips = (int)wstrips;
+        const size_t wlds = wave_lds_bytes(false, 3, &hg.box_cap);
+        const unsigned wblk = (unsigned)(((wstrips + 7) / 8) * 8);
+        e = launch_wave_int(hg, v.order, v.in_dtype, ve.in, ve.out, wblk, wlds, stream);
     } else {
-    if (ORDER < 1) {
-        // order 0: one tap per voxel, no source box, straight from / to global memory
-        if (e == hipSuccess) {
-            const unsigned nblk = (unsigned)(ntiles * nb < (1 << 20) ? ntiles * nb : (1 << 20));
-            hipLaunchKernelGGL((deform_tile3_direct_kernel<T, ORDER, GRAD, false>), dim3(nblk),
-                               dim3(kBlock), 0, stream, g, ve, tg);
-            e = hipGetLastError();
-        }
-        return e;
-    }
-    // ---- level 1: strips, small boxes, highest occupancy ------------------------------------------
-    bool hot_done = false;
-    bool served_all = false;        // level 1 ran in self-serve form: no spill list to work off
-    HotGeom hg;
-    if (e == hipSuccess) {
-        const unsigned nblk = (unsigned)(((nstrips * nb + 7) / 8) * 8);
-        [[maybe_unused]] constexpr bool kBenchKernel = PAIR && ORDER == 3 && sizeof(T) == 4;
-        if constexpr (std::is_same<T, float>::value && ORDER >= 1) {
-            // float32, unit stride along x on both sides: the benchmark kernels of deform_hot.hip
-            if (tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ED_DBG(tg.dbg, 512) && !ed_env("EDHIP_NO_HOT")) {
-                fill_hot_geom(hg, tg, ve, v);
-                hg.self_serve = (fb.self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
-                if (v.out16 || wide)
-                    hg.self_serve = 1;          // (the spill levels know neither 16-bit storage nor per-strip tables)
-                hg.hint = tg.hint;              // (nullptr: a call without spill feedback)
-                size_t hlds = 0;
-                // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles) -- a function of the
-                // template arguments alone (the forward strips chosen above have at most 4 tiles, K1's limit; a longer one
-                // asked for with EDHIP_STRIP makes launch_k1_level1 decline, and the general kernels take the call)
-                constexpr bool kK1 = !GRAD && ORDER <= 3;
-                // round 6: strips along z on R tables (deform_k1z.hip) for every grid its geometry kernel holds in LDS
-#ifdef EDHIP_NO_K1Z          // (A/B build of the shipped library without the z-walk route: tools/abl_k1_size.sh)
-                const bool k1z = false;
-#else
-                // Which forward kernel (a function of the call's arguments alone: the two routes differ in the last bits).
-                // Measured on shipped builds (profiles/r06_k1_route_sweep.txt): on mild fields the z-walk wins where the
-                // x-strip kernel stumbles -- single volumes whose z and y extents are multiples of 256 (256^3 +7 %,
-                // 512 x 256 x 256 +18 %) -- and loses elsewhere (128^3 -50 %, 192^3 -24 %, 288^3 -10 %, batches -7 ... -26 %: its
-                // geometry kernel costs 20-35 us per call and its tables are per sample); on strong fields (sigma 15) it wins
-                // everywhere by 5-35 %.  The library cannot see the field's strength without a host round trip: the caller
-                // can say so (EDHIP_FLAG_STRONG_FIELD).
-                const bool z_shape = nb == 1 && g.out_len[0] % 256 == 0 && g.out_len[1] % 256 == 0 && g.in_len[0] % 256 == 0 &&
-                                     g.in_len[1] % 256 == 0;
-                const bool z_pick = ed_env("EDHIP_K1Z_ALWAYS") || (batch && batch->strong) || z_shape;
-                const bool k1z = kK1 && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
-#endif
-                ZGeom zg;
-                memset(&zg, 0, sizeof(zg));
-                GeoBuffer* zgeo = nullptr;
-                if (k1z) {
-                    (void)k1z_lds_bytes(&hg.small_cap, false);
-                    hlds = k1z_lds_bytes(&hg.box_cap, fb.large_boxes);
-                    hg.off_box = 0;
-                    zg.slack_scale = box_margin_scale(g);
-                    zgeo = geo_buffer(stream);
-                    const K1zGeoLayout gl = k1z_geo_layout(g, ntiles, nb);
-                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, gl.total, &e) : nullptr;
-                    if (!gb)
-                        return e != hipSuccess ? e : hipErrorOutOfMemory;
-                    zg.ctl = (int*)gb;                       // the lists' counters: 32 ints in the cleared head
-                    zg.zgen = gb + gl.zgen;
-                    zg.zt = (const AxTab*)(gb + gl.zt);
-                    zg.recs = (int*)(gb + gl.recs);
-                    zg.missed = (int*)(gb + gl.missed);
-                    zg.sinfo = (int*)(gb + gl.sinfo);
-                    zg.list_g = (int*)(gb + gl.list_g);
-                    zg.list_f = (int*)(gb + gl.list_f);
-                    zg.recs_half = (int*)(gb + gl.recs_half);
-                    zg.steps = (long long*)(gb + gl.steps);
-                    zg.r = (const double*)(gb + gl.r);
-                    zg.r_bstride = (long long)(gl.r_stride / 8);
-                    zg.parity = (int)(zgeo->parity & 1);
-                    zg.disp_bstride = tg.disp_bstride;
-                    zg.ncpz = (int)g.ncp[0];
-                    zg.order = ORDER;
-                    // strips of 4 tiles where that leaves the chip enough of them (256^3: 8192); strips of 2 below ~4096 (128^3:
-                    // 1024 -> 2048 strips, level-1 launch 45.8 -> 37.0 us; 192^3: 105.8 -> 91.8; at 256^3 strips of 2 cost 6 %);
-                    // single tiles only for volumes that have fewer than 1024 pairs (profiles/r06_k1_route_sweep.txt)
-                    zg.strip_tiles = 4;
-                    auto zstrips = [&](int st) { return (int64_t)nb * tg.tiles[1] * tg.tiles[2] * ((tg.tiles[0] + st - 1) / st); };
-                    if (zstrips(4) < 4096)
-                        zg.strip_tiles = 2;
-                    if (zstrips(2) < 1024)
-                        zg.strip_tiles = 1;
-#ifdef EDHIP_EXPERIMENTS
-                    if (const char* st = ed_env("EDHIP_ZSTRIP"))
-                        zg.strip_tiles = atoi(st) >= 1 ? atoi(st) : zg.strip_tiles;
-#endif
-                    zg.nstrips = tg.tiles[1] * tg.tiles[2] * ((tg.tiles[0] + zg.strip_tiles - 1) / zg.strip_tiles);
-                    zg.total_strips = zg.nstrips * nb;
-                    zg.hint = hg.hint;
-                    zg.hint_host = tg.hint_host;
-                    zg.hint_seq = tg.hint_seq;
-#ifdef EDHIP_EXPERIMENTS
-                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                        hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
-#endif
-                } else if (kK1) {
-                    int off_small = 0;
-                    (void)k1_lds_bytes(hg.ncpx, &hg.small_cap, &off_small, false);
-                    if (fb.large_boxes)
-                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, true);
-                    if (!hlds)
-                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, false);
-                    tg.slack = (double*)((char*)ws + 2 * list_bytes + xt_only_bytes(g));
-                    tg.slack_scale = box_margin_scale(g);
-                    hg.slack = tg.slack;
-#ifdef EDHIP_EXPERIMENTS
-                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                        hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
-#endif
-                } else {
-                    // the gradient (deform_hot.hip); forward, orders 4 / 5: only whether a box fits next to the Q rows at
-                    // all is asked here -- the one-wave kernels below size their own
-                    int off_small = 0;
-                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.small_cap, &off_small, 0);
-                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.large_cap, &off_small, 1);
-                    if (fb.huge_boxes)
-                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 2);
-                    if (!hlds && fb.large_boxes)
-                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 1);
-                    if (!hlds)
-                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 0);
-                }
-                if (v.out16 && !hlds)
-                    return hipErrorNotSupported;        // (nothing has been launched yet)
-                // (a wide grid whose window leaves no room for a hot box: the general kernels below, same tables)
-                hg.lds_grp = (int)((hlds + 15) & ~(size_t)15);
-                // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes live in a buffer of their own (nothing
-                // else writes it) under a host-side key of everything they depend on.
-                KeepKey* key = nullptr;
-                KeepKey cur;
-                memset(&cur, 0, sizeof(cur));
-                const int box_mode = batch ? batch->box_mode : 0;
-                if (hlds && box_mode && !ed_env("EDHIP_NO_BOXES")) {
-                    hipError_t ke = hipSuccess;
-                    int* kb = (int*)keep_reserve(stream, ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255, &key, &ke);
-                    if (kb) {
-                        int n = 0;
-                        cur.w[n++] = 1;                                   // valid
-                        cur.w[n++] = (unsigned long long)(size_t)batch->disp_id;
-                        cur.w[n++] = (unsigned long long)g.disp_dtype | ((unsigned long long)batch->raw << 8) |
-                                     ((unsigned long long)ORDER << 16) | ((unsigned long long)tg.mode << 24) |
-                                     ((unsigned long long)g.has_affine << 32);
-                        cur.w[n++] = (unsigned long long)nb;
-                        cur.w[n++] = (unsigned long long)batch->disp_bstride;
-                        for (int k = 0; k < 3; ++k) {
-                            cur.w[n++] = (unsigned long long)g.in_len[k];
-                            cur.w[n++] = (unsigned long long)g.out_len[k];
-                            cur.w[n++] = (unsigned long long)g.off[k];
-                            cur.w[n++] = (unsigned long long)g.ncp[k];
-                        }
-                        for (int k = 0; k < 4; ++k)      // (RAW: the strides of the filtered copy -- a function of ncp)
-                            cur.w[n++] = (unsigned long long)g.disp_stride[k];
-                        if (g.has_affine)
-                            for (int k = 0; k < 12; ++k)
-                                memcpy(&cur.w[n++], &g.affine[k], sizeof(double));
-                        if (!GRAD && box_mode == 1) {
-                            hg.boxes = kb;
-                            *key = KeepKey();                  // not valid until this launch is in the stream
-                        } else if (GRAD && box_mode == 2 && ORDER >= 3 && memcmp(key, &cur, sizeof(cur)) == 0) {
-                            // (orders 1 / 2: the box pass is a small part of a short tile, and the
-                            // hand-over's bookkeeping costs more than it saves: 190 -> 196, 242 -> 252 us)
-                            hg.boxes = kb;
-                            hg.use_boxes = 1;
-                            if (fb.self_serve_boxes && ORDER <= 3)
-                                hg.self_serve = 1;
-                        }
-                    }
-                }
-                if (k1z && e == hipSuccess) {
-                    // the geometry kernel in place of the tables kernel: R, the z table, tile records (and boxes), work lists
-                    GridPrefilter gp;
-                    const bool own = take_grid_prefilter(batch, nb, 0, gp);
-                    e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
-                    if (e == hipSuccess)
-                        ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
-                    if (own && e == hipSuccess)
-                        batch->gridpf_done = true;
-                    tables_done = true;
-                }
-                launch_tables();
-                profile_mark(false, stream);
-                // Orders 4 / 5 run on the wave-per-tile kernels (deform_wave.hip: one wavefront per tile,
-                // one copy of the box, tiles that do not fit taken as two x-halves): the 4-wave kernels
-                // give up on a tile as soon as its 5- / 6-tap windows need the wide row pitch, and at
-                // these orders that is a large share of the tiles (256^3, sigma 5, whole call: order 4
-                // forward 419 -> 339 us, order 5 gradient 944 -> 886 us; profiles/r03_wave_vs_4wave.txt).
-                // Orders 1-3 stay on the 4-wave kernels, which are 10-30 % faster there.
-                int wave_mode = ORDER >= 4 ? 3 : 0;
-#ifdef EDHIP_EXPERIMENTS
-                if (const char* wm = ed_env("EDHIP_WAVE"))        // 1 forward, 2 gradient, 3 both, 0 neither
-                    wave_mode = atoi(wm);
-#endif
-                if ((hlds || wide_wave) && (wave_mode & (GRAD ? 2 : 1))) {
-                    HotGeom wg = hg;
-                    wg.self_serve = 0;
-                    wg.strip_tiles = 4;
-#ifdef EDHIP_EXPERIMENTS
-                    if (const char* st = ed_env("EDHIP_WAVE_STRIP"))
-                        wg.strip_tiles = atoi(st);
-#endif
-                    while (wg.strip_tiles > 1 &&
-                           (int64_t)nb * tg.tiles[0] * tg.tiles[1] * ((tg.tiles[2] + wg.strip_tiles - 1) / wg.strip_tiles) < 8192)
-                        wg.strip_tiles >>= 1;
-                    wg.strips_x = (tg.tiles[2] + wg.strip_tiles - 1) / wg.strip_tiles;
-                    const int64_t wstrips = (int64_t)tg.tiles[0] * tg.tiles[1] * wg.strips_x;
-                    if (wstrips * nb <= 0x3fffffffLL) {
-                        wg.nstrips = (int)wstrips;
-                        wg.total_strips = (int)(wstrips * nb);
-                        int occ = 3;
-#ifdef EDHIP_EXPERIMENTS
-                        if (const char* oc = ed_env("EDHIP_WAVE_OCC"))
-                            occ = atoi(oc);
-#endif
-                        size_t wlds = wave_lds_bytes(GRAD, occ, &wg.box_cap);
-                        // spill feedback: larger boxes (fewer waves per CU) once the geometry's calls spill.
-                        // 256^3 sigma 10, whole call: order 4 forward 453 -> 420 us, gradient 694 -> 662;
-                        // order 5 forward 1019 -> 657, gradient 1238 -> 1055 (sigma 5: +20 .. +40 us)
-                        wg.small_cap = wg.box_cap;
-                        if (fb.large_boxes) {
-                            wlds = (ORDER == 5 && !GRAD) ? 20480 : 16384;
-                            wg.box_cap = (int)((wlds - 416) / 4);
-                        }
-#ifdef EDHIP_EXPERIMENTS
-                        if (const char* kb = ed_env("EDHIP_WAVE_LDS")) {
-                            wlds = (size_t)atoi(kb);
-                            wg.box_cap = (int)((wlds - 416) / 4);
-                        }
-                        if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                            wg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
-#endif
-                        const unsigned wblk = (unsigned)(((wstrips * nb + 7) / 8) * 8);
-                        const hipError_t he = launch_wave_level1(wg, ORDER, GRAD, wblk, wlds, occ, stream);
-                        if (he == hipSuccess) {
-                            hot_done = true;
-                            if (!GRAD && hg.boxes && key)
-                                *key = cur;
-                        } else if (he != hipErrorNotSupported || wide_wave)
-                            e = he;
-                    }
-                }
-                if (wide_wave && !hot_done && e == hipSuccess)
-                    e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
-                if (hlds && !hot_done && e == hipSuccess) {
-                    // (forward, orders 4 / 5, when the one-wave kernels did not take the call: the general kernels below)
-                    hipError_t he = hipErrorNotSupported;
-                    if (k1z)
-                        he = launch_k1z(hg, zg, ORDER, hlds, stream);
-                    else if (kK1)
-                        he = launch_k1_level1(hg, ORDER, nblk, hlds, stream);
-                    else if (GRAD)
-                        he = launch_hot_grad_level1(hg, ORDER, nblk, hlds, stream);
-                    if (he == hipSuccess) {
-                        hot_done = true;
-                        served_all = hg.self_serve != 0 || k1z;
-                        if (!GRAD && hg.boxes && key)
-                            *key = cur;
-                    } else if (he != hipErrorNotSupported || v.out16 || wide)
-                        e = he;
-                }
-            }
-        }
-        if (!tables_done) {
-            launch_tables();
-            profile_mark(false, stream);
-        }
-        if (hot_done || e != hipSuccess)
-            ;
-        else if (GRAD)
-            hipLaunchKernelGGL((deform_tile3_grad_kernel<T, (ORDER < 1 ? 2 : ORDER), 16>), dim3(nblk),
-                               dim3(kBlock), lds, stream, g, ve, tg);
-#ifdef EDHIP_EXPERIMENTS
-        else if (kBenchKernel && tg.dbg) {
-            if constexpr (kBenchKernel) {
-            // profiling builds of the benchmark kernel (EDHIP_TILE_DBG), never used otherwise
-            switch (tg.dbg) {
-            case 2: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 2>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            case 4: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 4>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            case 6: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 6>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            case 16: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 16>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            case 64: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 64>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            case 38: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 38>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            default: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 0>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-            }
-            }
-        }
-#endif
-        else
-            hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR>), dim3(nblk), dim3(kBlock),
-                               lds, stream, g, ve, tg);
+        const unsigned nblk = (unsigned)(tg.ntiles < (1 << 20) ? tg.ntiles : (1 << 20));
+        hipLaunchKernelGGL(deform_tile3_label_kernel<T>, dim3(nblk), dim3(kBlock), 0, stream, g, ve, tg);
         e = hipGetLastError();
     }
-    profile_mark(true, stream);
-    // ---- level 2: the tiles level 1 could not hold, one 8^3 tile per work item, a 48 KiB box
-    //      (single copy, 24- / 56-wide rows), grid-stride over the worklist --------------------------
+    // the near-tie voxels, in the reference's evaluation order: the exact kernel's list form (control grid in
+    // LDS; it leaves at once when the list is empty).  A kernel of this file used to do it with the grid in
+    // global memory: its handful of voxels sat in ONE wave that walked 192 dependent loads -- 50 us behind a
+    // 29 us label kernel (128^3 uint8).
+    if (e == hipSuccess)
+        e = launch_deform_exact_list(g, v, tg.label_list, tg.label_cap, stream);
+    return e;
+}
+
+// Order 0: one tap per voxel, no source box, straight from / to global memory.
+template <typename T, int ORDER, bool GRAD>
+hipError_t launch_tile_direct(const GridGeom& g, const IOView& ve, const TileGeom& tg, hipStream_t stream)
+{
+    const int64_t nt = (int64_t)tg.ntiles * tg.nbatch;
+    const unsigned nblk = (unsigned)(nt < (1 << 20) ? nt : (1 << 20));
+    hipLaunchKernelGGL((deform_tile3_direct_kernel<T, ORDER, GRAD, false>), dim3(nblk), dim3(kBlock), 0, stream, g, ve, tg);
+    return hipGetLastError();
+}
+
+// Levels 2 and 3 behind a level 1 that left its oversize tiles on the first spill list.
+//   level 2: the tiles level 1 could not hold, one 8^3 tile per work item, a 48 KiB box (single copy, 24- / 56-wide
+//            rows), grid-stride over the worklist -- not where the tables are plain ones of a wide grid (skip_l2)
+//   level 3: whatever is left goes straight through global memory
+template <typename T, int ORDER, bool GRAD>
+hipError_t launch_spill_levels(const GridGeom& g, const IOView& ve, const TileGeom& tg, bool skip_l2, hipStream_t stream)
+{
+    const int64_t nt = (int64_t)tg.ntiles * tg.nbatch;
+    int* const list_a = tg.spill;
+    int* const list_b = tg.spill_next;
+    hipError_t e = hipSuccess;
     TileGeom t2 = tg;
     t2.worklist = list_a;
     t2.spill = list_b;
@@ -1942,17 +1649,16 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
     unsigned wgs2 = (sizeof(T) == 4 && ORDER <= 3) ? 768 : 512;
     if (const char* kb = ed_env("EDHIP_L2_BOX_KB"))        // experiment: smaller boxes, more workgroups per CU
         box2 = (size_t)atoi(kb) * 1024;
-    if (const char* w = ed_env("EDHIP_L2_WGS"))
-        wgs2 = (unsigned)atoi(w);
+    if (const char* wg = ed_env("EDHIP_L2_WGS"))
+        wgs2 = (unsigned)atoi(wg);
     if (t2.off_ov + box2 > 64 * 1024)
         box2 = (64 * 1024 - t2.off_ov) & ~(size_t)63;
     t2.box_cap = (int)((box2 - (GRAD ? 64 : 0)) / sizeof(T));      // gradient: cells of sizeof(T) + wave sums
     const size_t lds2 = t2.off_ov + box2;
-    const unsigned n2 = (unsigned)(ntiles * nb < wgs2 ? ntiles * nb : wgs2);
-    const bool skip_l2 = ed_env("EDHIP_SKIP_L2") != nullptr || wide_wave;      // (debugging aid; wide grids: see above)
-    if (served_all)
-        return e;               // level 1 has served every tile
-    if (e == hipSuccess && !skip_l2) {
+    const unsigned n2 = (unsigned)(nt < wgs2 ? nt : wgs2);
+    if (ed_env("EDHIP_SKIP_L2"))      // (debugging aid)
+        skip_l2 = true;
+    if (!skip_l2) {
         if (GRAD)
             hipLaunchKernelGGL((deform_tile3_grad_kernel<T, (ORDER < 1 ? 2 : ORDER), 8>), dim3(n2),
                                dim3(kBlock), lds2, stream, g, ve, t2);
@@ -1961,11 +1667,10 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
                                stream, g, ve, t2);
         e = hipGetLastError();
     }
-    // ---- level 3: whatever is left goes straight through global memory ----------------------------
     if (e == hipSuccess) {
         TileGeom t3 = tg;
         t3.spill = skip_l2 ? list_a : list_b;
-        const unsigned nsp = (unsigned)(ntiles * nb < 512 ? ntiles * nb : 512);
+        const unsigned nsp = (unsigned)(nt < 512 ? nt : 512);
         hipLaunchKernelGGL((deform_tile3_direct_kernel<T, ORDER, GRAD, true>), dim3(nsp), dim3(kBlock),
                            0, stream, g, ve, t3);
         e = hipGetLastError();
@@ -1975,12 +1680,290 @@ hipError_t launch_tile(const GridGeom& g, const IOView& v, hipStream_t stream, c
         (void)hipStreamSynchronize(stream);
         (void)hipMemcpy(&c1, list_a, 4, hipMemcpyDeviceToHost);
         (void)hipMemcpy(&c2, list_b, 4, hipMemcpyDeviceToHost);
-        fprintf(stderr, "edhip: %s tiles %lld, level-2 %d, level-3 %d\n", GRAD ? "K2" : "K1",
-                (long long)(ntiles * nb), c1, c2);
+        fprintf(stderr, "edhip: %s tiles %lld, level-2 %d, level-3 %d\n", GRAD ? "K2" : "K1", (long long)nt, c1, c2);
     }
     return e;
-    }   // floating point T
 }
+
+// float32 / float64 volumes: level 1 (strips, small boxes, highest occupancy), then the spill levels.
+template <typename T, int ORDER, bool PAIR, bool GRAD>
+hipError_t launch_tile_float(const GridGeom& g, const IOView& v, hipStream_t stream, const DeformBatch* batch)
+{
+    TileGeom tg;
+    IOView ve;
+    WideTables w;
+    size_t lds;
+    char* scratch;
+    TileScratch l;
+    hipError_t e = tile_prologue(g, v, sizeof(T), false, ORDER, PAIR, GRAD, stream, batch, tg, ve, w, lds, scratch, l);
+    if (e != hipSuccess || tg.nstrips == 0)
+        return e;
+    // (a plain test: order 0 instantiates the levels below and orders 1-5 the direct launcher, none of them ever
+    // launched -- the library's set of kernels stays what it was)
+    if (ORDER < 1)
+        return launch_tile_direct<T, ORDER, GRAD>(g, ve, tg, stream);
+    const int nb = tg.nbatch;
+    const int64_t ntiles = tg.ntiles, nstrips = tg.nstrips;
+    const bool wide = w.kind != QTables::kWholeGrid;
+    const bool wide_wave = w.kind == QTables::kWavePlain;
+    // level-1 spill feedback (float32, orders 1-5): standard, large or huge boxes, self-serve or the spill levels
+    SpillFeedback fb;
+    if constexpr (std::is_same<T, float>::value && ORDER >= 1)
+        fb = spill_feedback(g, v.mode, ORDER, GRAD, nb, ntiles, stream);
+    if (fb.hint_host) {
+        // (a fixed place in the stream's workspace, whatever the geometry of the call: ed_workspace.h)
+        tg.hint = (int*)(scratch - kWorkspaceHintTail);
+        tg.hint_host = fb.hint_host;
+        tg.hint_seq = fb.hint_seq;
+    }
+    bool tables_done = false;
+    auto tables = [&]() {
+        if (tables_done || e != hipSuccess)
+            return;
+        tables_done = true;
+        e = launch_tables(g, tg, GRAD, stream, batch);
+    };
+    // ---- level 1: strips, small boxes, highest occupancy ------------------------------------------
+    bool hot_done = false;
+    bool served_all = false;        // level 1 ran in self-serve form: no spill list to work off
+    const unsigned nblk = (unsigned)(((nstrips * nb + 7) / 8) * 8);
+    [[maybe_unused]] constexpr bool kBenchKernel = PAIR && ORDER == 3 && sizeof(T) == 4;
+    if constexpr (std::is_same<T, float>::value && ORDER >= 1) {
+        // float32, unit stride along x on both sides: the benchmark kernels of deform_hot.hip
+        if (tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ED_DBG(tg.dbg, 512) && !ed_env("EDHIP_NO_HOT")) {
+            HotGeom hg;
+            fill_hot_geom(hg, tg, ve, v);
+            hg.self_serve = (fb.self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
+            if (v.out16 || wide)
+                hg.self_serve = 1;          // (the spill levels know neither 16-bit storage nor per-strip tables)
+            hg.hint = tg.hint;              // (nullptr: a call without spill feedback)
+            size_t hlds = 0;
+            // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles) -- a function of the
+            // template arguments alone (the forward strips chosen above have at most 4 tiles, K1's limit; a longer one
+            // asked for with EDHIP_STRIP makes launch_k1_level1 decline, and the general kernels take the call)
+            constexpr bool kK1 = !GRAD && ORDER <= 3;
+            // round 6: strips along z on R tables (deform_k1z.hip) for every grid its geometry kernel holds in LDS
+#ifdef EDHIP_NO_K1Z          // (A/B build of the shipped library without the z-walk route: tools/abl_k1_size.sh)
+            const bool k1z = false;
+#else
+            // Which forward kernel (a function of the call's arguments alone: the two routes differ in the last bits).
+            // Measured on shipped builds (profiles/r06_k1_route_sweep.txt): on mild fields the z-walk wins where the
+            // x-strip kernel stumbles -- single volumes whose z and y extents are multiples of 256 (256^3 +7 %,
+            // 512 x 256 x 256 +18 %) -- and loses elsewhere (128^3 -50 %, 192^3 -24 %, 288^3 -10 %, batches -7 ... -26 %: its
+            // geometry kernel costs 20-35 us per call and its tables are per sample); on strong fields (sigma 15) it wins
+            // everywhere by 5-35 %.  The library cannot see the field's strength without a host round trip: the caller
+            // can say so (EDHIP_FLAG_STRONG_FIELD).
+            const bool z_shape = nb == 1 && g.out_len[0] % 256 == 0 && g.out_len[1] % 256 == 0 && g.in_len[0] % 256 == 0 &&
+                                 g.in_len[1] % 256 == 0;
+            const bool z_pick = ed_env("EDHIP_K1Z_ALWAYS") || (batch && batch->strong) || z_shape;
+            const bool k1z = kK1 && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
+#endif
+            ZGeom zg;
+            memset(&zg, 0, sizeof(zg));
+            GeoBuffer* zgeo = nullptr;
+            if (k1z) {
+                (void)k1z_lds_bytes(&hg.small_cap, false);
+                hlds = k1z_lds_bytes(&hg.box_cap, fb.large_boxes);
+                hg.off_box = 0;
+                zgeo = geo_buffer(stream);
+                const K1zGeoLayout gl = k1z_geo_layout(g, ntiles, nb);
+                char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, gl.total, &e) : nullptr;
+                if (!gb)
+                    return e != hipSuccess ? e : hipErrorOutOfMemory;
+                fill_zgeom(zg, g, tg, ORDER, gb, gl);
+                zg.parity = (int)(zgeo->parity & 1);
+#ifdef EDHIP_EXPERIMENTS
+                if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                    hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+#endif
+            } else if (kK1) {
+                int off_small = 0;
+                (void)k1_lds_bytes(hg.ncpx, &hg.small_cap, &off_small, false);
+                if (fb.large_boxes)
+                    hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, true);
+                if (!hlds)
+                    hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, false);
+                tg.slack = (double*)(scratch + l.slack);
+                tg.slack_scale = box_margin_scale(g);
+                hg.slack = tg.slack;
+#ifdef EDHIP_EXPERIMENTS
+                if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                    hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+#endif
+            } else {
+                // the gradient (deform_hot.hip); forward, orders 4 / 5: only whether a box fits next to the Q rows at
+                // all is asked here -- the one-wave kernels below size their own
+                int off_small = 0;
+                (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.small_cap, &off_small, 0);
+                (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.large_cap, &off_small, 1);
+                if (fb.huge_boxes)
+                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 2);
+                if (!hlds && fb.large_boxes)
+                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 1);
+                if (!hlds)
+                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 0);
+            }
+            // (remains: whether a hot box fits next to the Q rows is the level-1 kernels' own arithmetic)
+            if (v.out16 && !hlds)
+                return hipErrorNotSupported;        // (nothing has been launched yet)
+            // (a wide grid whose window leaves no room for a hot box: the general kernels below, same tables)
+            hg.lds_grp = (int)((hlds + 15) & ~(size_t)15);
+            // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes live in a buffer of their own (nothing
+            // else writes it) under a host-side key of everything they depend on.
+            KeepKey* key = nullptr;
+            KeepKey cur;
+            memset(&cur, 0, sizeof(cur));
+            const int box_mode = batch ? batch->box_mode : 0;
+            if (hlds && box_mode && !ed_env("EDHIP_NO_BOXES")) {
+                hipError_t ke = hipSuccess;
+                int* kb = (int*)keep_reserve(stream, ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255, &key, &ke);
+                if (kb) {
+                    fill_keep_key(cur, g, tg, ORDER, *batch);
+                    if (!GRAD && box_mode == 1) {
+                        hg.boxes = kb;
+                        *key = KeepKey();                  // not valid until this launch is in the stream
+                    } else if (GRAD && box_mode == 2 && ORDER >= 3 && memcmp(key, &cur, sizeof(cur)) == 0) {
+                        // (orders 1 / 2: the box pass is a small part of a short tile, and the
+                        // hand-over's bookkeeping costs more than it saves: 190 -> 196, 242 -> 252 us)
+                        hg.boxes = kb;
+                        hg.use_boxes = 1;
+                        if (fb.self_serve_boxes && ORDER <= 3)
+                            hg.self_serve = 1;
+                    }
+                }
+            }
+            if (k1z && e == hipSuccess) {
+                // the geometry kernel in place of the tables kernel: R, the z table, tile records (and boxes), work lists
+                GridPrefilter gp;
+                const bool own = take_grid_prefilter(batch, nb, 0, gp);
+                e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
+                if (e == hipSuccess)
+                    ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
+                if (own && e == hipSuccess)
+                    batch->gridpf_done = true;
+                tables_done = true;
+            }
+            tables();
+            profile_mark(false, stream);
+            // Orders 4 / 5 run on the wave-per-tile kernels (deform_wave.hip: one wavefront per tile,
+            // one copy of the box, tiles that do not fit taken as two x-halves): the 4-wave kernels
+            // give up on a tile as soon as its 5- / 6-tap windows need the wide row pitch, and at
+            // these orders that is a large share of the tiles (256^3, sigma 5, whole call: order 4
+            // forward 419 -> 339 us, order 5 gradient 944 -> 886 us; profiles/r03_wave_vs_4wave.txt).
+            // Orders 1-3 stay on the 4-wave kernels, which are 10-30 % faster there.
+            int wave_mode = ORDER >= 4 ? 3 : 0;
+#ifdef EDHIP_EXPERIMENTS
+            if (const char* wm = ed_env("EDHIP_WAVE"))        // 1 forward, 2 gradient, 3 both, 0 neither
+                wave_mode = atoi(wm);
+#endif
+            if ((hlds || wide_wave) && (wave_mode & (GRAD ? 2 : 1))) {
+                HotGeom wg = hg;
+                wg.self_serve = 0;
+                int wstart = 4;
+#ifdef EDHIP_EXPERIMENTS
+                if (const char* st = ed_env("EDHIP_WAVE_STRIP"))
+                    wstart = atoi(st);
+#endif
+                const int64_t across = (int64_t)tg.tiles[0] * tg.tiles[1];
+                wg.strip_tiles = shorten_strips(wstart, 1, 8192, nb, across, tg.tiles[2]);
+                wg.strips_x = (tg.tiles[2] + wg.strip_tiles - 1) / wg.strip_tiles;
+                const int64_t wstrips = strip_count(1, across, tg.tiles[2], wg.strip_tiles);
+                // (no more strips than tiles, which the prologue has bounded)
+                if (wstrips * nb <= 0x3fffffffLL) {
+                    wg.nstrips = (int)wstrips;
+                    wg.total_strips = (int)(wstrips * nb);
+                    int occ = 3;
+#ifdef EDHIP_EXPERIMENTS
+                    if (const char* oc = ed_env("EDHIP_WAVE_OCC"))
+                        occ = atoi(oc);
+#endif
+                    size_t wlds = wave_lds_bytes(GRAD, occ, &wg.box_cap);
+                    // spill feedback: larger boxes (fewer waves per CU) once the geometry's calls spill.
+                    // 256^3 sigma 10, whole call: order 4 forward 453 -> 420 us, gradient 694 -> 662;
+                    // order 5 forward 1019 -> 657, gradient 1238 -> 1055 (sigma 5: +20 .. +40 us)
+                    wg.small_cap = wg.box_cap;
+                    if (fb.large_boxes) {
+                        wlds = (ORDER == 5 && !GRAD) ? 20480 : 16384;
+                        wg.box_cap = (int)((wlds - 416) / 4);
+                    }
+#ifdef EDHIP_EXPERIMENTS
+                    if (const char* kb = ed_env("EDHIP_WAVE_LDS")) {
+                        wlds = (size_t)atoi(kb);
+                        wg.box_cap = (int)((wlds - 416) / 4);
+                    }
+                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                        wg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+#endif
+                    const unsigned wblk = (unsigned)(((wstrips * nb + 7) / 8) * 8);
+                    const hipError_t he = launch_wave_level1(wg, ORDER, GRAD, wblk, wlds, occ, stream);
+                    if (he == hipSuccess) {
+                        hot_done = true;
+                        if (!GRAD && hg.boxes && key)
+                            *key = cur;
+                    } else if (he != hipErrorNotSupported || wide_wave)
+                        e = he;
+                }
+            }
+            // (remains: whether the one-wave kernels take a call is launch_wave_level1's own answer)
+            if (wide_wave && !hot_done && e == hipSuccess)
+                e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
+            if (hlds && !hot_done && e == hipSuccess) {
+                // (forward, orders 4 / 5, when the one-wave kernels did not take the call: the general kernels below)
+                hipError_t he = hipErrorNotSupported;
+                if (k1z)
+                    he = launch_k1z(hg, zg, ORDER, hlds, stream);
+                else if (kK1)
+                    he = launch_k1_level1(hg, ORDER, nblk, hlds, stream);
+                else if (GRAD)
+                    he = launch_hot_grad_level1(hg, ORDER, nblk, hlds, stream);
+                if (he == hipSuccess) {
+                    hot_done = true;
+                    served_all = hg.self_serve != 0 || k1z;
+                    if (!GRAD && hg.boxes && key)
+                        *key = cur;
+                } else if (he != hipErrorNotSupported || v.out16 || wide)
+                    e = he;
+            }
+        }
+    }
+    if (!tables_done) {
+        tables();
+        profile_mark(false, stream);
+    }
+    if (hot_done || e != hipSuccess)
+        ;
+    else if (GRAD)
+        hipLaunchKernelGGL((deform_tile3_grad_kernel<T, (ORDER < 1 ? 2 : ORDER), 16>), dim3(nblk),
+                           dim3(kBlock), lds, stream, g, ve, tg);
+#ifdef EDHIP_EXPERIMENTS
+    else if (kBenchKernel && tg.dbg) {
+        if constexpr (kBenchKernel) {
+        // profiling builds of the benchmark kernel (EDHIP_TILE_DBG), never used otherwise
+        switch (tg.dbg) {
+        case 2: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 2>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        case 4: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 4>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        case 6: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 6>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        case 16: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 16>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        case 64: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 64>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        case 38: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 38>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        default: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 0>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+        }
+        }
+    }
+#endif
+    else
+        hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR>), dim3(nblk), dim3(kBlock),
+                           lds, stream, g, ve, tg);
+    e = hipGetLastError();
+    profile_mark(true, stream);
+    if (served_all)
+        return e;               // level 1 has served every tile
+    if (e != hipSuccess)
+        return e;
+    // (plain tables of a wide grid: straight to the direct level, the level-2 kernel stages Q rows like the others)
+    return launch_spill_levels<T, ORDER, GRAD>(g, ve, tg, wide_wave, stream);
+}
+
 
 }  // namespace
 
@@ -2001,16 +1984,11 @@ size_t deform_tile_workspace_bytes(const GridGeom& g, int nbatch, bool f64)
 {
     if (g.naxis != 3)
         return kWorkspaceGridBytes;
-    int64_t ntiles = 1;
-    for (int k = 0; k < 3; ++k)
-        ntiles *= (g.out_len[k] + kT - 1) / kT;
-    const size_t list_bytes = (sizeof(int) * ((size_t)ntiles * nbatch + 1) + 63) & ~(size_t)63;
-    const size_t xt_bytes = xt_block_bytes(g, nbatch);
-    const size_t q = q_global_bytes(g, f64 && nbatch == 1);       // (float64 volumes may take the per-strip layout)
-    if (q > ((size_t)512 << 20))
+    // (float64 volumes may take the optional per-strip layout: reserved wherever a call of the geometry can ask for it)
+    const TileScratch l = tile_scratch_layout(g, nbatch, f64 && nbatch == 1);
+    if (l.q_stride > kQTableMaxBytes)
         return kWorkspaceGridBytes;
-    return kWorkspaceGridBytes + 2 * list_bytes + xt_bytes + ((q * (size_t)nbatch + 63) & ~(size_t)63) +
-           label_list_bytes(g);
+    return kWorkspaceGridBytes + l.total;
 }
 
 bool deform_tile_supported(const GridGeom& g, const IOView& v, int gradient)
@@ -2019,34 +1997,14 @@ bool deform_tile_supported(const GridGeom& g, const IOView& v, int gradient)
         return false;
     if (!deform_fast_supported(g, v, gradient))
         return false;
-    const int64_t esz = v.in_dtype == EDHIP_F32 ? 4 : 8;
-    int64_t in_span = 0, out_span = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (g.in_len[k] >= 0x3fffffff || g.out_len[k] >= 0x3fffffff || g.ncp[k] > 1024)
-            return false;
-        const int64_t si = v.in_stride[k] / esz, so = v.out_stride[k] / esz;
-        in_span += (si < 0 ? -si : si) * (g.in_len[k] - 1);
-        out_span += (so < 0 ? -so : so) * (g.out_len[k] - 1);
-    }
-    if (in_span >= 0x7fffffffLL || out_span >= 0x7fffffffLL)   // 32-bit element offsets inside a volume
+    const bool f32 = v.in_dtype == EDHIP_F32;
+    const int64_t esz = f32 ? 4 : 8;
+    // head + Q + box must stay within a 64 KiB block.  Wider control grids (wide_tables, ed_tile_host.h): per-strip Q
+    // tables or the one-wave kernels' plain ones, everything else goes to the row kernel of deform_fast.hip.  (The
+    // number of samples is not known here: the launcher declines a batch of a wide grid.)
+    if (wide_tables(g, !f32, v.order, v.in_stride[2] == esz && v.out_stride[2] == esz, 1).kind == QTables::kNone)
         return false;
-    // head + Q + box must stay within a 64 KiB block; the per-call Q table within 512 MiB; the
-    // tables kernel keeps 3 * ncp_y * ncp_x doubles in LDS.  Wider control grids: float32 volumes of orders 1-3 with
-    // unit stride along x go to the level-1 kernels on per-strip Q tables (launch_tile), everything else to the
-    // row kernel of deform_fast.hip
-    if (wide_grid(g)) {
-        if (v.order < 1)
-            return false;
-        // float32 orders 4 / 5 with unit stride along x: the one-wave kernels, plain tables, any width; everything else
-        // on per-strip tables, whose window has to fit
-        const bool wave = v.in_dtype == EDHIP_F32 && v.order >= 4 && v.in_stride[2] == 4 && v.out_stride[2] == 4;
-        if (!wave &&
-            (wide_window(g) > kWideMaxWin || (g.out_len[2] + kWideStripTiles * kT - 1) / (kWideStripTiles * kT) > 256))
-            return false;
-    }
-    if (q_global_bytes(g) > ((size_t)512 << 20) || 24 * (size_t)g.ncp[1] * (size_t)g.ncp[2] > 48 * 1024)
-        return false;
-    return true;
+    return tile_addressable(g, v, esz, false);
 }
 
 static int label_elem_size(int dt)
@@ -2066,29 +2024,10 @@ bool deform_label_supported(const GridGeom& g, const IOView& v, int gradient)
     const int64_t esz = label_elem_size(v.in_dtype);
     if (((uintptr_t)v.in % esz) || ((uintptr_t)v.out % esz))
         return false;
-    int64_t in_span = 0, out_span = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (g.in_len[k] >= 0x3fffffff || g.out_len[k] >= 0x3fffffff || g.ncp[k] > 1024)
-            return false;
-        if (v.in_stride[k] % esz || v.out_stride[k] % esz)
-            return false;
-        const int64_t si = v.in_stride[k] / esz, so = v.out_stride[k] / esz;
-        in_span += (si < 0 ? -si : si) * (g.in_len[k] - 1);
-        out_span += (so < 0 ? -so : so) * (g.out_len[k] - 1);
-    }
-    for (int l = 0; l < v.nstep; ++l)
-        if (v.in_step_stride[l] % esz || v.out_step_stride[l] % esz)
-            return false;
-    if (in_span >= 0x7fffffffLL || out_span >= 0x7fffffffLL)
-        return false;
-    if (q_global_bytes(g) > ((size_t)512 << 20) || 24 * (size_t)g.ncp[1] * (size_t)g.ncp[2] > 48 * 1024)
-        return false;
     // wide control grids (per-strip Q tables) are a float route: label maps and the integer fast path stay on whole-grid
-    // tables, beyond them the exact kernels take the volume.  (This test was missing: launch_tile declined such a call
+    // tables, beyond them the exact kernels take the volume.  (This test was missing: the launcher declined such a call
     // AFTER the route had been chosen and edhip_deform failed with "operation not supported" -- found by fuzz_api.py.)
-    if (wide_grid(g))
-        return false;
-    return true;
+    return tile_addressable(g, v, esz, true) && !wide_grid(g);
 }
 
 // integer fast path: 8- / 16-bit volumes, orders 1-5, forward, unit stride along the last deformed axis
@@ -2118,9 +2057,9 @@ hipError_t launch_deform_int(const GridGeom& g, const IOView& v, hipStream_t str
     if (!deform_int_supported(g, v, 0))
         return hipErrorNotSupported;
     switch (label_elem_size(v.in_dtype)) {
-    case 1: return launch_tile<uint8_t, 0, false, false>(g, v, stream, batch);
-    case 2: return launch_tile<uint16_t, 0, false, false>(g, v, stream, batch);
-    default: return launch_tile<uint32_t, 0, false, false>(g, v, stream, batch);
+    case 1: return launch_tile_int<uint8_t>(g, v, stream, batch);
+    case 2: return launch_tile_int<uint16_t>(g, v, stream, batch);
+    default: return launch_tile_int<uint32_t>(g, v, stream, batch);
     }
 }
 
@@ -2129,10 +2068,10 @@ hipError_t launch_deform_label(const GridGeom& g, const IOView& v, hipStream_t s
     if (!deform_label_supported(g, v, 0))
         return hipErrorNotSupported;
     switch (label_elem_size(v.in_dtype)) {
-    case 1: return launch_tile<uint8_t, 0, false, false>(g, v, stream, batch);
-    case 2: return launch_tile<uint16_t, 0, false, false>(g, v, stream, batch);
-    case 4: return launch_tile<uint32_t, 0, false, false>(g, v, stream, batch);
-    default: return launch_tile<uint64_t, 0, false, false>(g, v, stream, batch);
+    case 1: return launch_tile_int<uint8_t>(g, v, stream, batch);
+    case 2: return launch_tile_int<uint16_t>(g, v, stream, batch);
+    case 4: return launch_tile_int<uint32_t>(g, v, stream, batch);
+    default: return launch_tile_int<uint64_t>(g, v, stream, batch);
     }
 }
 
@@ -2148,49 +2087,49 @@ hipError_t launch_deform_tile(const GridGeom& g, const IOView& v, int gradient, 
         // direct kernel (forward gathers / float atomics)
         if (gradient) {
             if (f32)
-                return v.order == 0 ? launch_tile<float, 0, false, true>(g, v, stream, batch)
-                                    : launch_tile<float, 1, false, true>(g, v, stream, batch);
-            return v.order == 0 ? launch_tile<double, 0, false, true>(g, v, stream, batch)
-                                : launch_tile<double, 1, false, true>(g, v, stream, batch);
+                return v.order == 0 ? launch_tile_float<float, 0, false, true>(g, v, stream, batch)
+                                    : launch_tile_float<float, 1, false, true>(g, v, stream, batch);
+            return v.order == 0 ? launch_tile_float<double, 0, false, true>(g, v, stream, batch)
+                                : launch_tile_float<double, 1, false, true>(g, v, stream, batch);
         }
         if (f32)
-            return v.order == 0 ? launch_tile<float, 0, false, false>(g, v, stream, batch)
-                                : launch_tile<float, 1, true, false>(g, v, stream, batch);
-        return v.order == 0 ? launch_tile<double, 0, false, false>(g, v, stream, batch)
-                            : launch_tile<double, 1, false, false>(g, v, stream, batch);
+            return v.order == 0 ? launch_tile_float<float, 0, false, false>(g, v, stream, batch)
+                                : launch_tile_float<float, 1, true, false>(g, v, stream, batch);
+        return v.order == 0 ? launch_tile_float<double, 0, false, false>(g, v, stream, batch)
+                            : launch_tile_float<double, 1, false, false>(g, v, stream, batch);
     }
     if (gradient) {
         if (f32) {
             switch (v.order) {
-            case 2: return launch_tile<float, 2, false, true>(g, v, stream, batch);
-            case 3: return launch_tile<float, 3, false, true>(g, v, stream, batch);
-            case 4: return launch_tile<float, 4, false, true>(g, v, stream, batch);
-            case 5: return launch_tile<float, 5, false, true>(g, v, stream, batch);
+            case 2: return launch_tile_float<float, 2, false, true>(g, v, stream, batch);
+            case 3: return launch_tile_float<float, 3, false, true>(g, v, stream, batch);
+            case 4: return launch_tile_float<float, 4, false, true>(g, v, stream, batch);
+            case 5: return launch_tile_float<float, 5, false, true>(g, v, stream, batch);
             default: return hipErrorNotSupported;
             }
         }
         switch (v.order) {
-        case 2: return launch_tile<double, 2, false, true>(g, v, stream, batch);
-        case 3: return launch_tile<double, 3, false, true>(g, v, stream, batch);
-        case 4: return launch_tile<double, 4, false, true>(g, v, stream, batch);
-        case 5: return launch_tile<double, 5, false, true>(g, v, stream, batch);
+        case 2: return launch_tile_float<double, 2, false, true>(g, v, stream, batch);
+        case 3: return launch_tile_float<double, 3, false, true>(g, v, stream, batch);
+        case 4: return launch_tile_float<double, 4, false, true>(g, v, stream, batch);
+        case 5: return launch_tile_float<double, 5, false, true>(g, v, stream, batch);
         default: return hipErrorNotSupported;
         }
     }
     if (f32) {
         switch (v.order) {
-        case 2: return launch_tile<float, 2, true, false>(g, v, stream, batch);
-        case 3: return launch_tile<float, 3, true, false>(g, v, stream, batch);
-        case 4: return launch_tile<float, 4, true, false>(g, v, stream, batch);
-        case 5: return launch_tile<float, 5, true, false>(g, v, stream, batch);
+        case 2: return launch_tile_float<float, 2, true, false>(g, v, stream, batch);
+        case 3: return launch_tile_float<float, 3, true, false>(g, v, stream, batch);
+        case 4: return launch_tile_float<float, 4, true, false>(g, v, stream, batch);
+        case 5: return launch_tile_float<float, 5, true, false>(g, v, stream, batch);
         default: return hipErrorNotSupported;
         }
     }
     switch (v.order) {
-    case 2: return launch_tile<double, 2, false, false>(g, v, stream, batch);
-    case 3: return launch_tile<double, 3, false, false>(g, v, stream, batch);
-    case 4: return launch_tile<double, 4, false, false>(g, v, stream, batch);
-    case 5: return launch_tile<double, 5, false, false>(g, v, stream, batch);
+    case 2: return launch_tile_float<double, 2, false, false>(g, v, stream, batch);
+    case 3: return launch_tile_float<double, 3, false, false>(g, v, stream, batch);
+    case 4: return launch_tile_float<double, 4, false, false>(g, v, stream, batch);
+    case 5: return launch_tile_float<double, 5, false, false>(g, v, stream, batch);
     default: return hipErrorNotSupported;
     }
 }

@@ -62,6 +62,10 @@ struct GridStamp {
     long long shape[9] = {}, stride[9] = {};
 };
 GridStamp* grid_stamp(hipStream_t stream);
+// The control grid uses at most 32 KiB of the workspace head (its first kWorkspaceGridBytes, ed_params.h); the tail of
+// the head holds two fixed slots, whatever the geometry of the call -- bytes back from the end of the head:
+constexpr size_t kWorkspaceHintTail = 128;      // the tile path's spill counters (TileGeom::hint), 64 bytes
+constexpr size_t kWorkspaceBoxTail = 64;        // the 64 result bytes of edhip_source_box / edhip_source_window
 // counts the times the stream's workspace buffer was freed or replaced (a stamp from an earlier generation is void)
 unsigned long long workspace_generation(hipStream_t stream);
 

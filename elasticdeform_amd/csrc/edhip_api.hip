@@ -886,11 +886,11 @@ int edhip_source_box(const edhip_array* displacement, const int64_t* in_len, con
         if (int st = stage_raw_grid(displacement, flags, stream, false, g, nullptr, err, errlen))
             return st;
     hipError_t e = hipSuccess;
-    // the box lives in the last bytes of the workspace head (the control grid uses at most 32 KiB)
+    // the box lives in the last bytes of the workspace head (ed_workspace.h)
     char* ws = (char*)workspace_reserve(stream, deform_tile_workspace_bytes(g), &e);
     if (!ws)
         return hip_fail(err, errlen, e, "scratch allocation");
-    int* dbox = (int*)(ws + kWorkspaceGridBytes - 64);
+    int* dbox = (int*)(ws + kWorkspaceGridBytes - kWorkspaceBoxTail);
     e = launch_source_box(g, dbox, stream, (flags & EDHIP_FLAG_FAST) != 0);
     if (e == hipErrorNotSupported)
         return fail(err, errlen, EDHIP_ERR_UNSUPPORTED,
@@ -1130,7 +1130,7 @@ int edhip_source_window(const edhip_array* displacement, const int64_t* in_len, 
     char* ws = (char*)workspace_reserve(stream, deform_tile_workspace_bytes(g), &e);
     if (!ws)
         return hip_fail(err, errlen, e, "scratch allocation");
-    int* dbox = (int*)(ws + kWorkspaceGridBytes - 64);
+    int* dbox = (int*)(ws + kWorkspaceGridBytes - kWorkspaceBoxTail);
     e = launch_source_box(g, dbox, stream, true, &sw);
     if (e != hipSuccess)
         return hip_fail(err, errlen, e, "source window launch");

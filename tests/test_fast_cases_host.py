@@ -271,7 +271,7 @@ def test_the_constants_are_the_sources():
         assert fast[name] == getattr(fc, name), name
     tile_h = _constexpr(open(os.path.join(CSRC, "ed_tile.h")).read())
     assert tile_h["kT"] == fc.kT and tile_h["kOffQ"] == fc.kOffQ
-    tile = open(os.path.join(CSRC, "deform_tile.hip")).read()
+    tile = open(os.path.join(CSRC, "ed_tile_host.h")).read()       # (the tile launcher's host arithmetic)
     wide = _constexpr(tile, tile_h)
     assert wide["kWideStripTiles"] == fc.kWideStripTiles and wide["kWideMaxWin"] == fc.kWideMaxWin
     assert "24 * (size_t)g.ncp[1] * (size_t)g.ncp[2] > 48 * 1024" in tile
