@@ -1111,10 +1111,16 @@ hipError_t launch_typed(const GridGeom& g, const IOView& v, int gradient, hipStr
             return hipGetLastError();
         }
     }
-    if (gradient)
-        hipLaunchKernelGGL((deform_fast_kernel<T, NAXIS, ORDER, true>), dim3((unsigned)nblk),
-                           dim3(kBlock), 0, stream, g, ve, fv, nrows, (int)xblocks, rows);
-    else
+    // The row kernel's gradient form.  Two axes, orders 1-5, and four axes, order 3: the kernels above take every such
+    // call (four axes beyond kMaxE4: declined by deform_fast_supported), and only their switches send one here.
+    constexpr bool kGradAbove = (NAXIS == 2 && ORDER >= 1) || (NAXIS == 4 && ORDER == 3);
+    if (gradient) {
+        if constexpr (kGradAbove && !kEdExperiments)
+            return hipErrorNotSupported;
+        else
+            hipLaunchKernelGGL((deform_fast_kernel<T, NAXIS, ORDER, true>), dim3((unsigned)nblk),
+                               dim3(kBlock), 0, stream, g, ve, fv, nrows, (int)xblocks, rows);
+    } else
         hipLaunchKernelGGL((deform_fast_kernel<T, NAXIS, ORDER, false>), dim3((unsigned)nblk),
                            dim3(kBlock), 0, stream, g, ve, fv, nrows, (int)xblocks, rows);
     return hipGetLastError();

@@ -649,10 +649,17 @@ hipError_t launch_hot_grad_level1(const HotGeom& hg, int order, unsigned nblk, s
     case 1: return launch_grad_order<1>(hg, nblk, lds, stream);
     case 2: return launch_grad_order<2>(hg, nblk, lds, stream);
     case 3: return launch_grad_order<3>(hg, nblk, lds, stream);
-    case 4: return launch_grad_order<4>(hg, nblk, lds, stream);
-    case 5: return launch_grad_order<5>(hg, nblk, lds, stream);
-    default: return hipErrorNotSupported;
+    default: break;
     }
+    // orders 4 / 5: the one-wave kernels of deform_wave.hip take every such call that has a hot box (launch_tile_float:
+    // wave_mode), and only EDHIP_WAVE of the experiments builds sends one here
+    if constexpr (kEdExperiments) {
+        if (order == 4)
+            return launch_grad_order<4>(hg, nblk, lds, stream);
+        if (order == 5)
+            return launch_grad_order<5>(hg, nblk, lds, stream);
+    }
+    return hipErrorNotSupported;
 }
 
 }  // namespace tile

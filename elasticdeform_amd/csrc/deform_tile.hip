@@ -1618,12 +1618,12 @@ hipError_t launch_tile_int(const GridGeom& g, const IOView& v, hipStream_t strea
 }
 
 // Order 0: one tap per voxel, no source box, straight from / to global memory.
-template <typename T, int ORDER, bool GRAD>
+template <typename T, bool GRAD>
 hipError_t launch_tile_direct(const GridGeom& g, const IOView& ve, const TileGeom& tg, hipStream_t stream)
 {
     const int64_t nt = (int64_t)tg.ntiles * tg.nbatch;
     const unsigned nblk = (unsigned)(nt < (1 << 20) ? nt : (1 << 20));
-    hipLaunchKernelGGL((deform_tile3_direct_kernel<T, ORDER, GRAD, false>), dim3(nblk), dim3(kBlock), 0, stream, g, ve, tg);
+    hipLaunchKernelGGL((deform_tile3_direct_kernel<T, 0, GRAD, false>), dim3(nblk), dim3(kBlock), 0, stream, g, ve, tg);
     return hipGetLastError();
 }
 
@@ -1660,8 +1660,7 @@ hipError_t launch_spill_levels(const GridGeom& g, const IOView& ve, const TileGe
         skip_l2 = true;
     if (!skip_l2) {
         if (GRAD)
-            hipLaunchKernelGGL((deform_tile3_grad_kernel<T, (ORDER < 1 ? 2 : ORDER), 8>), dim3(n2),
-                               dim3(kBlock), lds2, stream, g, ve, t2);
+            hipLaunchKernelGGL((deform_tile3_grad_kernel<T, ORDER, 8>), dim3(n2), dim3(kBlock), lds2, stream, g, ve, t2);
         else
             hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, false>), dim3(n2), dim3(kBlock), lds2,
                                stream, g, ve, t2);
@@ -1685,7 +1684,8 @@ hipError_t launch_spill_levels(const GridGeom& g, const IOView& ve, const TileGe
     return e;
 }
 
-// float32 / float64 volumes: level 1 (strips, small boxes, highest occupancy), then the spill levels.
+// float32 / float64 volumes.  Order 0: the direct launcher.  Orders 1-5: level 1 (strips, small boxes, highest
+// occupancy), then the spill levels.  Each order instantiates its own side alone.
 template <typename T, int ORDER, bool PAIR, bool GRAD>
 hipError_t launch_tile_float(const GridGeom& g, const IOView& v, hipStream_t stream, const DeformBatch* batch)
 {
@@ -1698,270 +1698,270 @@ hipError_t launch_tile_float(const GridGeom& g, const IOView& v, hipStream_t str
     hipError_t e = tile_prologue(g, v, sizeof(T), false, ORDER, PAIR, GRAD, stream, batch, tg, ve, w, lds, scratch, l);
     if (e != hipSuccess || tg.nstrips == 0)
         return e;
-    // (a plain test: order 0 instantiates the levels below and orders 1-5 the direct launcher, none of them ever
-    // launched -- the library's set of kernels stays what it was)
-    if (ORDER < 1)
-        return launch_tile_direct<T, ORDER, GRAD>(g, ve, tg, stream);
-    const int nb = tg.nbatch;
-    const int64_t ntiles = tg.ntiles, nstrips = tg.nstrips;
-    const bool wide = w.kind != QTables::kWholeGrid;
-    const bool wide_wave = w.kind == QTables::kWavePlain;
-    // level-1 spill feedback (float32, orders 1-5): standard, large or huge boxes, self-serve or the spill levels
-    SpillFeedback fb;
-    if constexpr (std::is_same<T, float>::value && ORDER >= 1)
-        fb = spill_feedback(g, v.mode, ORDER, GRAD, nb, ntiles, stream);
-    if (fb.hint_host) {
-        // (a fixed place in the stream's workspace, whatever the geometry of the call: ed_workspace.h)
-        tg.hint = (int*)(scratch - kWorkspaceHintTail);
-        tg.hint_host = fb.hint_host;
-        tg.hint_seq = fb.hint_seq;
-    }
-    bool tables_done = false;
-    auto tables = [&]() {
-        if (tables_done || e != hipSuccess)
-            return;
-        tables_done = true;
-        e = launch_tables(g, tg, GRAD, stream, batch);
-    };
-    // ---- level 1: strips, small boxes, highest occupancy ------------------------------------------
-    bool hot_done = false;
-    bool served_all = false;        // level 1 ran in self-serve form: no spill list to work off
-    const unsigned nblk = (unsigned)(((nstrips * nb + 7) / 8) * 8);
-    [[maybe_unused]] constexpr bool kBenchKernel = PAIR && ORDER == 3 && sizeof(T) == 4;
-    if constexpr (std::is_same<T, float>::value && ORDER >= 1) {
-        // float32, unit stride along x on both sides: the benchmark kernels of deform_hot.hip
-        if (tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ED_DBG(tg.dbg, 512) && !ed_env("EDHIP_NO_HOT")) {
-            HotGeom hg;
-            fill_hot_geom(hg, tg, ve, v);
-            hg.self_serve = (fb.self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
-            if (v.out16 || wide)
-                hg.self_serve = 1;          // (the spill levels know neither 16-bit storage nor per-strip tables)
-            hg.hint = tg.hint;              // (nullptr: a call without spill feedback)
-            size_t hlds = 0;
-            // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles) -- a function of the
-            // template arguments alone (the forward strips chosen above have at most 4 tiles, K1's limit; a longer one
-            // asked for with EDHIP_STRIP makes launch_k1_level1 decline, and the general kernels take the call)
-            constexpr bool kK1 = !GRAD && ORDER <= 3;
-            // round 6: strips along z on R tables (deform_k1z.hip) for every grid its geometry kernel holds in LDS
+    if constexpr (ORDER < 1) {
+        return launch_tile_direct<T, GRAD>(g, ve, tg, stream);
+    } else {
+        const int nb = tg.nbatch;
+        const int64_t ntiles = tg.ntiles, nstrips = tg.nstrips;
+        const bool wide = w.kind != QTables::kWholeGrid;
+        const bool wide_wave = w.kind == QTables::kWavePlain;
+        // level-1 spill feedback (float32, orders 1-5): standard, large or huge boxes, self-serve or the spill levels
+        SpillFeedback fb;
+        if constexpr (std::is_same<T, float>::value)
+            fb = spill_feedback(g, v.mode, ORDER, GRAD, nb, ntiles, stream);
+        if (fb.hint_host) {
+            // (a fixed place in the stream's workspace, whatever the geometry of the call: ed_workspace.h)
+            tg.hint = (int*)(scratch - kWorkspaceHintTail);
+            tg.hint_host = fb.hint_host;
+            tg.hint_seq = fb.hint_seq;
+        }
+        bool tables_done = false;
+        auto tables = [&]() {
+            if (tables_done || e != hipSuccess)
+                return;
+            tables_done = true;
+            e = launch_tables(g, tg, GRAD, stream, batch);
+        };
+        // ---- level 1: strips, small boxes, highest occupancy ------------------------------------------
+        bool hot_done = false;
+        bool served_all = false;        // level 1 ran in self-serve form: no spill list to work off
+        const unsigned nblk = (unsigned)(((nstrips * nb + 7) / 8) * 8);
+        [[maybe_unused]] constexpr bool kBenchKernel = PAIR && ORDER == 3 && sizeof(T) == 4;
+        if constexpr (std::is_same<T, float>::value) {
+            // float32, unit stride along x on both sides: the benchmark kernels of deform_hot.hip
+            if (tg.in_stride[2] == 1 && tg.out_stride[2] == 1 && !ED_DBG(tg.dbg, 512) && !ed_env("EDHIP_NO_HOT")) {
+                HotGeom hg;
+                fill_hot_geom(hg, tg, ve, v);
+                hg.self_serve = (fb.self_serve && ORDER <= 3) ? 1 : 0;      // (orders 4 / 5: the one-wave kernels, which spill as before)
+                if (v.out16 || wide)
+                    hg.self_serve = 1;          // (the spill levels know neither 16-bit storage nor per-strip tables)
+                hg.hint = tg.hint;              // (nullptr: a call without spill feedback)
+                size_t hlds = 0;
+                // forward, orders 1-3: K1 of round 5 (deform_k1.hip: sampled tile boxes, fast tiles) -- a function of the
+                // template arguments alone (the forward strips chosen above have at most 4 tiles, K1's limit; a longer one
+                // asked for with EDHIP_STRIP makes launch_k1_level1 decline, and the general kernels take the call)
+                constexpr bool kK1 = !GRAD && ORDER <= 3;
+                // round 6: strips along z on R tables (deform_k1z.hip) for every grid its geometry kernel holds in LDS
 #ifdef EDHIP_NO_K1Z          // (A/B build of the shipped library without the z-walk route: tools/abl_k1_size.sh)
-            const bool k1z = false;
+                const bool k1z = false;
 #else
-            // Which forward kernel (a function of the call's arguments alone: the two routes differ in the last bits).
-            // Measured on shipped builds (profiles/r06_k1_route_sweep.txt): on mild fields the z-walk wins where the
-            // x-strip kernel stumbles -- single volumes whose z and y extents are multiples of 256 (256^3 +7 %,
-            // 512 x 256 x 256 +18 %) -- and loses elsewhere (128^3 -50 %, 192^3 -24 %, 288^3 -10 %, batches -7 ... -26 %: its
-            // geometry kernel costs 20-35 us per call and its tables are per sample); on strong fields (sigma 15) it wins
-            // everywhere by 5-35 %.  The library cannot see the field's strength without a host round trip: the caller
-            // can say so (EDHIP_FLAG_STRONG_FIELD).
-            const bool z_shape = nb == 1 && g.out_len[0] % 256 == 0 && g.out_len[1] % 256 == 0 && g.in_len[0] % 256 == 0 &&
-                                 g.in_len[1] % 256 == 0;
-            const bool z_pick = ed_env("EDHIP_K1Z_ALWAYS") || (batch && batch->strong) || z_shape;
-            const bool k1z = kK1 && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
+                // Which forward kernel (a function of the call's arguments alone: the two routes differ in the last bits).
+                // Measured on shipped builds (profiles/r06_k1_route_sweep.txt): on mild fields the z-walk wins where the
+                // x-strip kernel stumbles -- single volumes whose z and y extents are multiples of 256 (256^3 +7 %,
+                // 512 x 256 x 256 +18 %) -- and loses elsewhere (128^3 -50 %, 192^3 -24 %, 288^3 -10 %, batches -7 ... -26 %: its
+                // geometry kernel costs 20-35 us per call and its tables are per sample); on strong fields (sigma 15) it wins
+                // everywhere by 5-35 %.  The library cannot see the field's strength without a host round trip: the caller
+                // can say so (EDHIP_FLAG_STRONG_FIELD).
+                const bool z_shape = nb == 1 && g.out_len[0] % 256 == 0 && g.out_len[1] % 256 == 0 && g.in_len[0] % 256 == 0 &&
+                                     g.in_len[1] % 256 == 0;
+                const bool z_pick = ed_env("EDHIP_K1Z_ALWAYS") || (batch && batch->strong) || z_shape;
+                const bool k1z = kK1 && !wide && z_pick && k1z_supported(g) && ve.nsteps <= (int64_t)kK1zMaxSteps && !ed_env("EDHIP_K1_R5");
 #endif
-            ZGeom zg;
-            memset(&zg, 0, sizeof(zg));
-            GeoBuffer* zgeo = nullptr;
-            if (k1z) {
-                (void)k1z_lds_bytes(&hg.small_cap, false);
-                hlds = k1z_lds_bytes(&hg.box_cap, fb.large_boxes);
-                hg.off_box = 0;
-                zgeo = geo_buffer(stream);
-                const K1zGeoLayout gl = k1z_geo_layout(g, ntiles, nb);
-                char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, gl.total, &e) : nullptr;
-                if (!gb)
-                    return e != hipSuccess ? e : hipErrorOutOfMemory;
-                fill_zgeom(zg, g, tg, ORDER, gb, gl);
-                zg.parity = (int)(zgeo->parity & 1);
+                ZGeom zg;
+                memset(&zg, 0, sizeof(zg));
+                GeoBuffer* zgeo = nullptr;
+                if (k1z) {
+                    (void)k1z_lds_bytes(&hg.small_cap, false);
+                    hlds = k1z_lds_bytes(&hg.box_cap, fb.large_boxes);
+                    hg.off_box = 0;
+                    zgeo = geo_buffer(stream);
+                    const K1zGeoLayout gl = k1z_geo_layout(g, ntiles, nb);
+                    char* gb = zgeo ? (char*)geo_reserve(stream, zgeo, gl.total, &e) : nullptr;
+                    if (!gb)
+                        return e != hipSuccess ? e : hipErrorOutOfMemory;
+                    fill_zgeom(zg, g, tg, ORDER, gb, gl);
+                    zg.parity = (int)(zgeo->parity & 1);
 #ifdef EDHIP_EXPERIMENTS
-                if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                    hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                        hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
 #endif
-            } else if (kK1) {
-                int off_small = 0;
-                (void)k1_lds_bytes(hg.ncpx, &hg.small_cap, &off_small, false);
-                if (fb.large_boxes)
-                    hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, true);
-                if (!hlds)
-                    hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, false);
-                tg.slack = (double*)(scratch + l.slack);
-                tg.slack_scale = box_margin_scale(g);
-                hg.slack = tg.slack;
+                } else if (kK1) {
+                    int off_small = 0;
+                    (void)k1_lds_bytes(hg.ncpx, &hg.small_cap, &off_small, false);
+                    if (fb.large_boxes)
+                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, true);
+                    if (!hlds)
+                        hlds = k1_lds_bytes(hg.ncpx, &hg.box_cap, &hg.off_box, false);
+                    tg.slack = (double*)(scratch + l.slack);
+                    tg.slack_scale = box_margin_scale(g);
+                    hg.slack = tg.slack;
 #ifdef EDHIP_EXPERIMENTS
-                if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                    hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                        hg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
 #endif
-            } else {
-                // the gradient (deform_hot.hip); forward, orders 4 / 5: only whether a box fits next to the Q rows at
-                // all is asked here -- the one-wave kernels below size their own
-                int off_small = 0;
-                (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.small_cap, &off_small, 0);
-                (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.large_cap, &off_small, 1);
-                if (fb.huge_boxes)
-                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 2);
-                if (!hlds && fb.large_boxes)
-                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 1);
-                if (!hlds)
-                    hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 0);
-            }
-            // (remains: whether a hot box fits next to the Q rows is the level-1 kernels' own arithmetic)
-            if (v.out16 && !hlds)
-                return hipErrorNotSupported;        // (nothing has been launched yet)
-            // (a wide grid whose window leaves no room for a hot box: the general kernels below, same tables)
-            hg.lds_grp = (int)((hlds + 15) & ~(size_t)15);
-            // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes live in a buffer of their own (nothing
-            // else writes it) under a host-side key of everything they depend on.
-            KeepKey* key = nullptr;
-            KeepKey cur;
-            memset(&cur, 0, sizeof(cur));
-            const int box_mode = batch ? batch->box_mode : 0;
-            if (hlds && box_mode && !ed_env("EDHIP_NO_BOXES")) {
-                hipError_t ke = hipSuccess;
-                int* kb = (int*)keep_reserve(stream, ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255, &key, &ke);
-                if (kb) {
-                    fill_keep_key(cur, g, tg, ORDER, *batch);
-                    if (!GRAD && box_mode == 1) {
-                        hg.boxes = kb;
-                        *key = KeepKey();                  // not valid until this launch is in the stream
-                    } else if (GRAD && box_mode == 2 && ORDER >= 3 && memcmp(key, &cur, sizeof(cur)) == 0) {
-                        // (orders 1 / 2: the box pass is a small part of a short tile, and the
-                        // hand-over's bookkeeping costs more than it saves: 190 -> 196, 242 -> 252 us)
-                        hg.boxes = kb;
-                        hg.use_boxes = 1;
-                        if (fb.self_serve_boxes && ORDER <= 3)
-                            hg.self_serve = 1;
+                } else {
+                    // the gradient (deform_hot.hip); forward, orders 4 / 5: only whether a box fits next to the Q rows at
+                    // all is asked here -- the one-wave kernels below size their own
+                    int off_small = 0;
+                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.small_cap, &off_small, 0);
+                    (void)hot_lds_bytes(GRAD, hg.ncpx, &hg.large_cap, &off_small, 1);
+                    if (fb.huge_boxes)
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 2);
+                    if (!hlds && fb.large_boxes)
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 1);
+                    if (!hlds)
+                        hlds = hot_lds_bytes(GRAD, hg.ncpx, &hg.box_cap, &hg.off_box, 0);
+                }
+                // (remains: whether a hot box fits next to the Q rows is the level-1 kernels' own arithmetic)
+                if (v.out16 && !hlds)
+                    return hipErrorNotSupported;        // (nothing has been launched yet)
+                // (a wide grid whose window leaves no room for a hot box: the general kernels below, same tables)
+                hg.lds_grp = (int)((hlds + 15) & ~(size_t)15);
+                // EDHIP_FLAG_KEEP_BOXES / USE_BOXES: the forward kernel's tile boxes live in a buffer of their own (nothing
+                // else writes it) under a host-side key of everything they depend on.
+                KeepKey* key = nullptr;
+                KeepKey cur;
+                memset(&cur, 0, sizeof(cur));
+                const int box_mode = batch ? batch->box_mode : 0;
+                if (hlds && box_mode && !ed_env("EDHIP_NO_BOXES")) {
+                    hipError_t ke = hipSuccess;
+                    int* kb = (int*)keep_reserve(stream, ((size_t)ntiles * nb * 8 * sizeof(int) + 255) & ~(size_t)255, &key, &ke);
+                    if (kb) {
+                        fill_keep_key(cur, g, tg, ORDER, *batch);
+                        if (!GRAD && box_mode == 1) {
+                            hg.boxes = kb;
+                            *key = KeepKey();                  // not valid until this launch is in the stream
+                        } else if (GRAD && box_mode == 2 && ORDER >= 3 && memcmp(key, &cur, sizeof(cur)) == 0) {
+                            // (orders 1 / 2: the box pass is a small part of a short tile, and the
+                            // hand-over's bookkeeping costs more than it saves: 190 -> 196, 242 -> 252 us)
+                            hg.boxes = kb;
+                            hg.use_boxes = 1;
+                            if (fb.self_serve_boxes && ORDER <= 3)
+                                hg.self_serve = 1;
+                        }
                     }
                 }
-            }
-            if (k1z && e == hipSuccess) {
-                // the geometry kernel in place of the tables kernel: R, the z table, tile records (and boxes), work lists
-                GridPrefilter gp;
-                const bool own = take_grid_prefilter(batch, nb, 0, gp);
-                e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
-                if (e == hipSuccess)
-                    ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
-                if (own && e == hipSuccess)
-                    batch->gridpf_done = true;
-                tables_done = true;
-            }
-            tables();
-            profile_mark(false, stream);
-            // Orders 4 / 5 run on the wave-per-tile kernels (deform_wave.hip: one wavefront per tile,
-            // one copy of the box, tiles that do not fit taken as two x-halves): the 4-wave kernels
-            // give up on a tile as soon as its 5- / 6-tap windows need the wide row pitch, and at
-            // these orders that is a large share of the tiles (256^3, sigma 5, whole call: order 4
-            // forward 419 -> 339 us, order 5 gradient 944 -> 886 us; profiles/r03_wave_vs_4wave.txt).
-            // Orders 1-3 stay on the 4-wave kernels, which are 10-30 % faster there.
-            int wave_mode = ORDER >= 4 ? 3 : 0;
+                if (k1z && e == hipSuccess) {
+                    // the geometry kernel in place of the tables kernel: R, the z table, tile records (and boxes), work lists
+                    GridPrefilter gp;
+                    const bool own = take_grid_prefilter(batch, nb, 0, gp);
+                    e = launch_k1z_geo(g, hg, zg, gp, nb, stream);
+                    if (e == hipSuccess)
+                        ++zgeo->parity;       // (the launch is in the stream: the next call uses the other counters)
+                    if (own && e == hipSuccess)
+                        batch->gridpf_done = true;
+                    tables_done = true;
+                }
+                tables();
+                profile_mark(false, stream);
+                // Orders 4 / 5 run on the wave-per-tile kernels (deform_wave.hip: one wavefront per tile,
+                // one copy of the box, tiles that do not fit taken as two x-halves): the 4-wave kernels
+                // give up on a tile as soon as its 5- / 6-tap windows need the wide row pitch, and at
+                // these orders that is a large share of the tiles (256^3, sigma 5, whole call: order 4
+                // forward 419 -> 339 us, order 5 gradient 944 -> 886 us; profiles/r03_wave_vs_4wave.txt).
+                // Orders 1-3 stay on the 4-wave kernels, which are 10-30 % faster there.
+                int wave_mode = ORDER >= 4 ? 3 : 0;
 #ifdef EDHIP_EXPERIMENTS
-            if (const char* wm = ed_env("EDHIP_WAVE"))        // 1 forward, 2 gradient, 3 both, 0 neither
-                wave_mode = atoi(wm);
+                if (const char* wm = ed_env("EDHIP_WAVE"))        // 1 forward, 2 gradient, 3 both, 0 neither
+                    wave_mode = atoi(wm);
 #endif
-            if ((hlds || wide_wave) && (wave_mode & (GRAD ? 2 : 1))) {
-                HotGeom wg = hg;
-                wg.self_serve = 0;
-                int wstart = 4;
+                if ((hlds || wide_wave) && (wave_mode & (GRAD ? 2 : 1))) {
+                    HotGeom wg = hg;
+                    wg.self_serve = 0;
+                    int wstart = 4;
 #ifdef EDHIP_EXPERIMENTS
-                if (const char* st = ed_env("EDHIP_WAVE_STRIP"))
-                    wstart = atoi(st);
+                    if (const char* st = ed_env("EDHIP_WAVE_STRIP"))
+                        wstart = atoi(st);
 #endif
-                const int64_t across = (int64_t)tg.tiles[0] * tg.tiles[1];
-                wg.strip_tiles = shorten_strips(wstart, 1, 8192, nb, across, tg.tiles[2]);
-                wg.strips_x = (tg.tiles[2] + wg.strip_tiles - 1) / wg.strip_tiles;
-                const int64_t wstrips = strip_count(1, across, tg.tiles[2], wg.strip_tiles);
-                // (no more strips than tiles, which the prologue has bounded)
-                if (wstrips * nb <= 0x3fffffffLL) {
-                    wg.nstrips = (int)wstrips;
-                    wg.total_strips = (int)(wstrips * nb);
-                    int occ = 3;
+                    const int64_t across = (int64_t)tg.tiles[0] * tg.tiles[1];
+                    wg.strip_tiles = shorten_strips(wstart, 1, 8192, nb, across, tg.tiles[2]);
+                    wg.strips_x = (tg.tiles[2] + wg.strip_tiles - 1) / wg.strip_tiles;
+                    const int64_t wstrips = strip_count(1, across, tg.tiles[2], wg.strip_tiles);
+                    // (no more strips than tiles, which the prologue has bounded)
+                    if (wstrips * nb <= 0x3fffffffLL) {
+                        wg.nstrips = (int)wstrips;
+                        wg.total_strips = (int)(wstrips * nb);
+                        int occ = 3;
 #ifdef EDHIP_EXPERIMENTS
-                    if (const char* oc = ed_env("EDHIP_WAVE_OCC"))
-                        occ = atoi(oc);
+                        if (const char* oc = ed_env("EDHIP_WAVE_OCC"))
+                            occ = atoi(oc);
 #endif
-                    size_t wlds = wave_lds_bytes(GRAD, occ, &wg.box_cap);
-                    // spill feedback: larger boxes (fewer waves per CU) once the geometry's calls spill.
-                    // 256^3 sigma 10, whole call: order 4 forward 453 -> 420 us, gradient 694 -> 662;
-                    // order 5 forward 1019 -> 657, gradient 1238 -> 1055 (sigma 5: +20 .. +40 us)
-                    wg.small_cap = wg.box_cap;
-                    if (fb.large_boxes) {
-                        wlds = (ORDER == 5 && !GRAD) ? 20480 : 16384;
-                        wg.box_cap = (int)((wlds - 416) / 4);
+                        size_t wlds = wave_lds_bytes(GRAD, occ, &wg.box_cap);
+                        // spill feedback: larger boxes (fewer waves per CU) once the geometry's calls spill.
+                        // 256^3 sigma 10, whole call: order 4 forward 453 -> 420 us, gradient 694 -> 662;
+                        // order 5 forward 1019 -> 657, gradient 1238 -> 1055 (sigma 5: +20 .. +40 us)
+                        wg.small_cap = wg.box_cap;
+                        if (fb.large_boxes) {
+                            wlds = (ORDER == 5 && !GRAD) ? 20480 : 16384;
+                            wg.box_cap = (int)((wlds - 416) / 4);
+                        }
+#ifdef EDHIP_EXPERIMENTS
+                        if (const char* kb = ed_env("EDHIP_WAVE_LDS")) {
+                            wlds = (size_t)atoi(kb);
+                            wg.box_cap = (int)((wlds - 416) / 4);
+                        }
+                        if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
+                            wg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
+#endif
+                        const unsigned wblk = (unsigned)(((wstrips * nb + 7) / 8) * 8);
+                        const hipError_t he = launch_wave_level1(wg, ORDER, GRAD, wblk, wlds, occ, stream);
+                        if (he == hipSuccess) {
+                            hot_done = true;
+                            if (!GRAD && hg.boxes && key)
+                                *key = cur;
+                        } else if (he != hipErrorNotSupported || wide_wave)
+                            e = he;
                     }
-#ifdef EDHIP_EXPERIMENTS
-                    if (const char* kb = ed_env("EDHIP_WAVE_LDS")) {
-                        wlds = (size_t)atoi(kb);
-                        wg.box_cap = (int)((wlds - 416) / 4);
-                    }
-                    if (const char* pp = ed_env("EDHIP_DEBUG_PTR"))
-                        wg.dbgbuf = (unsigned long long*)strtoull(pp, nullptr, 16);
-#endif
-                    const unsigned wblk = (unsigned)(((wstrips * nb + 7) / 8) * 8);
-                    const hipError_t he = launch_wave_level1(wg, ORDER, GRAD, wblk, wlds, occ, stream);
+                }
+                // (remains: whether the one-wave kernels take a call is launch_wave_level1's own answer)
+                if (wide_wave && !hot_done && e == hipSuccess)
+                    e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
+                if (hlds && !hot_done && e == hipSuccess) {
+                    // (forward, orders 4 / 5, when the one-wave kernels did not take the call: the general kernels below)
+                    hipError_t he = hipErrorNotSupported;
+                    if (k1z)
+                        he = launch_k1z(hg, zg, ORDER, hlds, stream);
+                    else if (kK1)
+                        he = launch_k1_level1(hg, ORDER, nblk, hlds, stream);
+                    else if (GRAD)
+                        he = launch_hot_grad_level1(hg, ORDER, nblk, hlds, stream);
                     if (he == hipSuccess) {
                         hot_done = true;
+                        served_all = hg.self_serve != 0 || k1z;
                         if (!GRAD && hg.boxes && key)
                             *key = cur;
-                    } else if (he != hipErrorNotSupported || wide_wave)
+                    } else if (he != hipErrorNotSupported || v.out16 || wide)
                         e = he;
                 }
             }
-            // (remains: whether the one-wave kernels take a call is launch_wave_level1's own answer)
-            if (wide_wave && !hot_done && e == hipSuccess)
-                e = hipErrorNotSupported;        // (no other level-1 kernel can take a grid this wide)
-            if (hlds && !hot_done && e == hipSuccess) {
-                // (forward, orders 4 / 5, when the one-wave kernels did not take the call: the general kernels below)
-                hipError_t he = hipErrorNotSupported;
-                if (k1z)
-                    he = launch_k1z(hg, zg, ORDER, hlds, stream);
-                else if (kK1)
-                    he = launch_k1_level1(hg, ORDER, nblk, hlds, stream);
-                else if (GRAD)
-                    he = launch_hot_grad_level1(hg, ORDER, nblk, hlds, stream);
-                if (he == hipSuccess) {
-                    hot_done = true;
-                    served_all = hg.self_serve != 0 || k1z;
-                    if (!GRAD && hg.boxes && key)
-                        *key = cur;
-                } else if (he != hipErrorNotSupported || v.out16 || wide)
-                    e = he;
+        }
+        if (!tables_done) {
+            tables();
+            profile_mark(false, stream);
+        }
+        // the general level-1 kernels, where no kernel above took the call.  (A failure up to here is returned as it
+        // is: nothing more is launched behind it, and hipGetLastError() is asked only about a launch that was made.)
+        const bool general = !hot_done && e == hipSuccess;
+        if (!general)
+            ;
+        else if (GRAD)
+            hipLaunchKernelGGL((deform_tile3_grad_kernel<T, ORDER, 16>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg);
+#ifdef EDHIP_EXPERIMENTS
+        else if (kBenchKernel && tg.dbg) {
+            if constexpr (kBenchKernel) {
+            // profiling builds of the benchmark kernel (EDHIP_TILE_DBG), never used otherwise
+            switch (tg.dbg) {
+            case 2: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 2>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            case 4: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 4>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            case 6: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 6>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            case 16: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 16>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            case 64: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 64>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            case 38: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 38>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            default: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 0>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
+            }
             }
         }
-    }
-    if (!tables_done) {
-        tables();
-        profile_mark(false, stream);
-    }
-    if (hot_done || e != hipSuccess)
-        ;
-    else if (GRAD)
-        hipLaunchKernelGGL((deform_tile3_grad_kernel<T, (ORDER < 1 ? 2 : ORDER), 16>), dim3(nblk),
-                           dim3(kBlock), lds, stream, g, ve, tg);
-#ifdef EDHIP_EXPERIMENTS
-    else if (kBenchKernel && tg.dbg) {
-        if constexpr (kBenchKernel) {
-        // profiling builds of the benchmark kernel (EDHIP_TILE_DBG), never used otherwise
-        switch (tg.dbg) {
-        case 2: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 2>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        case 4: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 4>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        case 6: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 6>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        case 16: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 16>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        case 64: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 64>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        case 38: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 38>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        default: hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR, 0>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg); break;
-        }
-        }
-    }
 #endif
-    else
-        hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR>), dim3(nblk), dim3(kBlock),
-                           lds, stream, g, ve, tg);
-    e = hipGetLastError();
-    profile_mark(true, stream);
-    if (served_all)
-        return e;               // level 1 has served every tile
-    if (e != hipSuccess)
-        return e;
-    // (plain tables of a wide grid: straight to the direct level, the level-2 kernel stages Q rows like the others)
-    return launch_spill_levels<T, ORDER, GRAD>(g, ve, tg, wide_wave, stream);
+        else
+            hipLaunchKernelGGL((deform_tile3_fwd_kernel<T, ORDER, PAIR>), dim3(nblk), dim3(kBlock), lds, stream, g, ve, tg);
+        if (general)
+            e = hipGetLastError();
+        profile_mark(true, stream);
+        if (served_all || e != hipSuccess)
+            return e;               // level 1 has served every tile, or failed
+        // (plain tables of a wide grid: straight to the direct level, the level-2 kernel stages Q rows like the others)
+        return launch_spill_levels<T, ORDER, GRAD>(g, ve, tg, wide_wave, stream);
+    }
 }
 
 

@@ -1273,12 +1273,16 @@ hipError_t launch_wave_occ(const HotGeom& hg, bool gradient, unsigned nblk, size
 template <int ORDER>
 hipError_t launch_wave_order(const HotGeom& hg, bool gradient, unsigned nblk, size_t lds, int occ, hipStream_t stream)
 {
-#ifdef EDHIP_EXPERIMENTS
-    if (occ == 4)
-        return launch_wave_occ<ORDER, 4>(hg, gradient, nblk, lds, stream);
-#endif
-    (void)occ;
-    return launch_wave_occ<ORDER, 3>(hg, gradient, nblk, lds, stream);
+    // The shipped rule (launch_tile_float: wave_mode) sends orders 4 and 5 here, at occ 3; orders 1-3
+    // and occ 4 are the experiments builds' A/B switches (EDHIP_WAVE, EDHIP_WAVE_OCC).
+    if constexpr (kEdExperiments) {
+        if (occ == 4)
+            return launch_wave_occ<ORDER, 4>(hg, gradient, nblk, lds, stream);
+    }
+    if constexpr (ORDER >= 4 || kEdExperiments)
+        return launch_wave_occ<ORDER, 3>(hg, gradient, nblk, lds, stream);
+    else
+        return hipErrorNotSupported;
 }
 
 }  // namespace

@@ -17,11 +17,15 @@
 // Environment switches (kernel selection, ablations, debugging aids) exist only in EDHIP_EXPERIMENTS
 // builds (`make EXPERIMENTS=1`, used by tools/ on the GPU box).  The shipped library never calls
 // getenv: no environment variable can change what it launches or returns.
+// kEdExperiments: a dispatch keeps the kernels that only a switch can reach behind `if constexpr (kEdExperiments)`,
+// so the shipped library holds the kernels its launchers can reach and no others (tests/kernel_set.txt).
 #ifdef EDHIP_EXPERIMENTS
 #include <cstdlib>
 inline const char* ed_env(const char* name) { return getenv(name); }
+constexpr bool kEdExperiments = true;
 #else
 inline const char* ed_env(const char*) { return nullptr; }
+constexpr bool kEdExperiments = false;
 #endif
 
 namespace ed {

@@ -1935,3 +1935,57 @@ def test_grid_stamp_does_not_outlive_its_workspace():
         call(out2, _lib.FLAG_GRID_STAYS)
         stream_obj.synchronize()
     assert torch.equal(out1, out2)
+
+
+# ---- the kernel classes the tile launcher keeps (tests/kernel_set.txt, profiles/kernel_set_audit.txt) ------------------
+def _fwd_and_grad_vs_oracle(X, disp, kw, seed):
+    """Forward and gradient of one float volume against the CPU oracle, with the bounds of
+    test_forward_and_gradient_vs_golden.  The flat bound of _f32_grad_check compares two float32 evaluations, so it says
+    something only where the reference's own is well inside it: the input must leave the reference within HALF the flat
+    bound of the exact gradient (then an evaluation as accurate as the reference's meets the bound), and that is
+    asserted here, of the reference alone, before anything is asked of the GPU's gradient."""
+    want = orc.deform_grid(X, disp, **kw)
+    _check(ed.deform_grid(X, disp, **kw), want, exact_floats=False)
+    dY = np.random.default_rng(seed).standard_normal(want.shape).astype(X.dtype)
+    gw = orc.deform_grid_gradient(dY, disp, **kw)
+    gg = ed.deform_grid_gradient(dY, disp, **kw)
+    assert gg.dtype == gw.dtype and gg.shape == gw.shape
+    if X.dtype == np.float32:
+        truth = orc.deform_grid_gradient(dY.astype(np.float64), disp, **kw)
+        scale = max(1.0, float(np.abs(truth).max()))
+        err_ref = float(np.abs(gw.astype(np.float64) - truth).max())
+        assert err_ref <= 0.5 * 1e-5 * scale, ("the reference's own float32 error leaves the flat bound no room", err_ref, scale)
+        _f32_grad_check(gg, gw, truth, flat=True)
+    else:
+        np.testing.assert_allclose(gg, gw, rtol=1e-10, atol=1e-10)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_order_0_float_volume_on_the_direct_launcher(dtype):
+    """deform_tile3_direct_kernel<T, 0, GRAD, false>: order 0 on a float volume of 3 x 3 x 5 tiles, every tile in one
+    launch straight from / to global memory, forward and gradient."""
+    rng = np.random.default_rng(2400 + np.dtype(dtype).itemsize)
+    X = rng.random((24, 24, 40)).astype(dtype)
+    disp = rng.standard_normal((3, 3, 3, 3)) * 3.0
+    _fwd_and_grad_vs_oracle(X, disp, dict(order=0, mode="nearest"), 24)
+
+
+@pytest.mark.parametrize("order", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_level_3_takes_the_tiles_no_box_holds(dtype, order):
+    """deform_tile3_direct_kernel<T, 1..5, GRAD, true>: sigma 30 on a 40^3 volume folds nearly every tile's sources over
+    the whole volume, further than the boxes of level 1 and level 2 reach, and level 3 takes them through global memory
+    (the tiles per level of this very geometry: profiles/kernel_set_device_code.txt).
+
+    Without the prefilter.  With it the reference's float32 gradient (its transposed prefilter is rounded to float32
+    after every axis) is itself 6.4e-6 / 6.9e-6 / 2.7e-5 of the gradient's scale from the exact gradient at orders
+    3 / 4 / 5 -- at order 5 further than the whole flat bound of 1e-5, so that no float32 evaluation can be expected within
+    the bound of it: on the MI355X that input passed 9 of the 10 cases and at [float32-5] met the measured bound (3.9e-4
+    from the exact gradient, the reference 1.27e-3) and missed the flat one (|gpu - reference| 1.25e-3 against
+    4.64e-4).  Without the prefilter the reference is 4.9e-7 to 3.9e-6 of the scale from the exact gradient at every
+    order, inside half the flat bound (_fwd_and_grad_vs_oracle asserts it).  The prefilter is no part of the level-3
+    kernel; the geometry, the displacement field and both bounds are unchanged."""
+    rng = np.random.default_rng(4000 + order)
+    X = rng.random((40, 40, 40)).astype(dtype)
+    disp = rng.standard_normal((3, 3, 3, 3)) * 30.0
+    _fwd_and_grad_vs_oracle(X, disp, dict(order=order, mode="nearest", prefilter=False), 40 + order)
